@@ -12,6 +12,11 @@ in HBM.  Frame pairs shard across ranks (pair i -> rank i mod N, weak scaling);
 after each step the ranks all-gather their detection records with RCCL through the
 package's own C-ABI (dodt_comm_*, include/dodt_hip.h) on a side stream.  No PyTorch is
 imported.  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps and prints the headline line (`ms_per_step`: one
+timed step).  --full adds everything else measured beside it: the CPU baseline, the other arithmetics /
+batchings / configurations (`alt`), the conv stacks and HBM-bound kernels alone (`roofline`).
+--dump-outputs DIR writes the detection records of the last timed step (rank 0's) as DIR/*.npy, float32.
 """
 import argparse
 import json
@@ -68,6 +73,12 @@ def parse():
     ap.add_argument('--late-peer-ms', type=float, default=0.0,
                     help='experiment (with --comm): a device-side delay of this many ms in front of every gather on '
                          "the stream that carries the collectives -- a peer that arrives late at the rendezvous")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: CPU baseline, alt runs, roofline '
+                         '(--no-cpu-baseline / --no-alt still drop parts of it)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's detection records (what a caller of the pipeline receives) "
+                         'as DIR/records.npy and DIR/record_counts.npy, float32')
     return ap.parse_args()
 
 
@@ -302,12 +313,12 @@ def main():
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     n_gpus = max(args.gpus, 1)
     baseline = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         # first, while the GPU is still untouched: the workers are spawned processes
         baseline = cpu_baseline(args.heads == 'computed', args.cpu_pairs)
 
     m_pool, m_cores = None, _usable_cores()
-    if not args.no_alt and world == 1 and args.config == 'dodt' and args.heads == 'computed':
+    if args.full and not args.no_alt and world == 1 and args.config == 'dodt' and args.heads == 'computed':
         # the temporal module's workers: spawned now, while the GPU is untouched, idle until alt.temporal_host
         import multiprocessing as mp
         m_pool = mp.get_context('spawn').Pool(m_cores)
@@ -396,10 +407,12 @@ def main():
 
     def measure(conv_dtype, steps, warmup, head_dtype='f32', cfg=cfg, proposals=args.proposals,
                 from_host=False, pps=args.pairs_per_step, detail=False, hbm_detail=False, points=args.points,
-                tau=args.tau, n_boxes=args.boxes, computed=computed, keep_records=0):
-        """`steps` timed steps of the pipeline built for conv_dtype; with detail, then the conv
-        stacks alone layer by layer (roofline); with hbm_detail the HBM-bound kernels alone.
-        keep_records: download the records of that many of the last steps (for the host's temporal module)."""
+                tau=args.tau, n_boxes=args.boxes, computed=computed, keep_records=0, conv_alone=True,
+                last_outputs=False):
+        """`steps` timed steps of the pipeline built for conv_dtype; with conv_alone, then the conv stacks
+        alone (conv_ms); with detail, also layer by layer (roofline); with hbm_detail the HBM-bound kernels alone.
+        keep_records: download the records of that many of the last steps (for the host's temporal module).
+        last_outputs: download the last timed step's records and counts (res['outputs'])."""
         fps = cfg['frames_per_sample']
         feat_c = 256 if cfg['extractor'] == 'vgg' else 32
         pipe = FramePairPipeline(ctx, cfg, **synth.pipeline_weights(cfg),
@@ -556,6 +569,14 @@ def main():
                 for j in range(pps):
                     c_ = cring[k_ % (2 * G), j]
                     res['records'].append(np.concatenate([ring[k_ % (2 * G), j, f, :c_[f]] for f in range(fps)]))
+        if last_outputs:
+            # the last timed step's records as a caller gets them: the rows past a frame's count are not its
+            # detections and are written as zeros
+            slot = (pipe.step_idx - 1) % (2 * G)
+            rec, cnt = rec_ring.download()[slot], cnt_ring.download()[slot]
+            valid = np.arange(MAX_DET)[None, None, :, None] < cnt[:, :, None, None]
+            res['outputs'] = {'records': np.where(valid, rec, np.float32(0)).astype(np.float32),
+                              'record_counts': cnt.astype(np.float32)}
         if comm is not None and rank == 0 and state['last_block'] is not None:
             # the exchange really happened: rank 0's own part of the last message equals its records
             b = state['last_block']
@@ -567,20 +588,21 @@ def main():
 
         # ---- the conv stacks alone (each net by itself on its own stream, so that kernel
         #      durations do not overlap), layer by layer: HIP events on the stream the kernels run on
-        reps = max(3, min(steps, 10))
-        # (the stand-alone forwards read the inputs the last steps left in the pipeline's buffers)
-        pipe.bev_net.set_input(pipe.in_bev[0])
-        pipe.img_net.set_input(pipe.in_img[0])
-        nets = ((pipe.bev_net, ctx, pipe.feat[0]['bev_feat'], pipe.feat[0]['bev_bneck']),
-                (pipe.img_net, pipe.img_ctx, pipe.feat[0]['img_feat'], pipe.feat[0]['img_bneck']))
-        conv_ms = 0.0
-        for net, c, f, b in nets:
-            c.sync()
-            c.timer_start()
-            for _ in range(reps):
-                net.forward_device(None, f, b)
-            conv_ms += c.timer_stop() / reps
-        res.update(conv_ms=conv_ms, reps=reps)
+        if conv_alone or detail:
+            reps = max(3, min(steps, 10))
+            # (the stand-alone forwards read the inputs the last steps left in the pipeline's buffers)
+            pipe.bev_net.set_input(pipe.in_bev[0])
+            pipe.img_net.set_input(pipe.in_img[0])
+            nets = ((pipe.bev_net, ctx, pipe.feat[0]['bev_feat'], pipe.feat[0]['bev_bneck']),
+                    (pipe.img_net, pipe.img_ctx, pipe.feat[0]['img_feat'], pipe.feat[0]['img_bneck']))
+            conv_ms = 0.0
+            for net, c, f, b in nets:
+                c.sync()
+                c.timer_start()
+                for _ in range(reps):
+                    net.forward_device(None, f, b)
+                conv_ms += c.timer_stop() / reps
+            res.update(conv_ms=conv_ms, reps=reps)
         if detail:
             layers = []
             for net, c, f, b in nets:
@@ -670,11 +692,16 @@ def main():
         gc.collect()
         gc.freeze()
     pps = args.pairs_per_step
-    m = measure(args.conv_dtype, args.steps, args.warmup, args.head_dtype, detail=True, hbm_detail=True,
-                keep_records=16)
-    elapsed, host_enqueue_ms, conv_ms, reps = m['elapsed'], m['host_enqueue_ms'], m['conv_ms'], m['reps']
+    m = measure(args.conv_dtype, args.steps, args.warmup, args.head_dtype, detail=args.full, hbm_detail=args.full,
+                keep_records=16 if args.full else 0, conv_alone=args.full,
+                last_outputs=args.dump_outputs is not None and rank == 0)
+    elapsed, host_enqueue_ms = m['elapsed'], m['host_enqueue_ms']
+    if 'outputs' in m:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in m['outputs'].items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
     alt = None
-    if not args.no_alt and world == 1:      # (N > 1 runs measure the sharded path only)
+    if args.full and not args.no_alt and world == 1:      # (N > 1 runs measure the sharded path only)
         # other arithmetics / batchings of the same workload, shorter runs: reported beside the
         # main measurement, never part of `value`
         # (at least 60 steps behind 10 warm-up steps each: round 3's alt runs were 10 steps behind 2 and read 8 % low)
@@ -762,71 +789,74 @@ def main():
             m_pool.join()
 
     # ---- roofline of the dominant kernel ---------------------------------------------------------
-    # Everything below is measured in this run with HIP events on the streams the kernels run on;
-    # only the PMC byte counts come from the rocprofv3 --pmc passes over this same command
-    # (profiles/), because counters cannot be read from inside the process.
-    by_kernel = _group_by_kernel(m['layers'])
-    dom = max(by_kernel.values(), key=lambda k_: k_['ms'])
-    n_launch = sum(k_['launches'] for k_ in by_kernel.values())
-    layers_ms = sum(k_['ms'] for k_ in by_kernel.values())
-    peak = FP32_MFMA_PEAK if args.conv_dtype == 'f32' else BF16_MFMA_PEAK
-    # (written by tools/summarize_profile.py with the head they were taken at: `traffic_head`)
-    tj = _profile_json('conv_traffic_%s.json' % args.conv_dtype)
-    traffic = tj['kernels'].get(dom['kernel']) if tj else None
-    kernels = []
-    for k_ in sorted(by_kernel.values(), key=lambda k_: -k_['ms']):
-        tf = k_['flops_executed'] / (k_['ms'] * 1e-3) / 1e12
-        kernels.append(dict(kernel=k_['kernel'], launches_per_step=k_['launches'], ms_per_step=round(k_['ms'], 4),
-                            avg_launch_us=round(k_['ms'] * 1e3 / k_['launches'], 2),
-                            executed_gflop=round(k_['flops_executed'] / 1e9, 2), executed_tflops=round(tf, 2),
-                            frac=round(tf / peak, 4),
-                            direct_equivalent_tflops=round(k_['flops_direct'] / (k_['ms'] * 1e-3) / 1e12, 2),
-                            algorithmic_gbps=round(k_['bytes'] / (k_['ms'] * 1e-3) / 1e9, 1),
-                            layers=k_['layers']))
-    d = kernels[0]
-    all_tf = m['mfma_flops'] / (layers_ms * 1e-3) / 1e12
-    roofline = dict(
-        bound='mfma', kernel=d['kernel'], launches_per_step=d['launches_per_step'],
-        avg_launch_us=d['avg_launch_us'],
-        # executed MFMA FLOPs of the dominant kernel's launches / their stand-alone duration
-        achieved=d['executed_tflops'], peak=peak, unit='TFLOP/s', frac=d['frac'],
-        algorithmic_gflop_per_launch=round(d['executed_gflop'] / d['launches_per_step'], 3),
-        direct_equivalent_tflops=d['direct_equivalent_tflops'],
-        traffic=(round(traffic['fetch_bytes_per_launch'] + traffic['write_bytes_per_launch'])
-                 if traffic else None),
-        traffic_unit='bytes/launch', traffic_source=tj['source'] if tj else None,
-        traffic_head=tj.get('head') if tj else None,
-        algorithmic_bytes_per_launch=round(by_kernel[d['kernel']]['bytes'] / d['launches_per_step']),
-        arithmetic={'f32': 'fp32 MFMA (v_mfma_f32_16x16x4_f32 / 32x32x2), peak 157.3 TFLOP/s dense',
-                    'f32s': 'three bf16 MFMAs per product term (split mode), fp32 accumulate',
-                    'bf16': 'bf16 MFMA, fp32 accumulate'}[args.conv_dtype],
-        measured='HIP event pair around every layer, each net alone on its stream, %d forwards after the '
-                 'timed region; frac = executed MFMA FLOPs / time / peak' % reps,
-        conv_stacks=dict(launches_per_step=n_launch, ms=round(conv_ms, 4), layers_ms=round(layers_ms, 4),
-                         executed_gflop=round(m['mfma_flops'] / 1e9, 2), executed_tflops=round(all_tf, 2),
-                         frac=round(all_tf / peak, 4),
-                         direct_gflop=round(m['flops'] / 1e9, 2),
-                         direct_equivalent_tflops=round(m['flops'] / (conv_ms * 1e-3) / 1e12, 2),
-                         algorithmic_mbytes=round(m['conv_bytes'] / 1e6, 1),
-                         side_by_side_ms=round(m['both_ms'], 4),
-                         side_by_side_direct_equivalent_tflops=round(m['flops'] / (m['both_ms'] * 1e-3) / 1e12, 2)),
-        kernels=kernels,
-        # (a layer with no launch of its own -- conv1_1 folded into conv1_2's launch on the bf16 conv path -- lists its
-        #  FLOPs with `us` null: its time is inside the next row's)
-        layers=[dict(net='bev' if i < len(m['layers']) // 2 else 'img', name=l['name'], kernel=l['kernel'],
-                     items=l['items'], us=round(l['ms'] * 1e3, 1) if l['launches'] else None,
-                     executed_tflops=round(l['flops_executed'] / (l['ms'] * 1e-3) / 1e12, 1) if l['launches'] else None,
-                     **({} if l['launches'] else {'folded_into_next': True}))
-                for i, l in enumerate(m['layers'])])
-    hbm = m.get('hbm')
-    if hbm:
-        hj = _profile_json('hbm_traffic.json')
-        for h in hbm:
-            t = hj['kernels'].get(h['kernel']) if hj else None
-            h['traffic'] = round(t['fetch_bytes'] + t['write_bytes']) if t else None
-            h['traffic_source'] = hj['source'] if (hj and t) else None
-            h['traffic_head'] = hj.get('head') if (hj and t) else None
-        roofline['hbm'] = hbm
+    roofline = None
+    if args.full:
+        # Everything below is measured in this run with HIP events on the streams the kernels run on;
+        # only the PMC byte counts come from the rocprofv3 --pmc passes over this same command
+        # (profiles/), because counters cannot be read from inside the process.
+        conv_ms, reps = m['conv_ms'], m['reps']
+        by_kernel = _group_by_kernel(m['layers'])
+        dom = max(by_kernel.values(), key=lambda k_: k_['ms'])
+        n_launch = sum(k_['launches'] for k_ in by_kernel.values())
+        layers_ms = sum(k_['ms'] for k_ in by_kernel.values())
+        peak = FP32_MFMA_PEAK if args.conv_dtype == 'f32' else BF16_MFMA_PEAK
+        # (written by tools/summarize_profile.py with the head they were taken at: `traffic_head`)
+        tj = _profile_json('conv_traffic_%s.json' % args.conv_dtype)
+        traffic = tj['kernels'].get(dom['kernel']) if tj else None
+        kernels = []
+        for k_ in sorted(by_kernel.values(), key=lambda k_: -k_['ms']):
+            tf = k_['flops_executed'] / (k_['ms'] * 1e-3) / 1e12
+            kernels.append(dict(kernel=k_['kernel'], launches_per_step=k_['launches'], ms_per_step=round(k_['ms'], 4),
+                                avg_launch_us=round(k_['ms'] * 1e3 / k_['launches'], 2),
+                                executed_gflop=round(k_['flops_executed'] / 1e9, 2), executed_tflops=round(tf, 2),
+                                frac=round(tf / peak, 4),
+                                direct_equivalent_tflops=round(k_['flops_direct'] / (k_['ms'] * 1e-3) / 1e12, 2),
+                                algorithmic_gbps=round(k_['bytes'] / (k_['ms'] * 1e-3) / 1e9, 1),
+                                layers=k_['layers']))
+        d = kernels[0]
+        all_tf = m['mfma_flops'] / (layers_ms * 1e-3) / 1e12
+        roofline = dict(
+            bound='mfma', kernel=d['kernel'], launches_per_step=d['launches_per_step'],
+            avg_launch_us=d['avg_launch_us'],
+            # executed MFMA FLOPs of the dominant kernel's launches / their stand-alone duration
+            achieved=d['executed_tflops'], peak=peak, unit='TFLOP/s', frac=d['frac'],
+            algorithmic_gflop_per_launch=round(d['executed_gflop'] / d['launches_per_step'], 3),
+            direct_equivalent_tflops=d['direct_equivalent_tflops'],
+            traffic=(round(traffic['fetch_bytes_per_launch'] + traffic['write_bytes_per_launch'])
+                     if traffic else None),
+            traffic_unit='bytes/launch', traffic_source=tj['source'] if tj else None,
+            traffic_head=tj.get('head') if tj else None,
+            algorithmic_bytes_per_launch=round(by_kernel[d['kernel']]['bytes'] / d['launches_per_step']),
+            arithmetic={'f32': 'fp32 MFMA (v_mfma_f32_16x16x4_f32 / 32x32x2), peak 157.3 TFLOP/s dense',
+                        'f32s': 'three bf16 MFMAs per product term (split mode), fp32 accumulate',
+                        'bf16': 'bf16 MFMA, fp32 accumulate'}[args.conv_dtype],
+            measured='HIP event pair around every layer, each net alone on its stream, %d forwards after the '
+                     'timed region; frac = executed MFMA FLOPs / time / peak' % reps,
+            conv_stacks=dict(launches_per_step=n_launch, ms=round(conv_ms, 4), layers_ms=round(layers_ms, 4),
+                             executed_gflop=round(m['mfma_flops'] / 1e9, 2), executed_tflops=round(all_tf, 2),
+                             frac=round(all_tf / peak, 4),
+                             direct_gflop=round(m['flops'] / 1e9, 2),
+                             direct_equivalent_tflops=round(m['flops'] / (conv_ms * 1e-3) / 1e12, 2),
+                             algorithmic_mbytes=round(m['conv_bytes'] / 1e6, 1),
+                             side_by_side_ms=round(m['both_ms'], 4),
+                             side_by_side_direct_equivalent_tflops=round(m['flops'] / (m['both_ms'] * 1e-3) / 1e12, 2)),
+            kernels=kernels,
+            # (a layer with no launch of its own -- conv1_1 folded into conv1_2's launch on the bf16 conv path -- lists its
+            #  FLOPs with `us` null: its time is inside the next row's)
+            layers=[dict(net='bev' if i < len(m['layers']) // 2 else 'img', name=l['name'], kernel=l['kernel'],
+                         items=l['items'], us=round(l['ms'] * 1e3, 1) if l['launches'] else None,
+                         executed_tflops=round(l['flops_executed'] / (l['ms'] * 1e-3) / 1e12, 1) if l['launches'] else None,
+                         **({} if l['launches'] else {'folded_into_next': True}))
+                    for i, l in enumerate(m['layers'])])
+        hbm = m.get('hbm')
+        if hbm:
+            hj = _profile_json('hbm_traffic.json')
+            for h in hbm:
+                t = hj['kernels'].get(h['kernel']) if hj else None
+                h['traffic'] = round(t['fetch_bytes'] + t['write_bytes']) if t else None
+                h['traffic_source'] = hj['source'] if (hj and t) else None
+                h['traffic_head'] = hj.get('head') if (hj and t) else None
+            roofline['hbm'] = hbm
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -870,8 +900,9 @@ def main():
                                                                'FAILED, no records exchanged, host barrier only: ' + comm_error),
                        'conv_mode': os.environ.get('DODT_CONV_WINO', 'default'),
                        'anchors_kept': m['anchors']},
-            'roofline': roofline,
         }
+        if roofline is not None:
+            out['roofline'] = roofline
         if alt is not None:
             out['alt'] = alt
         if baseline is not None:

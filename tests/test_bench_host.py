@@ -54,3 +54,14 @@ def test_temporal_worker_on_synthetic_records():
     assert bench._temporal_worker((None, 0, 0)) == (0.0, 0)
     out = bench.temporal_host(None, 1, recs, 2, 100.0)
     assert out['one_thread_pairs_per_s'] > 0 and 'pool_pairs_per_s' not in out
+
+
+def test_plain_run_is_lean_unless_full(monkeypatch):
+    """A plain run times the headline only: --full (off by default) brings back the CPU baseline, the alt runs and
+    the roofline; --dump-outputs names the folder of the last timed step's records."""
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', 'out'])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == 'out'

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condense rocprofv3 outputs (gpurun_out/<tag>_stats, _pmc_mfma, _pmc_fetch, _pmc_write of
+"""Condense rocprofv3 outputs ($DODT_PROFILE_DIR, default profile_out/: <tag>_stats, _pmc_mfma, _pmc_fetch, _pmc_write of
 one `bench.py` command) into profiles/<tag>_*.  Usage: summarize_profile.py r1"""
 import collections
 import csv
@@ -16,12 +16,13 @@ def is_conv(name):
 
 tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+prof = os.environ.get('DODT_PROFILE_DIR', 'profile_out')     # where tools/profile_*.sh wrote
 out = os.path.join(root, 'profiles')
 os.makedirs(out, exist_ok=True)
 
 
 def one(pattern):
-    hits = glob.glob(os.path.join(root, 'gpurun_out', pattern), recursive=True)
+    hits = glob.glob(os.path.join(root, prof, pattern), recursive=True)
     return hits[0] if hits else None
 
 
@@ -29,7 +30,7 @@ stats = one('%s_stats/**/*kernel_stats.csv' % tag)
 shutil.copy(stats, os.path.join(out, '%s_kernel_stats.csv' % tag))
 rows = list(csv.DictReader(open(stats)))
 extra = ' '.join(sys.argv[2:])
-lines = ['# %s: rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-alt %s' % (tag, extra), '',
+lines = ['# %s: rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-alt %s' % (tag, extra), '',
          '| kernel | calls | total ms | avg us | % |', '|---|---|---|---|---|']
 conv_ns = conv_calls = 0
 for r in rows[:24]:
@@ -114,7 +115,7 @@ if len(traffic) == 2:
                'source': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, FETCH_SIZE x2 '
                          '(gfx950 correction), profiles/%s_summary.md' % tag},
               open(os.path.join(out, '%s_conv_traffic.json' % tag), 'w'), indent=1)
-bj = os.path.join(root, 'gpurun_out', '%s_bench.json' % tag)
+bj = os.path.join(root, prof, '%s_bench.json' % tag)
 if os.path.exists(bj):
     txt = [l for l in open(bj) if l.startswith('{')]
     if txt:

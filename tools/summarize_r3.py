@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condense the rocprofv3 outputs of tools/profile_r3.sh (gpurun_out/<tag>_stats, _pmc_mfma, _pmc_fetch,
+"""Condense the rocprofv3 outputs of tools/profile_r3.sh ($DODT_PROFILE_DIR, default profile_out/: <tag>_stats, _pmc_mfma, _pmc_fetch,
 _pmc_write of one `bench.py` command) into profiles/<tag>_summary.md, profiles/<tag>_kernel_stats.csv,
 profiles/<tag>_conv_traffic.json (per conv kernel) and, when the command ran the HBM-bound kernels'
 stand-alone section, profiles/<tag>_hbm_traffic.json.  Usage: summarize_r3.py <tag> [the bench.py args]
@@ -32,11 +32,12 @@ def short(name):
 
 tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+prof = os.environ.get('DODT_PROFILE_DIR', 'profile_out')     # where tools/profile_*.sh wrote
 out = os.path.join(root, 'profiles')
 
 
 def one(pattern):
-    hits = glob.glob(os.path.join(root, 'gpurun_out', pattern), recursive=True)
+    hits = glob.glob(os.path.join(root, prof, pattern), recursive=True)
     return hits[0] if hits else None
 
 
@@ -51,7 +52,7 @@ def counters(path):
 stats = one('%s_stats/**/*kernel_stats.csv' % tag)
 shutil.copy(stats, os.path.join(out, '%s_kernel_stats.csv' % tag))
 rows = list(csv.DictReader(open(stats)))
-lines = ['# %s: rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-alt --steps 10 %s'
+lines = ['# %s: rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-alt --steps 10 %s'
          % (tag, ' '.join(sys.argv[2:])), '', '| kernel | calls | total ms | avg us | % |', '|---|---|---|---|---|']
 for r in rows[:26]:
     lines.append('| %s | %s | %.2f | %.1f | %s |' % (r['Name'][:70].replace('|', '/'), r['Calls'],
@@ -64,7 +65,7 @@ alone = {}
 if trace:
     tr = list(csv.DictReader(open(trace)))
     tr.sort(key=lambda r: int(r['Start_Timestamp']))
-    bj = os.path.join(root, 'gpurun_out', '%s_stats.log' % tag)
+    bj = os.path.join(root, prof, '%s_stats.log' % tag)
     line = [l for l in open(bj) if l.startswith('{')]
     bench = json.loads(line[-1]) if line else None
     if bench:
@@ -143,7 +144,7 @@ if per:
         else:
             hbm_json[k] = {'fetch_bytes': ent['fetch_bytes_per_launch'], 'write_bytes': ent['write_bytes_per_launch'],
                            'dispatches': f[1]}
-    src = ('rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes over `python3 bench.py --no-cpu-baseline --no-alt '
+    src = ('rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes over `python3 bench.py --full --no-cpu-baseline --no-alt '
            '--steps 4 --warmup 1 %s`, FETCH_SIZE x2 (gfx950 correction), profiles/%s_summary.md' % (' '.join(sys.argv[2:]), tag))
     if conv_json:
         json.dump({'kernels': conv_json, 'source': src}, open(os.path.join(out, '%s_conv_traffic.json' % tag), 'w'), indent=1)
@@ -162,7 +163,7 @@ if trace and bench and bench['roofline'].get('hbm') and per:
           'Algorithmic bytes: SURVEY.md 8(d).  Peak 8000 GB/s.', '',
           '| stage | kernel(s) | algorithmic MB | events us | trace us (kernels only) | GB/s (events) | of peak | fetch MB | write MB |',
           '|---|---|---|---|---|---|---|---|---|']
-    plain = os.path.join(root, 'gpurun_out', '%s_bench.json' % tag)      # the un-profiled run's timing
+    plain = os.path.join(root, prof, '%s_bench.json' % tag)      # the un-profiled run's timing
     hbm_rows = bench['roofline']['hbm']
     if os.path.exists(plain):
         pl = [l for l in open(plain) if l.startswith('{')]
@@ -185,7 +186,7 @@ if trace and bench and bench['roofline'].get('hbm') and per:
            'which prices every tap); the correlation kernel moves 1.8 x its algorithmic bytes over the fabric (the '
            'rows a tile shares with the tile below are fetched again), i.e. 5.8 TB/s of real traffic.']
     open(os.path.join(out, '%s_hbm_summary.md' % tag), 'w').write('\n'.join(hl) + '\n')
-bj = os.path.join(root, 'gpurun_out', '%s_bench.json' % tag)
+bj = os.path.join(root, prof, '%s_bench.json' % tag)
 if os.path.exists(bj):
     txt = [l for l in open(bj) if l.startswith('{')]
     if txt:
