@@ -21,6 +21,7 @@ EXTRACTOR_BF16 = 0x200
 EXTRACTOR_SPLIT = 0x400
 FC_RELU = 1
 FC_BF16 = 2
+CONFLICT_RAISE, CONFLICT_NEXT_BEST = 0, 1
 
 
 class DodtError(RuntimeError):
@@ -158,6 +159,9 @@ SIGNATURES = {
     'dodt_comm_sync': (_i, [_vp]),
     'dodt_comm_barrier': (_i, [_vp]),
     'dodt_comm_max_f64': (_i, [_vp, C.POINTER(_d)]),
+    'dodt_three_d_iou_matrix': (_i, [_vp, _vp, _i, _vp, _i, _vp]),
+    'dodt_interpolate_pairs': (_i, [_vp, _vp, _i, _pi32, _i, _i, _i, _d, _i, _vp, C.POINTER(_d), _i, _vp,
+                                    _pi32, _pi32]),
 }
 COMM_ID_BYTES = 128
 

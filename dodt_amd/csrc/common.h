@@ -73,6 +73,7 @@ struct dodt_ctx {
     dodt::Scratch vox_ws;    // voxeliser: touched list + counters
     dodt::Scratch anchor_ws; // anchor filter: mask + block counts
     dodt::Scratch nms_ws;    // NMS: keys, sorted boxes, suppression mask
+    dodt::Scratch temporal_ws;   // temporal module: IoU of every row pair of a step's keyframe pairs
     int num_cus = 256;
     int32_t* pinned = nullptr;       // kFetchSlots x 16 int32, hipHostMalloc
     hipEvent_t fetch_ev[kFetchSlots] = {};

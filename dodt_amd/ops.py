@@ -291,3 +291,52 @@ class FullyConnected(object):
         if self.handle is not None:
             self.ctx.lib.dodt_fc_destroy(self.handle)
             self.handle = None
+
+
+def three_d_iou_matrix(ctx, d_a, na, d_b, nb, d_iou_out):
+    """d_iou_out (na,nb) float64 = 3-D IoU of boxes d_a (na,7) and d_b (nb,7), [x,y,z,l,w,h,ry] float64
+    (dt_evaluator_utils.three_d_iou_matrix on the device)."""
+    _lib.check(ctx.lib.dodt_three_d_iou_matrix(ctx.handle, _p(d_a), int(na), _p(d_b), int(nb), _p(d_iou_out)),
+               'dodt_three_d_iou_matrix')
+
+
+def temporal_calib(r0_rect, tr_velo_to_cam):
+    """The 42 doubles dodt_interpolate_pairs takes for recovery: inv(R0_rect), inv(Tr_velo_to_cam) (3x4, as
+    kitti_tracking_utils._rect_to_velo builds it), Tr_velo_to_cam, R0_rect."""
+    r0 = np.asarray(r0_rect, np.float64).reshape(3, 3)
+    tr = np.asarray(tr_velo_to_cam, np.float64).reshape(3, 4)
+    inv = np.zeros_like(tr)
+    inv[0:3, 0:3] = np.transpose(tr[0:3, 0:3])
+    inv[0:3, 3] = np.dot(-np.transpose(tr[0:3, 0:3]), tr[0:3, 3])
+    return np.concatenate([np.linalg.inv(r0).reshape(-1), inv.reshape(-1), tr.reshape(-1), r0.reshape(-1)])
+
+
+def temporal_ego(ego, n_frames):
+    """(n_frames, 13) float64 recovery parameters of one pair: ego = one (trans (3,), matrix (3,3), delta) per frame
+    1..n_frames-1 (kitti_tracking_utils.coordinate_transform); row 0 unused.  The inverse of matrix is taken here."""
+    if len(ego) != n_frames - 1:
+        raise ValueError('recovery needs one (trans, matrix, delta) per frame 1..n_frames-1')
+    out = np.zeros((n_frames, 13))
+    for i, (trans, matrix, delta) in enumerate(ego):
+        out[i + 1, 0:3] = np.asarray(trans, np.float64).reshape(3)
+        out[i + 1, 3:12] = np.linalg.inv(np.asarray(matrix, np.float64).reshape(3, 3)).reshape(-1)
+        out[i + 1, 12] = float(delta)
+    return out
+
+
+def interpolate_pairs(ctx, d_records, d_counts, n_pairs, max_det, n_frames, threshold, on_conflict, d_out,
+                      d_out_counts, d_status, d_recover=None, calib=None, max_out=None):
+    """Temporal module M for n_pairs keyframe pairs in one launch (dodt_interpolate_pairs): d_records
+    (n_pairs, 2, max_det, 17) float32 or float64, d_counts (n_pairs, 2) int32 -> d_out (n_pairs, n_frames, max_out,
+    13) float64, d_out_counts (n_pairs, n_frames) int32, d_status (n_pairs,) int32 (1: a 'raise'-mode conflict).
+    d_recover (n_pairs, n_frames, 13) float64 (temporal_ego) with calib (temporal_calib), or None."""
+    if on_conflict not in ('raise', 'next_best'):
+        raise ValueError("on_conflict must be 'raise' or 'next_best'")
+    if d_records.dtype not in (np.float32, np.float64):
+        raise ValueError('records must be float32 or float64')
+    cal = None if calib is None else _arr(C.c_double, calib)
+    _lib.check(ctx.lib.dodt_interpolate_pairs(
+        ctx.handle, _p(d_records), int(d_records.dtype == np.float64), _p(d_counts), int(n_pairs), int(max_det),
+        int(n_frames), float(threshold), _lib.CONFLICT_NEXT_BEST if on_conflict == 'next_best' else _lib.CONFLICT_RAISE,
+        _p(d_recover), cal, int(2 * max_det if max_out is None else max_out), _p(d_out), _p(d_out_counts),
+        _p(d_status)), 'dodt_interpolate_pairs')

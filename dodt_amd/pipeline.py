@@ -36,6 +36,7 @@ from dodt_amd.core.avod_fc_layers.fusion_fc_layers import EarlyFusionFcLayers
 from dodt_amd.core.feature_extractors.vgg import BevVgg, ImgVgg
 from dodt_amd.core.feature_extractors.vgg_pyramid import BevVggPyr, ImgVggPyr
 from dodt_amd.core.models.anchor_predictor import AnchorPredictor
+from dodt_amd.temporal import unpack_frames
 
 # feature_extractor_builder.get_extractor (avod/builders/feature_extractor_builder.py:8-24)
 EXTRACTORS = {'vgg_pyr': (BevVggPyr, ImgVggPyr), 'vgg': (BevVgg, ImgVgg)}
@@ -59,7 +60,9 @@ class FramePairPipeline(object):
                  r0_rect=_config.KITTI_R0_RECT, tr_velo_to_cam=_config.KITTI_TR_VELO_TO_CAM,
                  image_wh=_config.KITTI_IMAGE_WH, n_points_max=120000, rpn_nms_size=1024,
                  pairs_per_step=1, side_streams=None, head_params=None, conv_dtype='f32',
-                 head_dtype='f32', reuse_streams_of=None, tail_sets=None):
+                 head_dtype='f32', reuse_streams_of=None, tail_sets=None, temporal=None):
+        """temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
+        module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it."""
         self.ctx = ctx
         self.cfg = cfg
         self.p2 = np.asarray(p2, dtype=np.float64)
@@ -70,6 +73,20 @@ class FramePairPipeline(object):
         self.fps = int(cfg.get('frames_per_sample', 2))
         if self.fps not in (1, 2):
             raise ValueError('frames_per_sample must be 1 or 2')
+        self.temporal = None
+        if temporal is not None:
+            if self.fps != 2:
+                raise ValueError('temporal: needs frame pairs (frames_per_sample == 2)')
+            t = dict(temporal)
+            tm = dict(n_frames=int(t.pop('n_frames')), threshold=float(t.pop('threshold', 0.1)),
+                      on_conflict=t.pop('on_conflict', 'raise'))
+            if t:
+                raise ValueError('temporal: unknown keys %s' % sorted(t))
+            if tm['on_conflict'] not in ('raise', 'next_best'):
+                raise ValueError("temporal: on_conflict must be 'raise' or 'next_best'")
+            if not 1 <= tm['n_frames'] <= 64:
+                raise ValueError('temporal: n_frames must be 1..64')
+            self.temporal = tm
         self.nf = self.fps * self.pairs                # frames per step
         self.bev_h, self.bev_w = cfg['bev_dims']
         self.img_h, self.img_w = cfg['img_dims']
@@ -219,6 +236,10 @@ class FramePairPipeline(object):
         # step (sharding.Communicator.join) makes the tails wait for the all-gather that last
         # read it, at least a ring's half earlier
         self.on_records_reuse = None
+        # ---- temporal module M (opt-in): the frames between a pair's keyframes -----------------
+        if self.temporal is not None:
+            self.temporal_calib = ops.temporal_calib(r0_rect, tr_velo_to_cam)
+            self._alloc_frames()
         self.mark_steps = ()           # tools/pipe_marks.py: steps whose stages get timing marks
         self.early_prep = os.environ.get('DODT_PIPE_EARLY_PREP', '1') != '0'
         self.marks = {}                # name -> (context, slot)
@@ -276,6 +297,19 @@ class FramePairPipeline(object):
                      for p in rec_ptrs]
         self.cnt2 = [self.ctx.wrap(p, (self.pairs, self.fps), np.int32) for p in cnt_ptrs]
         self.d_records, self.d_rec_counts = self.rec2[0], self.cnt2[0]
+        self._alloc_frames()
+
+    def _alloc_frames(self):
+        """M's outputs (and the recovery parameters it reads): a ring as long as the record ring, step k in slot k % R."""
+        if self.temporal is None:
+            return
+        R, n = len(self.rec2), self.temporal['n_frames']
+        self.frames2 = [self.ctx.empty((self.pairs, n, 2 * MAX_DET, 13), np.float64) for _ in range(R)]
+        self.fcnt2 = [self.ctx.zeros((self.pairs, n), np.int32) for _ in range(R)]
+        self.fst2 = [self.ctx.zeros((self.pairs,), np.int32) for _ in range(R)]
+        # (on the image stream, which M runs on: an upload there is ordered behind M of the step that last read the slot)
+        self.ego2 = [self.img_ctx.zeros((self.pairs, n, 13), np.float64) for _ in range(R)]
+        self.d_frames, self.d_frame_counts, self.d_frame_status = self.frames2[0], self.fcnt2[0], self.fst2[0]
 
     def use_record_ring(self, d_rec_ring, d_cnt_ring):
         """The same with one contiguous ring: d_rec_ring (R, pairs, fps, MAX_DET, REC_COLS) float32,
@@ -368,7 +402,7 @@ class FramePairPipeline(object):
             c.mark(self.PREP_DONE_MARK + k % 3)
         self.prepped = k
 
-    def run(self, d_points, n_points, d_images, heads=None, ego_motion=None, lookahead=None):
+    def run(self, d_points, n_points, d_images, heads=None, ego_motion=None, lookahead=None, recover=None):
         """Enqueue one step.  Lists of length 2 * pairs_per_step, frame order
         [pair0 f0, pair0 f1, pair1 f0, ...]: d_points[f] (n,4) float32 velodyne xyzi;
         d_images[f] (H,W,3) uint8; heads[f] dict of device arrays rpn_logits (N,2),
@@ -383,6 +417,10 @@ class FramePairPipeline(object):
         in front of the previous step's tail on the side streams, so that the next step's convs do not wait for
         that tail (a caller that knows its next inputs -- a stream of frames -- should pass them; the next call
         must then be made with those inputs).
+        recover (pipelines built with `temporal` only): None, or per pair of the step a list of (trans (3,), matrix (3,3),
+        delta) for frames 1..n_frames-1 -- the recovery of those frames' detections into their own coordinates
+        (kitti_tracking_utils.recovery_coordinate).  Copied to the device behind the main stream's work so far, which
+        the host waits for.
         Returns the parity (0/1) of the record buffers this step will fill.  The
         detections of the PREVIOUS step are complete on the main stream when this returns
         (self.d_records / self.fr / self.last_anchor_counts then describe that step);
@@ -390,6 +428,14 @@ class FramePairPipeline(object):
         main, nf = self.ctx, self.nf
         if (heads is None) != (self.rpn_head is not None):
             raise ValueError('pass `heads` exactly when the pipeline has no head_params')
+        if recover is not None:
+            if self.temporal is None:
+                raise ValueError('recover: the pipeline has no temporal module')
+            if len(recover) != self.pairs:
+                raise ValueError('recover: one entry per pair of the step')
+            n = self.temporal['n_frames']
+            # slot k % R was last read by M of step k - R, enqueued on `main` before this copy
+            self.ego2[self.step_idx % len(self.rec2)].upload(np.stack([ops.temporal_ego(e, n) for e in recover]))
         cur = self.step_idx & 1
         sides, preps = self._streams(cur)
         ns = len(sides)
@@ -450,7 +496,8 @@ class FramePairPipeline(object):
                     self.img_ctx.wait_mark(s, self.TAIL_DONE_MARK)
                 if p_preps[i] is not s:
                     p_preps[i].wait_mark(s, self.TAIL_DONE_MARK)
-        self.pending = dict(cur=cur, heads=heads, step=k, rslot=k % len(self.rec2))
+            self._temporal_step(self.pending)
+        self.pending = dict(cur=cur, heads=heads, step=k, rslot=k % len(self.rec2), recover=recover is not None)
         if not self.early_prep:
             for s in sides:
                 s.wait_for(main)
@@ -460,14 +507,51 @@ class FramePairPipeline(object):
 
     def finish(self):
         """Enqueue the tail of the last step; afterwards self.fr / d_records hold it."""
-        if self.pending is not None:
-            self._wait_convs(self.pending)
-            self._tail(self.pending)
+        st = self.pending
+        if st is not None:
+            self._wait_convs(st)
+            self._tail(st)
             self.pending = None
         for sides, preps in self.stream_sets:
             for s in set(sides) | set(preps):
                 self.ctx.wait_for(s)
         self.ctx.wait_for(self.img_ctx)
+        if st is not None and self.temporal is not None:
+            self.img_ctx.wait_for(self.ctx)         # (the main stream has joined every stream, the last tails included)
+            self._temporal_step(st)
+            self.ctx.wait_for(self.img_ctx)
+
+    def _temporal_step(self, st):
+        """M of step `st` (pipelines built with `temporal`): one launch for all its pairs on the IMAGE stream, behind the
+        next step's image stack (the shorter of the two; on the main stream, behind the BEV stack, M's 0.1 ms lengthened
+        the step by 3 %).  That stream already waits for the step's tails (TAIL_DONE_MARK, run()) -- its records are
+        complete there; the next writer of the record slot, the tail of step st + R, waits for the conv stacks of step
+        st + R on both conv streams (CONV_DONE_MARK), i.e. behind this launch: no marks of its own.  The outputs go to
+        slot st % R of the frames ring (d_frames, frames()); finish() makes the main stream wait for them."""
+        if self.temporal is None:
+            return
+        T, r, c = self.temporal, st['rslot'], self.img_ctx
+        if os.environ.get('DODT_PIPE_IMG_WAIT', 'tail') == 'none':      # (then run() does not make it wait for them)
+            for s in self._streams(st['cur'])[0]:
+                c.wait_mark(s, self.TAIL_DONE_MARK)
+        self._mark(c, st['step'], 'temporal_start')
+        ops.interpolate_pairs(c, self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, T['n_frames'], T['threshold'],
+                              T['on_conflict'], self.frames2[r], self.fcnt2[r], self.fst2[r],
+                              d_recover=self.ego2[r] if st['recover'] else None,
+                              calib=self.temporal_calib if st['recover'] else None, max_out=2 * MAX_DET)
+        self._mark(c, st['step'], 'temporal_end')
+        self.d_frames, self.d_frame_counts, self.d_frame_status = self.frames2[r], self.fcnt2[r], self.fst2[r]
+
+    def frames(self):
+        """Every frame's detections of the last finished step (as d_records: after finish(), or of the previous step
+        once run() has returned), downloaded: per pair, the host function's list of n_frames (k,13) float64 arrays
+        (dt_evaluator_utils.interpolate_non_keyframe_predictions on that pair's records).  Raises ValueError if a pair
+        had a conflict and on_conflict is 'raise'."""
+        if self.temporal is None:
+            raise ValueError('frames: the pipeline has no temporal module')
+        self.ctx.wait_for(self.img_ctx)             # (the downloads go through the main stream)
+        return unpack_frames(self.d_frames.download(), self.d_frame_counts.download(),
+                             self.d_frame_status.download(), self.temporal['on_conflict'])
 
     CONV_DONE_MARK = 250        # mark slots 250, 251 of the conv contexts: end of a step's stacks, by parity
     CORR_MAP_MARK = 248         # ... 248, 249 of the image context: the step's correlation maps stand, by parity

@@ -455,6 +455,41 @@ int dodt_box_4c_decode(dodt_ctx* ctx, const float* d_top_anchors, const float* d
                        const float bev_extents[4], float* d_boxes_3d_out,
                        float* d_pred_anchors_out, float* d_bev_tf_out);
 
+/* ---- (f) temporal module "M" of S+T+M: the frames between two keyframes --------------------
+ * The detector runs on keyframes t and t + tau only; the frames in between get their detections by
+ * associating the two keyframes' detections by 3-D IoU and interpolating every track
+ * (avod/core/dt_evaluator_stride.py:304-313 -> dt_evaluator_utils.py:212-362,
+ * interpolate_non_keyframe_predicitons + interpolate_trajectory; the host form is
+ * dodt_amd/core/dt_evaluator_utils.py).  Float64 throughout.
+ *
+ * 3-D IoU of every box of d_a (na,7) with every box of d_b (nb,7), [x,y,z,l,w,h,ry] doubles (y = bottom,
+ * down positive), into d_iou_out (na,nb): bounding-sphere early exit (exactly 0), height overlap times the
+ * exact overlap of the two bases (Sutherland-Hodgman) -- the reference rasterises that overlap at 1 cm
+ * (wavedata/wavedata/tools/core/evaluation.py:60-75,182-261). */
+int dodt_three_d_iou_matrix(dodt_ctx* ctx, const double* d_a, int na, const double* d_b, int nb,
+                            double* d_iou_out);
+/* One workgroup per pair.  d_records (n_pairs, 2, max_det, 17): keyframe f of a pair is slot f, the
+ * pipeline's record layout, float32 (records_f64 = 0) or float64 (1), widened to float64 first;
+ * d_counts (n_pairs, 2) valid rows per slot.  Rows with score (column 7) > threshold take part, in order.
+ * n_frames (1..64): frames from keyframe 0 to keyframe 1 inclusive (tau + 1); 1 and 2 keep the
+ * reference's short-cuts (no association).  on_conflict: DODT_CONFLICT_RAISE -- a keyframe-0 detection
+ * whose best match is already taken sets d_status[pair] = 1 and that pair's counts to 0 (the reference's
+ * next_idx.remove raises, dt_evaluator_utils.py:266-268); DODT_CONFLICT_NEXT_BEST -- its best still-free
+ * match instead.  d_recover (n_pairs, n_frames, 13) or NULL (= identity): per pair and frame
+ * [trans(3), inv(matrix) (3x3 row-major), delta] of recovery_coordinate (dt_evaluator_utils.py:189-210,
+ * kitti_tracking_dataset.py:374-389), applied to frames 1..n_frames-1; calib (host, 42 doubles):
+ * inv(R0_rect) (3x3), inv(Tr_velo_to_cam) (3x4), Tr_velo_to_cam (3x4), R0_rect (3x3), read before the call
+ * returns.  Outputs: d_out (n_pairs, n_frames, max_out, 13) -- the records' first 13 columns, matched and
+ * unmatched keyframe-0 tracks in order, then the unmatched keyframe-1 ones --, d_out_counts (n_pairs,
+ * n_frames), d_status (n_pairs).  max_det <= 128, max_out >= 2 * max_det.  For n_frames >= 3 two launches: the
+ * IoU of every row pair over the whole chip into a workspace the context keeps, then one workgroup per pair. */
+#define DODT_CONFLICT_RAISE 0
+#define DODT_CONFLICT_NEXT_BEST 1
+int dodt_interpolate_pairs(dodt_ctx* ctx, const void* d_records, int records_f64, const int32_t* d_counts,
+                           int n_pairs, int max_det, int n_frames, double threshold, int on_conflict,
+                           const double* d_recover, const double* calib, int max_out, double* d_out,
+                           int32_t* d_out_counts, int32_t* d_status);
+
 /* ---- (e) multi-GPU: the one exchange step of the path, RCCL over xGMI, no PyTorch -----------
  * The reference runs on ONE device (avod/experiments/run_tracking_inference.py:109-128 sets a
  * single CUDA_VISIBLE_DEVICES and walks the sequences in a loop), so there is no reference
