@@ -390,3 +390,20 @@ def track_through_ious(dets_for_track, dets_for_ious, high_threshold, iou_thresh
     tracks_finished += [t for t in tracks_active
                         if t['max_score'] >= high_threshold and len(t['trajectory']) >= t_min]
     return tracks_finished
+
+
+def convert_trajectory_to_kitti_format(trajectories):
+    """dt_evaluator_utils.py:514-532: finished tracks -> KITTI tracking rows [frame_id, track id, type, truncated,
+    occluded, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, score], the track id being the position in
+    `trajectories`.  The rows are sorted by 100 * frame_id + id as written -- ids of 100 and more interleave with
+    later frames -- and returned as np.asarray of the mixed list (strings)."""
+    final_pred_label = []
+    for id in range(len(trajectories)):
+        trace = trajectories[id]
+        score = trace['max_score']
+        for obj in trace['trajectory']:
+            label = ([obj['frame_id']] + [id] + np.asarray(obj['info']).tolist() + obj['boxes2d'].tolist()
+                     + obj['boxes3d'].tolist() + [score])
+            final_pred_label.append(label)
+    final_pred_label.sort(key=lambda obj: 100 * int(obj[0]) + int(obj[1]))
+    return np.asarray(final_pred_label)

@@ -74,6 +74,8 @@ struct dodt_ctx {
     dodt::Scratch anchor_ws; // anchor filter: mask + block counts
     dodt::Scratch nms_ws;    // NMS: keys, sorted boxes, suppression mask
     dodt::Scratch temporal_ws;   // temporal module: IoU of every row pair of a step's keyframe pairs
+    dodt::Scratch tracking_ws;   // tracker: the IoU tables of a batch of pairs
+    dodt::Scratch tracking_enc;  // tracker: a batch's encoded label rows
     int num_cus = 256;
     int32_t* pinned = nullptr;       // kFetchSlots x 16 int32, hipHostMalloc
     hipEvent_t fetch_ev[kFetchSlots] = {};

@@ -102,6 +102,8 @@ int dodt_ctx_destroy(dodt_ctx* ctx) {
     ctx->anchor_ws.release();
     ctx->nms_ws.release();
     ctx->temporal_ws.release();
+    ctx->tracking_ws.release();
+    ctx->tracking_enc.release();
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     for (int i = 0; i < kFetchSlots; ++i)
         if (ctx->fetch_ev[i]) (void)hipEventDestroy(ctx->fetch_ev[i]);

@@ -340,3 +340,50 @@ def interpolate_pairs(ctx, d_records, d_counts, n_pairs, max_det, n_frames, thre
         int(n_frames), float(threshold), _lib.CONFLICT_NEXT_BEST if on_conflict == 'next_best' else _lib.CONFLICT_RAISE,
         _p(d_recover), cal, int(2 * max_det if max_out is None else max_out), _p(d_out), _p(d_out_counts),
         _p(d_status)), 'dodt_interpolate_pairs')
+
+
+def track_state_bytes(log_capacity):
+    """Bytes of a tracker state buffer (dodt_track_state_bytes)."""
+    n = C.c_size_t()
+    _lib.check(_lib.load().dodt_track_state_bytes(int(log_capacity), C.byref(n)), 'dodt_track_state_bytes')
+    return int(n.value)
+
+
+def track_reset(ctx, d_state, log_capacity):
+    _lib.check(ctx.lib.dodt_track_reset(ctx.handle, _p(d_state), int(log_capacity)), 'dodt_track_reset')
+
+
+def track_flush(ctx, d_state, high_threshold, t_min):
+    _lib.check(ctx.lib.dodt_track_flush(ctx.handle, _p(d_state), float(high_threshold), int(t_min)), 'dodt_track_flush')
+
+
+def track_encode(ctx, d_records, d_counts, n_pairs, max_det, p2, image_wh, threshold, d_track, d_ious, d_enc_counts):
+    """kitti_label_table of n_pairs record pairs (dodt_track_encode): d_records (n_pairs, 2, max_det, 17) float32 or
+    float64, d_counts (n_pairs, 2) -> d_track (n_pairs, 128, 23), d_ious (n_pairs, 128, 16) float32, d_enc_counts
+    (n_pairs, 4) int32."""
+    if d_records.dtype not in (np.float32, np.float64):
+        raise ValueError('records must be float32 or float64')
+    _lib.check(ctx.lib.dodt_track_encode(
+        ctx.handle, _p(d_records), int(d_records.dtype == np.float64), _p(d_counts), int(n_pairs), int(max_det),
+        _arr(C.c_double, np.asarray(p2, np.float64).reshape(12)), float(image_wh[0]), float(image_wh[1]),
+        float(threshold), _p(d_track), _p(d_ious), _p(d_enc_counts)), 'dodt_track_encode')
+
+
+def track_pairs(ctx, d_state, d_records, d_counts, n_pairs, max_det, p2, image_wh, score_threshold, high_threshold,
+                iou_threshold, t_min):
+    """Encode and track n_pairs record pairs of one sequence, continuing d_state (dodt_track_pairs)."""
+    if d_records.dtype not in (np.float32, np.float64):
+        raise ValueError('records must be float32 or float64')
+    _lib.check(ctx.lib.dodt_track_pairs(
+        ctx.handle, _p(d_state), _p(d_records), int(d_records.dtype == np.float64), _p(d_counts), int(n_pairs),
+        int(max_det), _arr(C.c_double, np.asarray(p2, np.float64).reshape(12)), float(image_wh[0]),
+        float(image_wh[1]), float(score_threshold), float(high_threshold), float(iou_threshold), int(t_min)),
+        'dodt_track_pairs')
+
+
+def track_encoded(ctx, d_state, d_track, d_ious, d_counts, n_pairs, max_rows, high_threshold, iou_threshold, t_min):
+    """Track n_pairs already encoded pairs (dodt_track_encoded): d_track (n_pairs, max_rows, 23), d_ious (n_pairs,
+    max_rows, 16) float32, d_counts (n_pairs, 2) int32."""
+    _lib.check(ctx.lib.dodt_track_encoded(
+        ctx.handle, _p(d_state), _p(d_track), _p(d_ious), _p(d_counts), int(n_pairs), int(max_rows),
+        float(high_threshold), float(iou_threshold), int(t_min)), 'dodt_track_encoded')

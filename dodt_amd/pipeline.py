@@ -30,7 +30,7 @@ import os
 import numpy as np
 
 from dodt_amd import config as _config
-from dodt_amd import device, ops
+from dodt_amd import device, ops, tracking
 from dodt_amd.core.anchor_generators import grid_anchor_3d_generator as gen
 from dodt_amd.core.avod_fc_layers.fusion_fc_layers import EarlyFusionFcLayers
 from dodt_amd.core.feature_extractors.vgg import BevVgg, ImgVgg
@@ -60,9 +60,13 @@ class FramePairPipeline(object):
                  r0_rect=_config.KITTI_R0_RECT, tr_velo_to_cam=_config.KITTI_TR_VELO_TO_CAM,
                  image_wh=_config.KITTI_IMAGE_WH, n_points_max=120000, rpn_nms_size=1024,
                  pairs_per_step=1, side_streams=None, head_params=None, conv_dtype='f32',
-                 head_dtype='f32', reuse_streams_of=None, tail_sets=None, temporal=None):
+                 head_dtype='f32', reuse_streams_of=None, tail_sets=None, temporal=None, tracker=None):
         """temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
-        module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it."""
+        module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it.
+        tracker: None, or dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3, classes=('Car',),
+        max_sequence_dets=65536) -- the IoU tracker on the device after every step: the pairs of the steps, in order,
+        are one sequence until end_sequence() (see _tracker_step, tracks_so_far()); None enqueues and allocates nothing
+        for it."""
         self.ctx = ctx
         self.cfg = cfg
         self.p2 = np.asarray(p2, dtype=np.float64)
@@ -87,6 +91,20 @@ class FramePairPipeline(object):
             if not 1 <= tm['n_frames'] <= 64:
                 raise ValueError('temporal: n_frames must be 1..64')
             self.temporal = tm
+        self.tracker = None
+        if tracker is not None:
+            if self.fps != 2:
+                raise ValueError('tracker: needs frame pairs (frames_per_sample == 2)')
+            t = dict(tracker)
+            tk = dict(score_threshold=float(t.pop('score_threshold', 0.1)),
+                      high_threshold=float(t.pop('high_threshold', 0.5)),
+                      iou_threshold=float(t.pop('iou_threshold', 0.005)), t_min=int(t.pop('t_min', 3)),
+                      classes=tuple(t.pop('classes', ('Car',))), max_sequence_dets=int(t.pop('max_sequence_dets', 65536)))
+            if t:
+                raise ValueError('tracker: unknown keys %s' % sorted(t))
+            if tk['max_sequence_dets'] < 1:
+                raise ValueError('tracker: max_sequence_dets must be >= 1')
+            self.tracker = tk
         self.nf = self.fps * self.pairs                # frames per step
         self.bev_h, self.bev_w = cfg['bev_dims']
         self.img_h, self.img_w = cfg['img_dims']
@@ -240,6 +258,13 @@ class FramePairPipeline(object):
         if self.temporal is not None:
             self.temporal_calib = ops.temporal_calib(r0_rect, tr_velo_to_cam)
             self._alloc_frames()
+        # ---- the IoU tracker (opt-in): one sequence's state on the device, launches on the image stream ------------
+        if self.tracker is not None:
+            tk = self.tracker
+            self.track_state = tracking.Tracker(self.ctx, tk['max_sequence_dets'], tk['high_threshold'],
+                                                tk['iou_threshold'], tk['t_min'], tk['score_threshold'])
+            self.img_ctx.wait_for(self.ctx)          # (the state's reset went on the main stream)
+            self.last_sequence_tracks = None
         self.mark_steps = ()           # tools/pipe_marks.py: steps whose stages get timing marks
         self.early_prep = os.environ.get('DODT_PIPE_EARLY_PREP', '1') != '0'
         self.marks = {}                # name -> (context, slot)
@@ -497,6 +522,7 @@ class FramePairPipeline(object):
                 if p_preps[i] is not s:
                     p_preps[i].wait_mark(s, self.TAIL_DONE_MARK)
             self._temporal_step(self.pending)
+            self._tracker_step(self.pending)
         self.pending = dict(cur=cur, heads=heads, step=k, rslot=k % len(self.rec2), recover=recover is not None)
         if not self.early_prep:
             for s in sides:
@@ -516,9 +542,10 @@ class FramePairPipeline(object):
             for s in set(sides) | set(preps):
                 self.ctx.wait_for(s)
         self.ctx.wait_for(self.img_ctx)
-        if st is not None and self.temporal is not None:
+        if st is not None and (self.temporal is not None or self.tracker is not None):
             self.img_ctx.wait_for(self.ctx)         # (the main stream has joined every stream, the last tails included)
             self._temporal_step(st)
+            self._tracker_step(st)
             self.ctx.wait_for(self.img_ctx)
 
     def _temporal_step(self, st):
@@ -541,6 +568,61 @@ class FramePairPipeline(object):
                               calib=self.temporal_calib if st['recover'] else None, max_out=2 * MAX_DET)
         self._mark(c, st['step'], 'temporal_end')
         self.d_frames, self.d_frame_counts, self.d_frame_status = self.frames2[r], self.fcnt2[r], self.fst2[r]
+
+    def _tracker_step(self, st):
+        """The tracker over the pairs of step `st` (pipelines built with `tracker`): three launches on the IMAGE stream,
+        right behind M (or where M would be), under the same record-slot argument as _temporal_step -- the next
+        writer of slot st % R, the tail of step st + R, waits for both conv streams of that step, i.e. behind these
+        launches.  The state carries over to the next step; nothing is downloaded."""
+        if self.tracker is None:
+            return
+        r, c = st['rslot'], self.img_ctx
+        if self.temporal is None and os.environ.get('DODT_PIPE_IMG_WAIT', 'tail') == 'none':
+            for s in self._streams(st['cur'])[0]:
+                c.wait_mark(s, self.TAIL_DONE_MARK)
+        self._mark(c, st['step'], 'tracker_start')
+        self.track_state.track_records(self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, self.p2, self.image_wh, ctx=c)
+        self._mark(c, st['step'], 'tracker_end')
+
+    def _frame_ids(self, frame_ids):
+        if frame_ids is not None:
+            ids = [tuple(f) for f in frame_ids]
+            return lambda pair, kf: ids[pair][kf]
+        tau = self.temporal['n_frames'] - 1 if self.temporal is not None else 1
+        return lambda pair, kf: pair * tau + kf * tau
+
+    def tracks_so_far(self, frame_ids=None):
+        """The tracks the device has finished so far in this sequence, up to the last step whose tail has been enqueued
+        (every step after finish()), downloaded: the host's track dicts (dt_evaluator_utils.track_through_ious on
+        encode_tracking_dets of the same records).  frame_ids: None -- pair j of the sequence is frames (j * tau,
+        j * tau + tau), tau = n_frames - 1 of `temporal` or 1 --, or one (frame_0, frame_1) per pair."""
+        if self.tracker is None:
+            raise ValueError('tracks_so_far: the pipeline has no tracker')
+        self.ctx.wait_for(self.img_ctx)             # (the downloads go through the main stream)
+        return tracking.tracks_from_log(self.track_state.read(), self._frame_ids(frame_ids), self.tracker['classes'])
+
+    def end_sequence(self, frame_ids=None):
+        """End the sequence after finish(): finish the remaining active tracks, download, and start a new sequence.
+        Returns the host function's tracks_finished (kept as last_sequence_tracks for kitti_tracking_rows())."""
+        if self.tracker is None:
+            raise ValueError('end_sequence: the pipeline has no tracker')
+        if self.pending is not None:
+            raise ValueError('end_sequence: call finish() first (the last step is not tracked yet)')
+        self.track_state.flush(ctx=self.img_ctx)
+        tracks = self.tracks_so_far(frame_ids)
+        self.track_state.reset(ctx=self.img_ctx)
+        self.last_sequence_tracks = tracks
+        return tracks
+
+    def kitti_tracking_rows(self, tracks=None):
+        """convert_trajectory_to_kitti_format of `tracks` (default: the last sequence end_sequence() returned): the
+        reference's KITTI tracking rows, as strings."""
+        from dodt_amd.core.dt_evaluator_utils import convert_trajectory_to_kitti_format
+        if tracks is None:
+            if self.tracker is None or self.last_sequence_tracks is None:
+                raise ValueError('kitti_tracking_rows: no sequence has ended')
+            tracks = self.last_sequence_tracks
+        return convert_trajectory_to_kitti_format(tracks)
 
     def frames(self):
         """Every frame's detections of the last finished step (as d_records: after finish(), or of the previous step

@@ -1,0 +1,198 @@
+"""The IoU tracker of the temporal module on the device, with the host module's own interfaces
+(dodt_amd.core.dt_evaluator_utils encode_tracking_dets, track_through_ious): numpy and dicts in, the same lists
+of dicts out, the encoding and the tracking in HIP (dodt_amd/csrc/tracking.hip).
+
+Tracker owns one sequence's device state.  The pipeline runs the same kernels on its detection records in place
+(FramePairPipeline(tracker=...), tracks_so_far(), end_sequence()); these wrappers are what the tests compare with
+the host module and the reference's goldens.
+"""
+import numpy as np
+
+from dodt_amd import device, ops
+
+MAX_ROWS = 128                  # rows per encoded list (dodt_track_*: max_det <= 128)
+TRK_COLS, K1_COLS = 23, 16      # encoded track item (KITTI row + offsets), keyframe-1 row
+STATUS_OVERFLOW = 1
+
+# the state buffer (tracking.hip: Header, Active, prev_off, prev_k1, Finished[cap], LogEntry[cap])
+_HDR = ('n_active', 'n_slots', 'n_log', 'n_fin', 'frame_num', 'seq_pair', 'status', 'has_prev',
+        'prev_pair', 'prev_nL', 'prev_n1', 'log_cap')
+_HDR_BYTES = 64
+_FIN_OFF = _HDR_BYTES + 2 * MAX_ROWS * 32 + 2 * MAX_ROWS * 7 * 4 + MAX_ROWS * K1_COLS * 4
+_FIN_WORDS, _LOG_WORDS = 4, 28
+
+
+class Tracker(object):
+    """One sequence's tracker state on the device (track_through_ious' tracks_active / tracks_finished, and a log
+    of every detection that entered a track).  log_capacity bounds the log and the finished list; running past it
+    raises when the tracks are read.  Every launch goes on `ctx` (default: the state's context)."""
+
+    def __init__(self, ctx=None, log_capacity=65536, high_threshold=0.5, iou_threshold=0.005, t_min=3,
+                 score_threshold=0.1):
+        self.ctx = ctx or device.default_context()
+        self.cap = int(log_capacity)
+        if self.cap < 1:
+            raise ValueError('log_capacity must be >= 1')
+        self.high, self.iou, self.t_min = float(high_threshold), float(iou_threshold), int(t_min)
+        self.score_threshold = float(score_threshold)
+        nbytes = ops.track_state_bytes(self.cap)
+        assert nbytes == _FIN_OFF + self.cap * 4 * (_FIN_WORDS + _LOG_WORDS), 'state layout'
+        self.d_state = self.ctx.empty((nbytes,), np.uint8)
+        self.reset()
+
+    def reset(self, ctx=None):
+        """Start a new sequence."""
+        ops.track_reset(ctx or self.ctx, self.d_state, self.cap)
+
+    def flush(self, ctx=None):
+        """Finish the remaining active tracks (the end of track_through_ious)."""
+        ops.track_flush(ctx or self.ctx, self.d_state, self.high, self.t_min)
+
+    def track_records(self, d_records, d_counts, n_pairs, max_det, p2, image_wh, ctx=None):
+        """Encode and track n_pairs record pairs (n_pairs, 2, max_det, 17), continuing the sequence."""
+        ops.track_pairs(ctx or self.ctx, self.d_state, d_records, d_counts, n_pairs, max_det, p2, image_wh,
+                        self.score_threshold, self.high, self.iou, self.t_min)
+
+    def track_encoded(self, d_track, d_ious, d_counts, n_pairs, max_rows, ctx=None):
+        ops.track_encoded(ctx or self.ctx, self.d_state, d_track, d_ious, d_counts, n_pairs, max_rows, self.high,
+                          self.iou, self.t_min)
+
+    def header(self):
+        h = self.d_state.offset(0, (len(_HDR),), np.int32).download()
+        return dict(zip(_HDR, (int(v) for v in h)))
+
+    def read(self):
+        """Download the finished tracks (synchronous on the state's context): a list of (start_frame, max_score
+        (float32), log rows (k, 28) int32 in trajectory order) -- a log row is [slot, pair, keyframe, row index,
+        16-col KITTI row, offsets (7), pad] with the floats as their int32 bits.  Raises RuntimeError if the log
+        overflowed."""
+        h = self.header()
+        if h['status'] & STATUS_OVERFLOW:
+            raise RuntimeError('tracker: log capacity %d exceeded (%d log entries, %d finished tracks needed)'
+                               % (self.cap, h['n_log'], h['n_fin']))
+        n_fin, n_log = h['n_fin'], h['n_log']
+        fin = self.d_state.offset(_FIN_OFF, (max(n_fin, 1), _FIN_WORDS), np.int32).download()[:n_fin]
+        log_off = _FIN_OFF + self.cap * 4 * _FIN_WORDS
+        log = self.d_state.offset(log_off, (max(n_log, 1), _LOG_WORDS), np.int32).download()[:n_log]
+        order = np.argsort(log[:, 0], kind='stable')
+        slots = log[order, 0]
+        out = []
+        for slot, start, length, score_bits in fin:
+            lo, hi = np.searchsorted(slots, slot, 'left'), np.searchsorted(slots, slot, 'right')
+            rows = log[order[lo:hi]]
+            if len(rows) != length:
+                raise RuntimeError('tracker: track %d has %d log entries, length %d' % (slot, len(rows), length))
+            out.append((int(start), np.array(score_bits, np.int32).view(np.float32)[()], rows))
+        return out
+
+
+def _floats(rows, a, b):
+    return np.ascontiguousarray(rows[:, a:b]).view(np.float32)
+
+
+def _label_item(frame_id, row, classes, offsets=None):
+    """The host's encode_tracking_dets item of one encoded row (16 float32, class index in col 0)."""
+    d = {'frame_id': str(frame_id), 'info': [classes[int(row[0])], '-1', '-1', '-10.0'],
+         'boxes2d': np.array(row[4:8], np.float32), 'boxes3d': np.array(row[8:15], np.float32),
+         'scores': np.float32(row[15])}
+    if offsets is not None:
+        d['offsets'] = np.array(offsets, np.float32)
+    return d
+
+
+def tracks_from_log(tracks, frame_ids, classes):
+    """Tracker.read() of a records-driven sequence -> the host's tracks_finished: dicts 'trajectory', 'max_score',
+    'start_frame' whose detections are encode_tracking_dets' items.  frame_ids(pair, keyframe) -> the frame id."""
+    out = []
+    for start, score, rows in tracks:
+        v, off = _floats(rows, 4, 20), _floats(rows, 20, 27)
+        traj = [_label_item(frame_ids(int(r[1]), int(r[2])), v[i], classes, off[i]) for i, r in enumerate(rows)]
+        out.append({'trajectory': traj, 'max_score': score, 'start_frame': start})
+    return out
+
+
+def _pack_records(pairs):
+    """[(frame_0, frame_1, records (n,17))] -> (n_pairs, 2, max_det, 17) float32, counts (n_pairs, 2): each keyframe's
+    rows (mark column 16) in order, as the host splits them."""
+    split = []
+    for _, _, rec in pairs:
+        rec = np.asarray(rec, dtype=np.float32).reshape(-1, 17)
+        split.append([rec[rec[:, -1] == 0], rec[rec[:, -1] == 1]])
+    max_det = max([1] + [len(s) for sp in split for s in sp])
+    if max_det > MAX_ROWS:
+        raise ValueError('at most %d rows per keyframe' % MAX_ROWS)
+    recs = np.zeros((len(pairs), 2, max_det, 17), np.float32)
+    counts = np.zeros((len(pairs), 2), np.int32)
+    for j, sp in enumerate(split):
+        for f in range(2):
+            recs[j, f, :len(sp[f])] = sp[f]
+            counts[j, f] = len(sp[f])
+    return recs, counts, max_det
+
+
+def encode_tracking_dets(pairs, calib_p2, image_size, classes, threshold, ctx=None):
+    """dt_evaluator_utils.encode_tracking_dets on the device (dodt_track_encode): the same (dets_for_track,
+    dets_for_ious) lists of dicts."""
+    ctx = ctx or device.default_context()
+    dets_for_track, dets_for_ious = [], [{}]
+    if len(pairs) == 0:
+        return dets_for_track, dets_for_ious
+    recs, counts, max_det = _pack_records(pairs)
+    n = len(pairs)
+    d_trk, d_k1 = ctx.empty((n, MAX_ROWS, TRK_COLS), np.float32), ctx.empty((n, MAX_ROWS, K1_COLS), np.float32)
+    d_cnt = ctx.empty((n, 4), np.int32)
+    ops.track_encode(ctx, ctx.array(recs), ctx.array(counts), n, max_det, calib_p2, image_size, threshold, d_trk,
+                     d_k1, d_cnt)
+    trk, k1, cnt = d_trk.download(), d_k1.download(), d_cnt.download()
+    for j, (frame_0, frame_1, _) in enumerate(pairs):
+        n_t, n_1, skip = cnt[j, :3]
+        if skip:
+            continue
+        dets_for_track.append([_label_item(frame_0, trk[j, i, :16], classes, trk[j, i, 16:23]) for i in range(n_t)])
+        dets_for_ious.append([_label_item(frame_1, k1[j, i], classes) for i in range(n_1)])
+    return dets_for_track, dets_for_ious
+
+
+def track_through_ious(dets_for_track, dets_for_ious, high_threshold, iou_threshold, t_min, ctx=None):
+    """dt_evaluator_utils.track_through_ious on the device (dodt_track_encoded): the same finished tracks, whose
+    trajectories hold the caller's detection dicts, copied as the host copies them (a merged keyframe-1 detection
+    gets 'offsets' = its own box).  Boxes and scores are taken as float32."""
+    ctx = ctx or device.default_context()
+    n = len(dets_for_track)
+    if n == 0:
+        return []
+
+    def ious_of(j):
+        f = dets_for_ious[j + 1] if j + 1 < len(dets_for_ious) else []
+        return f if isinstance(f, list) else []
+    rows = max([1] + [len(f) for f in dets_for_track] + [len(ious_of(j)) for j in range(n)])
+    if rows > MAX_ROWS:
+        raise ValueError('at most %d detections per list' % MAX_ROWS)
+    trk = np.zeros((n, rows, TRK_COLS), np.float32)
+    k1 = np.zeros((n, rows, K1_COLS), np.float32)
+    counts = np.zeros((n, 2), np.int32)
+    for j in range(n):
+        for i, d in enumerate(dets_for_track[j]):
+            trk[j, i, 8:15] = np.asarray(d['boxes3d'], np.float32)
+            trk[j, i, 15] = np.float32(d['scores'])
+            trk[j, i, 16:23] = np.asarray(d['offsets'], np.float32)
+        for i, d in enumerate(ious_of(j)):
+            k1[j, i, 8:15] = np.asarray(d['boxes3d'], np.float32)
+            k1[j, i, 15] = np.float32(d['scores'])
+        counts[j] = len(dets_for_track[j]), len(ious_of(j))
+    tr = Tracker(ctx, log_capacity=max(1, int(counts.sum())), high_threshold=high_threshold,
+                 iou_threshold=iou_threshold, t_min=t_min)
+    tr.track_encoded(ctx.array(trk), ctx.array(k1), ctx.array(counts), n, rows)
+    tr.flush()
+    out = []
+    for start, score, log in tr.read():
+        traj = []
+        for _, pair, kf, i in log[:, :4]:
+            if kf == 0:
+                traj.append(dict(dets_for_track[pair][i]))
+            else:
+                d = dict(ious_of(pair)[i])
+                d['offsets'] = d['boxes3d']
+                traj.append(d)
+        out.append({'trajectory': traj, 'max_score': score, 'start_frame': start})
+    return out

@@ -490,6 +490,57 @@ int dodt_interpolate_pairs(dodt_ctx* ctx, const void* d_records, int records_f64
                            const double* d_recover, const double* calib, int max_out, double* d_out,
                            int32_t* d_out_counts, int32_t* d_status);
 
+/* ---- (g) the IoU tracker of the temporal module: detections -> tracks ------------------------
+ * The reference's tracking evaluation turns each pair's records into KITTI label rows
+ * (encoder_tracking_dets) and links them across pairs (track_through_ious,
+ * avod/core/dt_evaluator_utils.py:368-511); the host form is dodt_amd/core/dt_evaluator_utils.py
+ * encode_tracking_dets + track_through_ious, reproduced with its quirks.  The tracker state of one
+ * sequence lives in a device buffer the caller allocates (d_state): the active tracks, the counters,
+ * the previous non-skipped pair's encoded rows, then a list of finished tracks and a log of every
+ * detection that entered a track, log_capacity entries each.  A log or finish list that would run
+ * past log_capacity sets the state's status word and is not written.  Nothing is downloaded: the
+ * caller reads the buffer when it wants the tracks (layout: dodt_amd/tracking.py).
+ *
+ * Bytes of a state buffer with room for log_capacity (>= 1) log entries and finished tracks. */
+int dodt_track_state_bytes(int log_capacity, size_t* bytes);
+/* Start a sequence: empty state, capacity log_capacity (the value the buffer was sized for). */
+int dodt_track_reset(dodt_ctx* ctx, void* d_state, int log_capacity);
+/* The end of the sequence (track_through_ious' last statement): every active track with max_score >=
+ * high_threshold (compared in float32) and length >= t_min is finished, in order; the active list is
+ * emptied. */
+int dodt_track_flush(dodt_ctx* ctx, void* d_state, double high_threshold, int t_min);
+/* kitti_label_table of n_pairs record pairs, one workgroup per pair, without tracking.  d_records
+ * (n_pairs, 2, max_det, 17) float32 (records_f64 = 0) or float64 (1), cast to float32 and widened to
+ * float64 as the host does; d_counts (n_pairs, 2) valid rows per slot; max_det <= 128.  Rows with
+ * score >= score_threshold are projected with p2 (host, 12 doubles, read before the call returns), the
+ * truncation rules applied against image_w x image_h, rounded to 3 decimals and stored as float32.
+ * Outputs, rows compacted in record order: d_track_out (n_pairs, 128, 23) -- the keyframe-0 row
+ * [class, 0, 0, -10, x1, y1, x2, y2, h, w, l, x, y, z, ry, score] in cols 0..15 and cols 8..14 of the
+ * shifted box's own row (record cols 9..15) in cols 16..22, zipped by position --; d_ious_out
+ * (n_pairs, 128, 16), the keyframe-1 rows; d_counts_out (n_pairs, 4): [track items (the shorter of the
+ * two keyframe-0 lists), keyframe-1 rows, skip (both keyframes empty), keyframe-0 rows]. */
+int dodt_track_encode(dodt_ctx* ctx, const void* d_records, int records_f64, const int32_t* d_counts,
+                      int n_pairs, int max_det, const double* p2, double image_w, double image_h,
+                      double score_threshold, float* d_track_out, float* d_ious_out, int32_t* d_counts_out);
+/* Encode and track n_pairs pairs of one sequence, in order, continuing the state: the encoding of
+ * dodt_track_encode, then per non-skipped pair the merge, the greedy walk (argmax over the free
+ * columns, a match needs IoU > iou_threshold), the finish rule (max_score >= high_threshold, length >=
+ * t_min) and the new tracks.  Three launches per 16 pairs, all on ctx's stream: the encoding (one
+ * workgroup per pair), every IoU the walk can read (float64, over the whole chip, into a workspace the
+ * context keeps) and the walk (one workgroup). */
+int dodt_track_pairs(dodt_ctx* ctx, void* d_state, const void* d_records, int records_f64,
+                     const int32_t* d_counts, int n_pairs, int max_det, const double* p2, double image_w,
+                     double image_h, double score_threshold, double high_threshold, double iou_threshold,
+                     int t_min);
+/* Track only, from lists already encoded (the host-array form): d_track (n_pairs, max_rows, 23) and
+ * d_ious (n_pairs, max_rows, 16) float32 in dodt_track_encode's layout (only the box cols 8..14, the
+ * score col 15 and the offsets cols 16..22 are read; the log copies cols 0..15), d_counts (n_pairs, 2):
+ * [track items, keyframe-1 rows].  Pair k's keyframe-1 rows are dets_for_ious[k + 1] of
+ * track_through_ious.  No pair is skipped; max_rows <= 128. */
+int dodt_track_encoded(dodt_ctx* ctx, void* d_state, const float* d_track, const float* d_ious,
+                       const int32_t* d_counts, int n_pairs, int max_rows, double high_threshold,
+                       double iou_threshold, int t_min);
+
 /* ---- (e) multi-GPU: the one exchange step of the path, RCCL over xGMI, no PyTorch -----------
  * The reference runs on ONE device (avod/experiments/run_tracking_inference.py:109-128 sets a
  * single CUDA_VISIBLE_DEVICES and walks the sequences in a loop), so there is no reference
