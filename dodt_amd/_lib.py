@@ -91,6 +91,7 @@ SIGNATURES = {
     'dodt_timer_stop': (_i, [_vp, C.POINTER(_f)]),
     'dodt_bev_slices': (_i, [_vp, _vp, _i, C.POINTER(BevParams), _pf, _vp]),
     'dodt_bev_status': (_i, [_vp, C.POINTER(_i)]),
+    'dodt_bev_support_mask': (_i, [C.POINTER(BevParams), _i, _vp, _i, _i]),
     'dodt_anchor_filter': (_i, [_vp, _vp, _i, _i, _pi32, _i, _i, _pi32, _pi32]),
     'dodt_project_anchors_f64': (_i, [_vp, _vp, _pi32, _i, _pi32,
                                       C.POINTER(_d), C.POINTER(_d), _d, _d,
@@ -109,6 +110,7 @@ SIGNATURES = {
     'dodt_extractor_forward': (_i, [_vp, _pf, _pf, _pf]),
     'dodt_extractor_forward_padded': (_i, [_vp, _pf, _pf, _pf]),
     'dodt_extractor_set_input': (_i, [_vp, _pf]),
+    'dodt_extractor_set_input_support': (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_longlong)]),
     'dodt_extractor_read_activation': (_i, [_vp, C.c_char_p, _vp,
                                             C.POINTER(_i), C.POINTER(_i),
                                             C.POINTER(_i)]),

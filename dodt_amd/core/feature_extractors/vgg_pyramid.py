@@ -31,6 +31,7 @@ class _VggPyr(object):
         self._handle = None
         self._shape = None
         self._params = None
+        self._support = None
 
     # -- lifetime ---------------------------------------------------------------
     def _ensure(self, batch, h, w, c):
@@ -51,6 +52,8 @@ class _VggPyr(object):
         self._shape = shape
         if self._params is not None:
             self._push_params()
+        if self._support is not None:
+            self._push_support()
 
     def close(self):
         if self._handle is not None:
@@ -94,6 +97,22 @@ class _VggPyr(object):
         _lib.check(self._ctx.lib.dodt_extractor_forward_padded(
             self._handle, C.c_void_p(d_x0.ptr), C.c_void_p(d_feat.ptr),
             None if d_bottleneck is None else C.c_void_p(d_bottleneck.ptr)), 'dodt_extractor_forward_padded')
+
+    def set_input_support(self, mask):
+        """mask: (PAD_TOP + h, w) array, nonzero wherever an input may be nonzero (dodt_amd.ops.bev_support_mask);
+        the fp32 net then skips the work items whose outputs no input reaches (dodt_extractor_set_input_support).
+        None: full tables.  Kept across a rebuild for another batch size.  Output buffers are told apart by address:
+        the skipped regions of the ones a forward has written keep their values.  Returns the items skipped per forward."""
+        self._support = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        return self._push_support() if self._handle is not None else 0
+
+    def _push_support(self):
+        m = self._support
+        n = C.c_longlong()
+        _lib.check(self._ctx.lib.dodt_extractor_set_input_support(
+            self._handle, None if m is None else m.ctypes.data, 0 if m is None else m.shape[0],
+            0 if m is None else m.shape[1], C.byref(n)), 'dodt_extractor_set_input_support')
+        return n.value
 
     def set_input(self, d_x0):
         """Forwards without an input argument read d_x0 (extractor input layout) from now on; None: the extractor's
@@ -183,6 +202,9 @@ class _VggPyr(object):
         oh, ow, oc = self.output_shape()
         d_feat = ctx.empty((b, oh, ow, oc), np.float32)
         d_bn = ctx.empty((b, oh, ow, 1), np.float32) if with_bottleneck else None
+        if self._support is not None:
+            # fresh output buffers, perhaps at an address a freed pair had: forget the output pairs written so far
+            self._push_support()
         self.forward_device(d_in, d_feat, d_bn)
         end_points = {}
         if with_bottleneck:

@@ -17,7 +17,9 @@
 #include <string>
 #include <vector>
 
+#include <algorithm>
 #include <array>
+#include <utility>
 
 #include "common.h"
 #include "conv_kernels.h"
@@ -373,6 +375,9 @@ struct Launch {
     int n_items = 0;
     int4* d_items = nullptr;
     float* d_w = nullptr;   // weights blocked for this variant's BN
+    std::vector<int4> h_items;   // the full table on the host (skip tables are filtered from it)
+    int n_skip = -1;             // >= 0: the skip table (dodt_extractor_set_input_support), possibly empty
+    int4* d_skip = nullptr;
 };
 
 struct Layer {
@@ -389,6 +394,7 @@ struct Layer {
     int real_cin = 0;  // channels that carry data (conv1_1 of the image net: 3 of 4)
     float* d_first_w = nullptr;   // conv1_1 of a bf16 extractor: hi + lo bf16 MFMA fragments for conv3x3_bf16_first2_kernel
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // dodt_extractor_forward_timed
+    double skip_frac = 1.0;   // share of the layer's MFMA work its skip tables keep
 };
 
 enum Buf { X0, C1A, CAT1, P1, C2A, CAT2, P2, C3A, C3B, CAT3, P3, C4A, C4B, C4C, F3, F2, F1, NBUF };
@@ -414,6 +420,12 @@ struct dodt_extractor {
     bool timed = false;   // this forward records an event pair around every layer
     int first2_variant = -1;   // >= 0: conv1_1 runs folded into conv1_2's launch (bf16 conv path; DODT_CONV_BF16_FIRST2=0: not)
     float* own_x0 = nullptr;   // the extractor's own input buffer while dodt_extractor_set_input points X0 elsewhere
+    // input support (dodt_extractor_set_input_support): skip tables built; a full forward has run since the last
+    // weight load; the (feature, bottleneck) output pairs pyramid_fusion1 has written with full tables since then
+    bool skip_on = false;
+    bool primed = false;
+    std::vector<std::pair<const float*, const float*>> primed_out;
+    std::vector<char> skipping;   // per layer: this forward runs its skip tables
 };
 
 namespace {
@@ -464,8 +476,11 @@ int run_launch(dodt_extractor* ex, const Layer& l, const Launch& ln, int which,
     a.counter_base = ex->d_counters + 64;
     // (eight counters, 64 bytes apart, per layer: words 2048.. of the block)
     a.xcd_counters = variant_xcd_queue(v) ? ex->d_counters + 2048 + 128 * (&l - ex->layers.data()) : nullptr;
-    a.items = ln.d_items;
-    a.n_items = ln.n_items;
+    const size_t li = &l - ex->layers.data();
+    const bool skip = li < ex->skipping.size() && ex->skipping[li] && ln.n_skip >= 0;
+    a.items = skip ? ln.d_skip : ln.d_items;
+    a.n_items = skip ? ln.n_skip : ln.n_items;
+    if (a.n_items == 0) return DODT_OK;   // every item of the launch skipped
     a.in_part_stride = (long long)src.frame_floats() * ex->batch;
     a.out_part_stride = (long long)dst.frame_floats() * ex->batch;
     a.pool_part_stride = pool_dst >= 0 ? (long long)ex->buf[pool_dst].frame_floats() * ex->batch : 0;
@@ -580,23 +595,28 @@ const char* kernel_name(const KernelVariant& v) {
     return "conv3x3_mfma_kernel";
 }
 
-double layer_direct_flops(const dodt_extractor* ex, const Layer& l) {
-    return 2.0 * l.H * l.W * (double)l.Cout * 9.0 * l.real_cin * ex->batch;
+// frac: share of the layer's work items that run (skip tables: Layer::skip_frac)
+double layer_direct_flops(const dodt_extractor* ex, const Layer& l, double frac = 1.0) {
+    return 2.0 * l.H * l.W * (double)l.Cout * 9.0 * l.real_cin * ex->batch * frac;
 }
+
+// the share of a layer's work a forward in steady state runs (skip tables once primed)
+double steady_frac(const dodt_extractor* ex, const Layer& l) { return ex->skip_on ? l.skip_frac : 1.0; }
 
 // FLOPs the matrix pipe executes for a layer: the Winograd kernels multiply 36 times per 4x4
 // outputs and channel pair (F(4x4,3x3)) or 16 times per 2x2 (F(2x2,3x3)) where the direct form
 // needs 144 / 36; split mode issues three bf16 MFMAs per product term
-double layer_executed_flops(const dodt_extractor* ex, const Layer& l) {
+double layer_executed_flops(const dodt_extractor* ex, const Layer& l, double frac = 1.0) {
     const KernelVariant& kv = variants()[l.main.variant];
-    const double direct = layer_direct_flops(ex, l);
+    const double direct = layer_direct_flops(ex, l, frac);
     if (kv.wino) return direct * (kv.wino_m == 4 ? 36.0 / 144.0 : 16.0 / 36.0);
     return kv.parts == 2 ? 3.0 * direct : direct;
 }
 
 // algorithmic HBM bytes of a layer: input map and weights read once, output map (and its pooled
-// copy) written once; split mode keeps two bf16 maps (hi + lo) and two bf16 weight sets per tensor
-double layer_bytes(const dodt_extractor* ex, const Layer& l) {
+// copy) written once; split mode keeps two bf16 maps (hi + lo) and two bf16 weight sets per tensor;
+// frac < 1 (skip tables): that share of the maps
+double layer_bytes(const dodt_extractor* ex, const Layer& l, double frac = 1.0) {
     const Buffer& src = ex->buf[l.src];
     const Buffer& dst = ex->buf[l.dst];
     const double in_e = src.bf16 ? 2.0 * src.parts : 4.0;
@@ -610,7 +630,8 @@ double layer_bytes(const dodt_extractor* ex, const Layer& l) {
     if (ex->first2_variant >= 0 && &l == &ex->layers[1]) b -= ex->batch * (double)l.H * l.W * l.real_cin * in_e;
     if (l.name == "conv1_2" || l.name == "conv2_2" || l.name == "conv3_3")
         b += ex->batch * std::floor(oh / 2) * std::floor(ow / 2) * l.Cout * out_e;
-    return b;
+    const double w_bytes = 9.0 * l.real_cin * l.Cout * w_e;
+    return (b - w_bytes) * frac + w_bytes;
 }
 
 // Work items of a layer.  The main launch walks big tiles; when their count leaves the
@@ -694,6 +715,96 @@ int run_pool(dodt_extractor* ex, int src, int dst) {
                        d.ptr, ex->batch);
     DODT_LAUNCH_CHECK();
     return DODT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// input support: where a layer's outputs can depend on the input (dodt_extractor_set_input_support)
+// ---------------------------------------------------------------------------
+// An output whose receptive field holds only inputs that are zero in every frame (zero padding included) is a
+// function of the weights alone: a full forward writes it, and later forwards need not.
+struct Support {
+    int h = 0, w = 0;
+    std::vector<uint8_t> m;   // 1: may depend on the input
+    Support() = default;
+    Support(int h_, int w_) : h(h_), w(w_), m((size_t)h_ * w_, 0) {}
+    uint8_t& at(int y, int x) { return m[(size_t)y * w + x]; }
+    uint8_t at(int y, int x) const { return m[(size_t)y * w + x]; }
+};
+
+// the outputs of a 3x3 SAME conv (r = 1), or the margin of a transposed conv (r = 2)
+Support dilate(const Support& a, int r) {
+    Support t(a.h, a.w), o(a.h, a.w);
+    for (int y = 0; y < a.h; ++y)
+        for (int x = 0; x < a.w; ++x)
+            for (int d = -r; d <= r; ++d)
+                if (x + d >= 0 && x + d < a.w && a.at(y, x + d)) { t.at(y, x) = 1; break; }
+    for (int y = 0; y < a.h; ++y)
+        for (int x = 0; x < a.w; ++x)
+            for (int d = -r; d <= r; ++d)
+                if (y + d >= 0 && y + d < a.h && t.at(y + d, x)) { o.at(y, x) = 1; break; }
+    return o;
+}
+
+// VALID 2x2 max pool (odd sizes floored)
+Support pool2(const Support& a) {
+    Support o(a.h / 2, a.w / 2);
+    for (int y = 0; y < o.h; ++y)
+        for (int x = 0; x < o.w; ++x)
+            o.at(y, x) = a.at(2 * y, 2 * x) | a.at(2 * y, 2 * x + 1) | a.at(2 * y + 1, 2 * x) | a.at(2 * y + 1, 2 * x + 1);
+    return o;
+}
+
+// 3x3 stride-2 transposed conv: input i reaches outputs 2i .. 2i + 2 (or 2i - 1 .. 2i + 1 for the other padding
+// split); nearest 2x upsampling dilated by 2 covers both
+Support upconv2(const Support& a) {
+    Support u(2 * a.h, 2 * a.w);
+    for (int y = 0; y < u.h; ++y)
+        for (int x = 0; x < u.w; ++x) u.at(y, x) = a.at(y / 2, x / 2);
+    return dilate(u, 2);
+}
+
+// summed-area table: does a rectangle hold an input-dependent output?
+struct SupportSum {
+    int h = 0, w = 0;
+    std::vector<int> s;
+    explicit SupportSum(const Support& a) : h(a.h), w(a.w), s((size_t)(a.h + 1) * (a.w + 1), 0) {
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x)
+                s[(size_t)(y + 1) * (w + 1) + x + 1] = a.at(y, x) + s[(size_t)y * (w + 1) + x + 1] +
+                                                       s[(size_t)(y + 1) * (w + 1) + x] - s[(size_t)y * (w + 1) + x];
+    }
+    bool any(int y0, int y1, int x0, int x1) const {   // [y0, y1) x [x0, x1), clipped
+        y0 = std::max(y0, 0); x0 = std::max(x0, 0); y1 = std::min(y1, h); x1 = std::min(x1, w);
+        if (y0 >= y1 || x0 >= x1) return false;
+        return s[(size_t)y1 * (w + 1) + x1] - s[(size_t)y0 * (w + 1) + x1] - s[(size_t)y1 * (w + 1) + x0] +
+                   s[(size_t)y0 * (w + 1) + x0] > 0;
+    }
+};
+
+// Winograd F(4x4,3x3): an output's fp32 value depends on the whole 6 x 6 input tile of its 4 x 4 block (the
+// transforms are dense: taps outside its 3 x 3 field cancel exactly, not in rounding).  (F(2x2,3x3) has no such
+// reach: output 0 of a block never reads input 3, output 1 never input 0.)
+Support wino_blocks(const Support& a, int m) {
+    const SupportSum sum(a);
+    Support o(a.h, a.w);
+    for (int y0 = 0; y0 < a.h; y0 += m)
+        for (int x0 = 0; x0 < a.w; x0 += m)
+            if (sum.any(y0 - 1, y0 + m + 1, x0 - 1, x0 + m + 1))
+                for (int y = y0; y < std::min(y0 + m, a.h); ++y)
+                    for (int x = x0; x < std::min(x0 + m, a.w); ++x) o.at(y, x) = 1;
+    return o;
+}
+
+void free_skip_tables(dodt_extractor* ex) {
+    for (Layer& l : ex->layers) {
+        for (Launch* ln : {&l.main, &l.tail}) {
+            if (ln->d_skip) (void)hipFree(ln->d_skip);
+            ln->d_skip = nullptr;
+            ln->n_skip = -1;
+        }
+        l.skip_frac = 1.0;
+    }
+    ex->skip_on = false;
 }
 
 }  // namespace
@@ -814,6 +925,7 @@ int dodt_extractor_create(dodt_ctx* ctx, int kind, int in_h, int in_w, int in_c,
         plan_layer(l, batch, ctx->num_cus, !shared_gpu, mi, ti);
         for (auto pr : {std::make_pair(&l.main, &mi), std::make_pair(&l.tail, &ti)}) {
             pr.first->n_items = (int)pr.second->size();
+            pr.first->h_items = *pr.second;
             if (pr.second->empty()) continue;
             DODT_HIP_CHECK(hipMalloc(&pr.first->d_items, pr.second->size() * sizeof(int4)));
             DODT_HIP_CHECK(hipMemcpyAsync(pr.first->d_items, pr.second->data(),
@@ -865,6 +977,7 @@ int dodt_extractor_destroy(dodt_extractor* ex) {
         for (Launch* ln : {&l.main, &l.tail}) {
             if (ln->d_w) (void)hipFree(ln->d_w);
             if (ln->d_items) (void)hipFree(ln->d_items);
+            if (ln->d_skip) (void)hipFree(ln->d_skip);
         }
         if (l.d_scale) (void)hipFree(l.d_scale);
         if (l.d_shift) (void)hipFree(l.d_shift);
@@ -886,6 +999,9 @@ int dodt_extractor_set_layer(dodt_extractor* ex, const char* name, const float* 
                              const float* var) {
     DODT_REQUIRE(ex && name && w && beta && mean && var, "dodt_extractor_set_layer: NULL argument");
     hipStream_t s = ex->ctx->stream;
+    // new weights: the input-independent outputs the skip tables leave alone change (the next forward primes)
+    ex->primed = false;
+    ex->primed_out.clear();
     if (std::strcmp(name, "bottleneck") == 0) {
         const int fc = ex->out_c;   // 32 (pyramid) or 256 (plain VGG: rpn_model.py:251-267)
         DODT_REQUIRE(kh == 1 && kw == 1 && c_a == fc && c_b == 1,
@@ -1131,6 +1247,13 @@ int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_
     // (the whole block: the launches' counters in words 0..63, the XCD-grouped queues' in words 2048..; the
     //  diagnostic words in between are only read right behind the launch that wrote them)
     DODT_HIP_CHECK(hipMemsetAsync(ex->d_counters, 0, 4096 * sizeof(int), s));
+    // skip tables once a full forward has primed the buffers; pyramid_fusion1 writes the caller's buffers, so it
+    // primes every output pair of its own
+    const bool skip = ex->skip_on && ex->primed;
+    bool last_skip = false;
+    for (const auto& pr : ex->primed_out) last_skip |= skip && pr.first == d_feat_out && pr.second == d_bottleneck_out;
+    ex->skipping.assign(ex->layers.size(), skip);
+    if (ex->kind == DODT_EXTRACTOR_VGG_PYR) ex->skipping[find_layer(ex, "pyramid_fusion1")] = last_skip;
     int rc;
     auto L = [&](const char* n) -> const Layer& { return ex->layers[find_layer(ex, n)]; };
 #define RUN(name)                                           \
@@ -1190,6 +1313,13 @@ int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_
                            ex->bneck_shift, d_bottleneck_out);
         DODT_LAUNCH_CHECK();
     }
+    if (ex->skip_on) {
+        ex->primed = true;
+        if (!last_skip) {
+            ex->primed_out.emplace_back(d_feat_out, d_bottleneck_out);
+            if (ex->primed_out.size() > 8) ex->primed_out.erase(ex->primed_out.begin());   // (re-primed when back)
+        }
+    }
     return DODT_OK;
 }
 
@@ -1209,6 +1339,67 @@ int dodt_extractor_set_input(dodt_extractor* ex, const float* d_x0) {
     DODT_REQUIRE(ex, "dodt_extractor_set_input: extractor is NULL");
     if (!ex->own_x0) ex->own_x0 = ex->buf[X0].ptr;
     ex->buf[X0].ptr = d_x0 ? const_cast<float*>(d_x0) : ex->own_x0;
+    return DODT_OK;
+}
+
+int dodt_extractor_set_input_support(dodt_extractor* ex, const uint8_t* mask, int rows, int cols,
+                                     long long* skipped_items) {
+    DODT_REQUIRE(ex, "dodt_extractor_set_input_support: extractor is NULL");
+    DODT_REQUIRE(!mask || (rows == ex->H && cols == ex->W),
+                 "dodt_extractor_set_input_support: mask is %dx%d, the padded input %dx%d", rows, cols, ex->H, ex->W);
+    if (skipped_items) *skipped_items = 0;
+    DODT_HIP_CHECK(hipStreamSynchronize(ex->ctx->stream));   // (no launch still reads the old tables)
+    free_skip_tables(ex);
+    ex->primed = false;
+    ex->primed_out.clear();
+    // fp32 pyramid only (the bf16 / split paths and the plain VGG keep full tables)
+    if (!mask || ex->kind != DODT_EXTRACTOR_VGG_PYR || ex->bf16 || ex->first2_variant >= 0) return DODT_OK;
+    // each layer's input-dependent outputs, in forward order; a buffer's mask is the OR of its writers so far
+    Support bufs[NBUF];
+    bufs[X0] = Support(ex->H, ex->W);
+    for (int y = 0; y < ex->H; ++y)
+        for (int x = 0; x < ex->W; ++x) bufs[X0].at(y, x) = mask[(size_t)y * ex->W + x] != 0;
+    long long skipped = 0;
+    for (Layer& l : ex->layers) {
+        const KernelVariant& lv = variants()[l.main.variant];
+        const Support out = l.deconv ? upconv2(bufs[l.src])
+                            : lv.wino && lv.wino_m == 4 ? wino_blocks(bufs[l.src], 4) : dilate(bufs[l.src], 1);
+        Support& d = bufs[l.dst];
+        if (d.m.empty()) d = out;
+        else
+            for (size_t k = 0; k < d.m.size(); ++k) d.m[k] |= out.m[k];
+        // the fused (or stand-alone) 2x2 pools behind conv1_2 / conv2_2 / conv3_3
+        if (l.name == "conv1_2") bufs[P1] = pool2(out);
+        if (l.name == "conv2_2") bufs[P2] = pool2(out);
+        if (l.name == "conv3_3") bufs[P3] = pool2(out);
+        // an item is kept if any output it writes may depend on the input: its conv tile (and with it the pooled
+        // outputs of the tile, the NHWC copy and the bottleneck), a transposed conv's 2TH x 2TW outputs
+        const SupportSum sum(out);
+        double kept_units = 0.0, all_units = 0.0;
+        for (Launch* ln : {&l.main, &l.tail}) {
+            if (ln->h_items.empty()) continue;
+            const KernelVariant& v = variants()[ln->variant];
+            const int f = l.deconv ? 2 : 1;
+            std::vector<int4> keep;
+            for (const int4& it : ln->h_items)
+                if (sum.any(f * it.z, f * (it.z + v.TH), f * it.w, f * (it.w + v.TW))) keep.push_back(it);
+            const double units = (double)v.TH * v.TW * v.BN;
+            kept_units += units * keep.size();
+            all_units += units * ln->h_items.size();
+            skipped += (long long)(ln->h_items.size() - keep.size());
+            ln->n_skip = (int)keep.size();
+            if (keep.empty()) continue;
+            DODT_HIP_CHECK(hipMalloc(&ln->d_skip, keep.size() * sizeof(int4)));
+            DODT_HIP_CHECK(hipMemcpy(ln->d_skip, keep.data(), keep.size() * sizeof(int4), hipMemcpyHostToDevice));
+        }
+        l.skip_frac = all_units > 0 ? kept_units / all_units : 1.0;
+    }
+    ex->skip_on = true;
+    if (skipped_items) *skipped_items = skipped;
+    if (getenv("DODT_DEBUG_PLAN"))
+        for (const Layer& l : ex->layers)
+            fprintf(stderr, "[dodt] %-16s skip tables: %d of %d items\n", l.name.c_str(),
+                    std::max(l.main.n_skip, 0) + std::max(l.tail.n_skip, 0), l.main.n_items + l.tail.n_items);
     return DODT_OK;
 }
 
@@ -1277,7 +1468,7 @@ int dodt_extractor_read_activation(dodt_extractor* ex, const char* name, float* 
 double dodt_extractor_bytes(const dodt_extractor* ex) {
     if (!ex) return 0.0;
     double b = 0.0;
-    for (const Layer& l : ex->layers) b += layer_bytes(ex, l);
+    for (const Layer& l : ex->layers) b += layer_bytes(ex, l, steady_frac(ex, l));
     if (ex->kind == DODT_EXTRACTOR_VGG)   // upsampling: conv4_3 read, the feature map written
         b += (double)ex->batch * ((double)ex->buf[C4C].H * ex->buf[C4C].W * 256 +
                                   (double)ex->out_h * ex->out_w * 256) * 4.0;
@@ -1288,7 +1479,7 @@ double dodt_extractor_bytes(const dodt_extractor* ex) {
 double dodt_extractor_mfma_flops(const dodt_extractor* ex) {
     if (!ex) return 0.0;
     double f = 0.0;
-    for (const Layer& l : ex->layers) f += layer_executed_flops(ex, l);
+    for (const Layer& l : ex->layers) f += layer_executed_flops(ex, l, steady_frac(ex, l));
     return f;
 }
 
@@ -1314,11 +1505,16 @@ int dodt_extractor_forward_timed(dodt_extractor* ex, const float* d_in, float* d
         snprintf(o.name, sizeof(o.name), "%s", l.name.c_str());
         const bool folded = ex->first2_variant >= 0 && i < 2;      // conv1_1 and conv1_2 are one launch, timed as conv1_2
         snprintf(o.kernel, sizeof(o.kernel), "%s", kernel_name(variants()[folded ? ex->first2_variant : l.main.variant]));
-        o.launches = folded && i == 0 ? 0 : l.tail.n_items > 0 ? 2 : 1;
-        o.items = l.main.n_items + l.tail.n_items;
-        o.flops_direct = layer_direct_flops(ex, l);
-        o.flops_executed = layer_executed_flops(ex, l);
-        o.bytes = layer_bytes(ex, l);
+        // (what this forward ran: the skip tables of a layer that skipped)
+        const bool sk = i < ex->skipping.size() && ex->skipping[i];
+        const double frac = sk ? l.skip_frac : 1.0;
+        const int n_main = sk && l.main.n_skip >= 0 ? l.main.n_skip : l.main.n_items;
+        const int n_tail = sk && l.tail.n_skip >= 0 ? l.tail.n_skip : l.tail.n_items;
+        o.launches = folded && i == 0 ? 0 : (n_main > 0) + (n_tail > 0);
+        o.items = n_main + n_tail;
+        o.flops_direct = layer_direct_flops(ex, l, frac);
+        o.flops_executed = layer_executed_flops(ex, l, frac);
+        o.bytes = layer_bytes(ex, l, frac);
         DODT_HIP_CHECK(hipEventElapsedTime(&o.ms, l.ev0, l.ev1));
     }
     return DODT_OK;
@@ -1326,9 +1522,8 @@ int dodt_extractor_forward_timed(dodt_extractor* ex, const float* d_in, float* d
 
 double dodt_extractor_flops(const dodt_extractor* ex) {
     if (!ex) return 0.0;
-    double f = 0.0;  // 2*M*N*K per layer; transposed convs counted on input pixels
-    for (const Layer& l : ex->layers)
-        f += 2.0 * l.H * l.W * (double)l.Cout * 9.0 * l.real_cin * ex->batch;
+    double f = 0.0;  // 2*M*N*K per layer; transposed convs counted on input pixels; skipped items not counted
+    for (const Layer& l : ex->layers) f += layer_direct_flops(ex, l, steady_frac(ex, l));
     return f;
 }
 

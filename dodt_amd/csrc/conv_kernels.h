@@ -804,7 +804,7 @@ template <int TW, int MTB, int CK, bool OUT16 = false, bool SPLIT = false>
 __global__ void __launch_bounds__(256)
 conv3x3_small_cin_kernel(const ConvArgs a) {
     using Cfg = SmallCfg<TW, MTB, CK>;
-    constexpr int TH = Cfg::TH, PH = Cfg::PH, PW = Cfg::PW, PS = Cfg::PS, MT = Cfg::MT;
+    constexpr int PH = Cfg::PH, PW = Cfg::PW, PS = Cfg::PS, MT = Cfg::MT;
     constexpr int BN = 32;
     constexpr int VEC = (CK % 4 == 0) ? 4 : 2;
 
@@ -817,7 +817,6 @@ conv3x3_small_cin_kernel(const ConvArgs a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wm = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
-    const int tiles = a.tiles_x * a.tiles_y;
     const int n_items = a.n_items;
     constexpr int CG = CK / VEC;
     constexpr int ITEMS = PH * PW * CG;
@@ -826,9 +825,10 @@ conv3x3_small_cin_kernel(const ConvArgs a) {
     float v[NIT][VEC];
     // every load of the thread is issued before the first LDS write (a loop with a load and its write per trip ran
     // one global-memory latency per trip)
+    // work item bid of the table: (frame, channel tile = 0, ty0, tx0) -- the host may leave tiles out
     auto load_patch = [&](int bid) {
-        const int frame = bid / tiles, t2 = bid - frame * tiles;
-        const int ty0 = (t2 / a.tiles_x) * TH, tx0 = (t2 % a.tiles_x) * TW;
+        const int4 item = a.items[bid];
+        const int frame = item.x, ty0 = item.z, tx0 = item.w;
         const float* in = a.in + (size_t)frame * a.in_frame_stride;
 #pragma unroll
         for (int i = 0; i < NIT; ++i) {
@@ -902,8 +902,8 @@ conv3x3_small_cin_kernel(const ConvArgs a) {
                 }
             }
         }
-        const int frame = bid / tiles, t2 = bid - frame * tiles;
-        const int ty0 = (t2 / a.tiles_x) * TH, tx0 = (t2 % a.tiles_x) * TW;
+        const int4 item = a.items[bid];
+        const int frame = item.x, ty0 = item.z, tx0 = item.w;
         float* out = a.out + (size_t)frame * a.out_frame_stride;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {

@@ -22,6 +22,7 @@
 #include "common.h"
 
 #include <cmath>
+#include <vector>
 
 namespace {
 
@@ -313,6 +314,57 @@ extern "C" int dodt_bev_slices(dodt_ctx* ctx, const void* d_points, int n_points
     hipLaunchKernelGGL(vox_finalize, dim3(dodt::ceil_div(fin, 256)), dim3(256), 0, ctx->stream,
                        d_points, P, out, list, counters, (uint32_t)cap);
     DODT_LAUNCH_CHECK();
+    return DODT_OK;
+}
+
+// Where vox_scatter can write: the frustum test in load_point keeps a point only if 0 < u < im_w.  u = un / w is a
+// ratio of affine functions of (x, y, z); where w > 0 on the whole cell box its extremes over the box lie at corners,
+// so the corners bound it.  Everything else (v, z > 0, extents, slices) can only drop more points.
+extern "C" int dodt_bev_support_mask(const dodt_bev_params* bp, int pad_top, uint8_t* mask, int rows, int cols) {
+    DODT_REQUIRE(bp && mask, "dodt_bev_support_mask: NULL argument");
+    DODT_REQUIRE(bp->point_format == DODT_PTS_VELO_XYZI,
+                 "dodt_bev_support_mask: only velodyne points pass the frustum filter");
+    DODT_REQUIRE(bp->voxel_size > 0 && pad_top >= 0, "dodt_bev_support_mask: bad voxel size or padding");
+    const double vs = bp->voxel_size;
+    const double minx = std::floor(bp->extents[0] / vs), maxx = std::ceil(bp->extents[1] / vs - 1);
+    const double minz = std::floor(bp->extents[4] / vs), maxz = std::ceil(bp->extents[5] / vs - 1);
+    const int X = (int)(maxx - minx + 1), Z = (int)(maxz - minz + 1);
+    DODT_REQUIRE(X > 0 && Z > 0 && rows == pad_top + Z && cols == X,
+                 "dodt_bev_support_mask: map is %dx%d, expected %dx%d", rows, cols, pad_top + Z, X);
+    const double* p = bp->p2;
+    const double ys[2] = {bp->extents[2], bp->extents[3]};
+    std::vector<uint8_t> cell((size_t)rows * cols, 0);
+    for (int zi = 0; zi < Z; ++zi) {
+        const double zs[2] = {(zi + minz) * vs, (zi + minz + 1) * vs};
+        for (int xi = 0; xi < X; ++xi) {
+            const double xs[2] = {(xi + minx) * vs, (xi + minx + 1) * vs};
+            bool maybe = false;
+            double umin = INFINITY, umax = -INFINITY;
+            for (int k = 0; k < 8; ++k) {
+                const double x = xs[k & 1], y = ys[(k >> 1) & 1], z = zs[k >> 2];
+                const double w = p[8] * x + p[9] * y + p[10] * z + p[11];
+                if (!(w > 0.0)) { maybe = true; break; }
+                const double u = (p[0] * x + p[1] * y + p[2] * z + p[3]) / w;
+                umin = std::fmin(umin, u);
+                umax = std::fmax(umax, u);
+            }
+            if (maybe || (umax > 0.0 && umin < bp->im_w)) cell[(size_t)(pad_top + Z - 1 - zi) * cols + xi] = 1;
+        }
+    }
+    // vox_finalize writes the origin cell of a slice with <= 1 member (its substitute point (0, 0, 0))
+    const int ox = 0 - (int)minx, oz = 0 - (int)minz;
+    if (ox >= 0 && ox < X && oz >= 0 && oz < Z) cell[(size_t)(pad_top + Z - 1 - oz) * cols + ox] = 1;
+    // one cell of margin (floor(x / vs) next to a cell edge); the pad rows stay 0
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < cols; ++c) {
+            uint8_t m = 0;
+            for (int dr = -1; dr <= 1 && !m && r >= pad_top; ++dr)
+                for (int dc = -1; dc <= 1 && !m; ++dc) {
+                    const int rr = r + dr, cc = c + dc;
+                    m = rr >= 0 && rr < rows && cc >= 0 && cc < cols && cell[(size_t)rr * cols + cc];
+                }
+            mask[(size_t)r * cols + c] = m;
+        }
     return DODT_OK;
 }
 

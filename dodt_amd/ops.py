@@ -66,6 +66,20 @@ def bev_slices(ctx, d_points, n_points, bev_params, d_bev_out, d_occ_bits=None):
                                        _p(d_occ_bits)), 'dodt_bev_slices')
 
 
+def bev_support_mask(bev_params, pad_top=0, lib=None):
+    """(pad_top + Z, X) uint8: the BEV cells dodt_bev_slices can ever write under bev_params (velodyne points: the
+    image-frustum filter), in a pyramid extractor's padded input layout; host only (dodt_bev_support_mask)."""
+    lib = lib or _lib.load()
+    vs = bev_params.voxel_size
+    ext = list(bev_params.extents)
+    nx = int(np.ceil(ext[1] / vs - 1) - np.floor(ext[0] / vs) + 1)
+    nz = int(np.ceil(ext[5] / vs - 1) - np.floor(ext[4] / vs) + 1)
+    out = np.zeros((int(pad_top) + nz, nx), np.uint8)
+    _lib.check(lib.dodt_bev_support_mask(C.byref(bev_params), int(pad_top), out.ctypes.data, out.shape[0],
+                                         out.shape[1]), 'dodt_bev_support_mask')
+    return out
+
+
 def bev_status(ctx):
     f = C.c_int()
     _lib.check(ctx.lib.dodt_bev_status(ctx.handle, C.byref(f)), 'dodt_bev_status')

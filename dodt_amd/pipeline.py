@@ -30,7 +30,7 @@ import os
 import numpy as np
 
 from dodt_amd import config as _config
-from dodt_amd import device, ops, tracking
+from dodt_amd import _lib, device, ops, tracking
 from dodt_amd.core.anchor_generators import grid_anchor_3d_generator as gen
 from dodt_amd.core.avod_fc_layers.fusion_fc_layers import EarlyFusionFcLayers
 from dodt_amd.core.feature_extractors.vgg import BevVgg, ImgVgg
@@ -60,13 +60,16 @@ class FramePairPipeline(object):
                  r0_rect=_config.KITTI_R0_RECT, tr_velo_to_cam=_config.KITTI_TR_VELO_TO_CAM,
                  image_wh=_config.KITTI_IMAGE_WH, n_points_max=120000, rpn_nms_size=1024,
                  pairs_per_step=1, side_streams=None, head_params=None, conv_dtype='f32',
-                 head_dtype='f32', reuse_streams_of=None, tail_sets=None, temporal=None, tracker=None):
+                 head_dtype='f32', reuse_streams_of=None, tail_sets=None, temporal=None, tracker=None,
+                 bev_input_skip=True):
         """temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
         module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it.
         tracker: None, or dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3, classes=('Car',),
         max_sequence_dets=65536) -- the IoU tracker on the device after every step: the pairs of the steps, in order,
         are one sequence until end_sequence() (see _tracker_step, tracks_so_far()); None enqueues and allocates nothing
-        for it."""
+        for it.
+        bev_input_skip: the fp32 BEV net skips the tiles that no BEV cell inside the camera's frustum reaches (their
+        values depend on the weights alone, dodt_extractor_set_input_support); False: full tables."""
         self.ctx = ctx
         self.cfg = cfg
         self.p2 = np.asarray(p2, dtype=np.float64)
@@ -152,6 +155,12 @@ class FramePairPipeline(object):
         self.bev_net = bev_cls(ctx=ctx, shared_gpu=True, conv_dtype=conv_dtype)
         self.bev_net.load_params(bev_params)
         self.bev_net._ensure(self.nf, self.bev_h, self.bev_w, cfg['bev_depth'])
+        # only cells inside the image frustum are ever non-zero (the ego-motion warp comes before the frustum test)
+        self.bev_skipped_items = 0
+        if bev_input_skip and conv_dtype == 'f32' and hasattr(self.bev_net, 'set_input_support') \
+                and self.bp.point_format == _lib.PTS_VELO_XYZI:
+            self.bev_skipped_items = self.bev_net.set_input_support(
+                ops.bev_support_mask(self.bp, self.bev_net.PAD_TOP, ctx.lib))
         self.img_net = img_cls(ctx=self.img_ctx, shared_gpu=True, conv_dtype=conv_dtype)
         self.img_net.load_params(img_params)
         self.img_net._ensure(self.nf, self.img_h, self.img_w, 4)

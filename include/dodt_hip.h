@@ -140,6 +140,15 @@ int dodt_bev_slices(dodt_ctx* ctx, const void* d_points, int n_points,
  * the reference raises ValueError("Extents are smaller than ...")
  * (voxel_grid_2d.py:130-138) -- or overflowed its work list (*flags & 2). */
 int dodt_bev_status(dodt_ctx* ctx, int* flags);
+/* Host only (no device work): the BEV cells dodt_bev_slices can ever write for DODT_PTS_VELO_XYZI points under
+ * `params`, as a (pad_top + Z, X) byte map in a pyramid extractor's padded input layout (row pad_top + Z-1-z, the
+ * pad_top rows 0): 1 = possibly written, 0 = zero in every frame.  A point survives only if its image column
+ * u = (P2 p)_0 / (P2 p)_2 lies in (0, im_w); a cell counts as possibly written if u, evaluated in float64 at the
+ * 8 corners of its (x, y, z) box over the y extents, reaches (0, im_w), or if w = (P2 p)_2 <= 0 at a corner.
+ * Then the substitute-point cell of the slice quirk (x = z = 0) is added and the map dilated by one cell.  The
+ * frustum test follows the ego-motion warp, so the map holds for has_pre_transform frames too.
+ * DODT_PTS_CAM_3XN skips the frustum test: DODT_ERR_INVALID. */
+int dodt_bev_support_mask(const dodt_bev_params* params, int pad_top, uint8_t* mask_out, int rows, int cols);
 
 /* ---- a4: empty-anchor filter -------------------------------------------------
  * Stands behind get_empty_anchor_filter_2d (avod/core/anchor_filter.py:64-119)
@@ -257,6 +266,19 @@ int dodt_extractor_forward_padded(dodt_extractor* ex, const float* d_x0, float* 
 /* Until further notice (d_x0 = NULL: back to its own buffer) forwards without an input argument read d_x0, laid out
  * as above, as the extractor's input buffer; d_x0 must outlive that use (tools: stand-alone timing on a pipeline's inputs). */
 int dodt_extractor_set_input(dodt_extractor* ex, const float* d_x0);
+/* Input support of an fp32 pyramid extractor: mask (rows = pad_top + in_h, cols = in_w bytes, host memory, e.g.
+ * dodt_bev_support_mask) is nonzero wherever some input frame may be nonzero; every input it marks 0 is zero in
+ * every frame.  The mask is propagated through the net (3x3 convs dilate by 1, pools OR their 2x2 windows,
+ * transposed convs dilate by 2 at the output resolution, concat ORs), and each layer's work items whose outputs all
+ * lie where no input reaches are dropped from its launches (table order kept).  Skipped outputs are not rewritten:
+ * they keep the input-independent values of a full forward.  So the first forward after this call or after any
+ * dodt_extractor_set_layer runs full tables, and pyramid_fusion1 runs full tables for every (d_feat_out,
+ * d_bottleneck_out) pair it has not written since then (pairs are told apart by address: a caller that frees
+ * and reallocates its output buffers calls this again); the caller must not write those buffers itself.  mask NULL:
+ * full tables again.  The bf16 / split conv paths and DODT_EXTRACTOR_VGG keep full tables (the call only checks the
+ * sizes).  *skipped_items (may be NULL): work items dropped per forward in steady state. */
+int dodt_extractor_set_input_support(dodt_extractor* ex, const uint8_t* mask, int rows, int cols,
+                                     long long* skipped_items);
 /* Size of the feature map forward() returns: (in_h, in_w, 32) for the pyramid,
  * (in_h / 8 * 4, in_w / 8 * 4, 256) for DODT_EXTRACTOR_VGG. */
 int dodt_extractor_output_shape(const dodt_extractor* ex, int* h, int* w, int* c);
@@ -270,7 +292,9 @@ int dodt_extractor_first_layers_folded(const dodt_extractor* ex);
 int dodt_extractor_read_activation(dodt_extractor* ex, const char* name, float* dst,
                                    int* h, int* w, int* c);
 /* FLOPs of one forward call (2*M*N*K summed over conv layers, all frames): the ALGORITHMIC
- * count of the direct form, whatever kernel computes a layer. */
+ * count of the direct form, whatever kernel computes a layer.  With skip tables
+ * (dodt_extractor_set_input_support) this, dodt_extractor_mfma_flops and dodt_extractor_bytes count the work of a
+ * steady-state forward: skipped items are not counted. */
 double dodt_extractor_flops(const dodt_extractor* ex);
 /* FLOPs the matrix pipe executes for one forward.  The fp32 3x3 stride-1 layers run as Winograd
  * minimal filtering, fp32 throughout: F(4x4,3x3) (36 multiplications per 4x4 outputs and channel pair
@@ -285,6 +309,7 @@ double dodt_extractor_bytes(const dodt_extractor* ex);
  * waits for the stream).  bench.py's roofline object is built from this: `kernel` is the
  * __global__ function a rocprofv3 kernel trace lists, flops_executed what the matrix pipe issues
  * for the layer (see dodt_extractor_mfma_flops), bytes the layer's share of dodt_extractor_bytes. */
+/* (items, launches, flops and bytes: what that forward ran -- a forward on skip tables reports the kept items.) */
 typedef struct dodt_layer_info {
     char name[32];          /* TF variable scope of the layer */
     char kernel[48];
