@@ -32,6 +32,8 @@ class _VggPyr(object):
         self._shape = None
         self._params = None
         self._support = None
+        self._frame_tables = False
+        self.frame_tables_on = False
 
     # -- lifetime ---------------------------------------------------------------
     def _ensure(self, batch, h, w, c):
@@ -98,12 +100,16 @@ class _VggPyr(object):
             self._handle, C.c_void_p(d_x0.ptr), C.c_void_p(d_feat.ptr),
             None if d_bottleneck is None else C.c_void_p(d_bottleneck.ptr)), 'dodt_extractor_forward_padded')
 
-    def set_input_support(self, mask):
+    def set_input_support(self, mask, frame_tables=False):
         """mask: (PAD_TOP + h, w) array, nonzero wherever an input may be nonzero (dodt_amd.ops.bev_support_mask);
         the fp32 net then skips the work items whose outputs no input reaches (dodt_extractor_set_input_support).
         None: full tables.  Kept across a rebuild for another batch size.  Output buffers are told apart by address:
-        the skipped regions of the ones a forward has written keep their values.  Returns the items skipped per forward."""
+        the skipped regions of the ones a forward has written keep their values.  Returns the items skipped per forward.
+        frame_tables: every forward also filters these tables on the device by the cells that are non-zero in its own
+        input (dodt_extractor_set_frame_tables); frame_tables_on tells whether the net took them."""
         self._support = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        self._frame_tables = bool(frame_tables) and mask is not None
+        self.frame_tables_on = False
         return self._push_support() if self._handle is not None else 0
 
     def _push_support(self):
@@ -112,7 +118,20 @@ class _VggPyr(object):
         _lib.check(self._ctx.lib.dodt_extractor_set_input_support(
             self._handle, None if m is None else m.ctypes.data, 0 if m is None else m.shape[0],
             0 if m is None else m.shape[1], C.byref(n)), 'dodt_extractor_set_input_support')
+        if self._frame_tables:
+            on = C.c_int()
+            _lib.check(self._ctx.lib.dodt_extractor_set_frame_tables(self._handle, 1, C.byref(on)),
+                       'dodt_extractor_set_frame_tables')
+            self.frame_tables_on = bool(on.value)
         return n.value
+
+    def frame_items(self):
+        """Work items each layer of the last forward ran from per-frame tables, in launch order; -1 for a layer that
+        ran a full or static table (dodt_extractor_frame_items; waits for the stream)."""
+        n = self._ctx.lib.dodt_extractor_layer_count(self._handle)
+        items = (C.c_int * n)()
+        _lib.check(self._ctx.lib.dodt_extractor_frame_items(self._handle, items, n), 'dodt_extractor_frame_items')
+        return list(items)
 
     def set_input(self, d_x0):
         """Forwards without an input argument read d_x0 (extractor input layout) from now on; None: the extractor's

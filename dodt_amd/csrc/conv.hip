@@ -24,6 +24,7 @@
 #include "common.h"
 #include "conv_kernels.h"
 #include "conv_variants.h"
+#include "frame_tables.h"
 
 namespace {
 
@@ -378,6 +379,9 @@ struct Launch {
     std::vector<int4> h_items;   // the full table on the host (skip tables are filtered from it)
     int n_skip = -1;             // >= 0: the skip table (dodt_extractor_set_input_support), possibly empty
     int4* d_skip = nullptr;
+    // per-frame tables (dodt_extractor_set_frame_tables): this forward's items of the skip table and their count
+    int4* d_run = nullptr;
+    int* d_count = nullptr;
 };
 
 struct Layer {
@@ -425,7 +429,18 @@ struct dodt_extractor {
     bool skip_on = false;
     bool primed = false;
     std::vector<std::pair<const float*, const float*>> primed_out;
-    std::vector<char> skipping;   // per layer: this forward runs its skip tables
+    std::vector<char> skipping;   // per layer: this forward runs its skip tables (2: the per-frame ones)
+    // per-frame tables (dodt_extractor_set_frame_tables): the builder's plan (frame_tables.h), its device copy, the
+    // frames' input bit masks, every allocation of the tables, and per remembered output pair (primed_out) which
+    // of the eight item sets of pyramid_fusion1's last forward into it is the pair's
+    bool frame_on = false;
+    dodt::ft::Plan frame_plan;
+    dodt::ft::Plan* d_frame_plan = nullptr;
+    uint32_t* d_frame_bits = nullptr;
+    int* d_frame_counts = nullptr;
+    std::vector<void*> frame_allocs;
+    uint8_t* out_prev[8][2] = {};
+    std::vector<int> out_slot;
 };
 
 namespace {
@@ -481,6 +496,10 @@ int run_launch(dodt_extractor* ex, const Layer& l, const Launch& ln, int which,
     a.items = skip ? ln.d_skip : ln.d_items;
     a.n_items = skip ? ln.n_skip : ln.n_items;
     if (a.n_items == 0) return DODT_OK;   // every item of the launch skipped
+    // per-frame tables: the builder's launches ahead in the stream wrote this forward's items and their count
+    const bool per_frame = skip && ex->skipping[li] == 2 && ln.d_run;
+    if (per_frame) a.items = ln.d_run;
+    a.n_items_dev = per_frame ? ln.d_count : nullptr;
     a.in_part_stride = (long long)src.frame_floats() * ex->batch;
     a.out_part_stride = (long long)dst.frame_floats() * ex->batch;
     a.pool_part_stride = pool_dst >= 0 ? (long long)ex->buf[pool_dst].frame_floats() * ex->batch : 0;
@@ -795,7 +814,128 @@ Support wino_blocks(const Support& a, int m) {
     return o;
 }
 
+// ---------------------------------------------------------------------------
+// per-frame tables (frame_tables.h): three launches at the head of a forward
+// ---------------------------------------------------------------------------
+// the non-zero cells of the frames' input maps (NHWC, any channel; -0.0 counts as non-zero: it is not the +0.0 the
+// skipped outputs were computed from) as bit masks: half a wave per word
+__global__ void __launch_bounds__(256)
+frame_support_kernel(const float* __restrict__ x, long long frame_stride, int H, int W, int C, uint32_t* __restrict__ bits) {
+    const int p = dodt::ft::pitch(W), words = H * p;
+    const int word = blockIdx.x * 8 + (threadIdx.x >> 5), frame = blockIdx.y;
+    const int y = word / p, cx = (word - y * p) * 32 + (threadIdx.x & 31);
+    bool nz = false;
+    if (word < words && cx < W) {
+        const uint2* c = reinterpret_cast<const uint2*>(x + (size_t)frame * frame_stride + ((size_t)y * W + cx) * C);
+        uint32_t acc = 0;
+        for (int k = 0; k < C / 2; ++k) {      // (C is even: dodt_extractor_create)
+            const uint2 v = c[k];
+            acc |= v.x | v.y;
+        }
+        nz = (acc & 0x7fffffffu) != 0;
+    }
+    const unsigned long long b = __ballot(nz);
+    if ((threadIdx.x & 31) == 0 && word < words)
+        bits[(size_t)frame * words + word] = (uint32_t)((threadIdx.x & 32) ? b >> 32 : b);
+}
+
+// one workgroup per frame walks the net's geometry on two masks in LDS and marks the items its frame reaches
+__global__ void __launch_bounds__(1024)
+frame_walk_kernel(const dodt::ft::Plan* __restrict__ pl, const uint32_t* __restrict__ bits) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t ft_lds[];
+    const int words = dodt::ft::level_words(pl->H, pl->W, 0);
+    uint32_t* a = ft_lds;
+    uint32_t* b = ft_lds + words;
+    const int frame = blockIdx.x;
+    for (int i = threadIdx.x; i < words; i += blockDim.x) a[i] = bits[(size_t)frame * words + i];
+    __syncthreads();
+    dodt::ft::walk(*pl, frame, a, b, (int)threadIdx.x, (int)blockDim.x, [] { __syncthreads(); });
+}
+
+// one workgroup per table: the items this forward runs, in the table's order (a prefix sum: the same table for the
+// same masks, whatever order the workgroups run in)
+__global__ void __launch_bounds__(256)
+frame_compact_kernel(const dodt::ft::Plan* __restrict__ pl, uint8_t* last_prev_main, uint8_t* last_prev_tail) {
+    __shared__ int scan[257];
+    const dodt::ft::Table t = pl->t[blockIdx.x];
+    if (!t.items) return;
+    const bool last = (int)blockIdx.x / 2 == dodt::ft::kLayers - 1;     // pyramid_fusion1: the output pair's set
+    uint8_t* prev = last ? ((blockIdx.x & 1) ? last_prev_tail : last_prev_main) : t.prev;
+    dodt::ft::compact(t, prev, scan, (int)threadIdx.x, (int)blockDim.x, [] { __syncthreads(); });
+}
+
+void free_frame_tables(dodt_extractor* ex) {
+    for (void* p : ex->frame_allocs) (void)hipFree(p);
+    ex->frame_allocs.clear();
+    for (Layer& l : ex->layers)
+        for (Launch* ln : {&l.main, &l.tail}) {
+            ln->d_run = nullptr;
+            ln->d_count = nullptr;
+        }
+    ex->frame_plan = dodt::ft::Plan();
+    ex->d_frame_plan = nullptr;
+    ex->d_frame_bits = nullptr;
+    ex->d_frame_counts = nullptr;
+    ex->out_slot.clear();
+    ex->frame_on = false;
+}
+
+// the builder's launches for this forward's input; slot: the output pair's item set of pyramid_fusion1
+int build_frame_tables(dodt_extractor* ex, int slot) {
+    const Buffer& x0 = ex->buf[X0];
+    const int words = dodt::ft::level_words(ex->H, ex->W, 0);
+    hipStream_t s = ex->ctx->stream;
+    hipLaunchKernelGGL(frame_support_kernel, dim3((unsigned)dodt::ceil_div(words, 8), (unsigned)ex->batch), dim3(256), 0, s,
+                       x0.ptr, (long long)x0.frame_floats(), ex->H, ex->W, x0.C, ex->d_frame_bits);
+    DODT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(frame_walk_kernel, dim3((unsigned)ex->batch), dim3(1024), (size_t)words * 8, s,
+                       ex->d_frame_plan, ex->d_frame_bits);
+    DODT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(frame_compact_kernel, dim3(dodt::ft::kTables), dim3(256), 0, s, ex->d_frame_plan,
+                       ex->out_prev[slot][0], ex->out_prev[slot][1]);
+    DODT_LAUNCH_CHECK();
+    return DODT_OK;
+}
+
+// the per-frame counts of the last forward (waits for the stream); false: per-frame tables are off
+bool read_frame_counts(const dodt_extractor* ex, int (&counts)[dodt::ft::kTables]) {
+    if (!ex->frame_on) return false;
+    if (hipStreamSynchronize(ex->ctx->stream) != hipSuccess) return false;
+    return hipMemcpy(counts, ex->d_frame_counts, sizeof(counts), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// The share of a layer's work that is counted: the steady state's (steady_frac), or with per-frame tables what the
+// last finished forward ran of a layer that took them (waits for the stream).
+struct WorkShare {
+    int counts[dodt::ft::kTables];
+    bool have;
+    explicit WorkShare(const dodt_extractor* ex) : have(read_frame_counts(ex, counts)) {}
+    bool per_frame(const dodt_extractor* ex, size_t li) const {
+        return have && li < ex->skipping.size() && ex->skipping[li] == 2;
+    }
+    int items(const dodt_extractor* ex, size_t li, int j) const {
+        const Layer& l = ex->layers[li];
+        return (j ? l.tail : l.main).d_count ? counts[2 * li + j] : 0;
+    }
+    double of(const dodt_extractor* ex, const Layer& l) const {
+        const size_t li = &l - ex->layers.data();
+        if (!per_frame(ex, li)) return steady_frac(ex, l);
+        double kept = 0.0, all = 0.0;
+        int j = 0;
+        for (const Launch* ln : {&l.main, &l.tail}) {
+            const int jj = j++;
+            if (ln->h_items.empty()) continue;
+            const KernelVariant& v = variants()[ln->variant];
+            const double units = (double)v.TH * v.TW * v.BN;
+            kept += units * items(ex, li, jj);
+            all += units * ln->h_items.size();
+        }
+        return all > 0 ? kept / all : 1.0;
+    }
+};
+
 void free_skip_tables(dodt_extractor* ex) {
+    free_frame_tables(ex);     // (they filter the skip tables)
     for (Layer& l : ex->layers) {
         for (Launch* ln : {&l.main, &l.tail}) {
             if (ln->d_skip) (void)hipFree(ln->d_skip);
@@ -971,6 +1111,7 @@ int dodt_extractor_destroy(dodt_extractor* ex) {
     if (!ex) return DODT_OK;
     if (ex->ctx) (void)hipStreamSynchronize(ex->ctx->stream);
     if (ex->own_x0) ex->buf[X0].ptr = ex->own_x0;      // (never free a caller's input buffer)
+    free_frame_tables(ex);
     for (int i = 0; i < NBUF; ++i)
         if (ex->buf[i].ptr) (void)hipFree(ex->buf[i].ptr);
     for (Layer& l : ex->layers) {
@@ -1251,10 +1392,38 @@ int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_
     // primes every output pair of its own
     const bool skip = ex->skip_on && ex->primed;
     bool last_skip = false;
-    for (const auto& pr : ex->primed_out) last_skip |= skip && pr.first == d_feat_out && pr.second == d_bottleneck_out;
-    ex->skipping.assign(ex->layers.size(), skip);
-    if (ex->kind == DODT_EXTRACTOR_VGG_PYR) ex->skipping[find_layer(ex, "pyramid_fusion1")] = last_skip;
+    size_t pair = 0;
+    while (pair < ex->primed_out.size() &&
+           !(ex->primed_out[pair].first == d_feat_out && ex->primed_out[pair].second == d_bottleneck_out))
+        ++pair;
+    const bool known_pair = pair < ex->primed_out.size();
+    last_skip = skip && known_pair;
+    ex->skipping.assign(ex->layers.size(), skip ? (ex->frame_on ? 2 : 1) : 0);
+    if (ex->kind == DODT_EXTRACTOR_VGG_PYR)
+        ex->skipping[find_layer(ex, "pyramid_fusion1")] = last_skip ? (ex->frame_on ? 2 : 1) : 0;
     int rc;
+    if (ex->frame_on) {
+        // Per-frame tables: every launch runs the items this input reaches and the ones the last forward into the
+        // same buffer reached (those go back to their input-independent values), and the builder keeps this input's
+        // set for the next forward.  A forward on full tables (priming; pyramid_fusion1 into a pair it has not
+        // written) records its set the same way.  A new pair takes the set of the pair it evicts, or a free one.
+        if (ex->primed_out.empty()) ex->out_slot.clear();
+        int slot = 0;
+        if (known_pair) {
+            slot = ex->out_slot[pair];
+        } else if (ex->primed_out.size() < 8) {
+            bool used[8] = {};
+            for (int k : ex->out_slot) used[k] = true;
+            while (used[slot]) ++slot;
+        } else {
+            slot = ex->out_slot[0];
+        }
+        if ((rc = build_frame_tables(ex, slot))) return rc;
+        if (!known_pair) {
+            if (ex->primed_out.size() >= 8) ex->out_slot.erase(ex->out_slot.begin());
+            ex->out_slot.push_back(slot);
+        }
+    }
     auto L = [&](const char* n) -> const Layer& { return ex->layers[find_layer(ex, n)]; };
 #define RUN(name)                                           \
     if ((rc = run_layer(ex, L(name), nullptr, 0, 0))) return rc;
@@ -1315,7 +1484,7 @@ int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_
     }
     if (ex->skip_on) {
         ex->primed = true;
-        if (!last_skip) {
+        if (!known_pair) {
             ex->primed_out.emplace_back(d_feat_out, d_bottleneck_out);
             if (ex->primed_out.size() > 8) ex->primed_out.erase(ex->primed_out.begin());   // (re-primed when back)
         }
@@ -1403,6 +1572,125 @@ int dodt_extractor_set_input_support(dodt_extractor* ex, const uint8_t* mask, in
     return DODT_OK;
 }
 
+int dodt_extractor_set_frame_tables(dodt_extractor* ex, int on, int* enabled) {
+    DODT_REQUIRE(ex, "dodt_extractor_set_frame_tables: extractor is NULL");
+    namespace ft = dodt::ft;
+    if (enabled) *enabled = 0;
+    DODT_HIP_CHECK(hipStreamSynchronize(ex->ctx->stream));   // (no launch still reads the old tables)
+    free_frame_tables(ex);
+    if (!on || !ex->skip_on) return DODT_OK;
+    // the layers in the builder's order, none of them block-wise (F(4x4) Winograd); both masks of a frame in LDS
+    if ((int)ex->layers.size() != ft::kLayers) return DODT_OK;
+    for (const Layer& l : ex->layers)
+        for (const Launch* ln : {&l.main, &l.tail})
+            if (ln->variant >= 0 && variants()[ln->variant].wino && variants()[ln->variant].wino_m == 4) return DODT_OK;
+    const size_t words = (size_t)ft::level_words(ex->H, ex->W, 0);
+    if (words * 8 > 160 * 1024 - 1024) return DODT_OK;
+    DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&frame_walk_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(words * 8)));
+    auto alloc = [&](size_t bytes, void** p) {
+        hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
+        if (e == hipSuccess) ex->frame_allocs.push_back(*p);
+        return e;
+    };
+    ft::Plan& pl = ex->frame_plan;
+    pl.H = ex->H; pl.W = ex->W; pl.frames = ex->batch;
+    DODT_HIP_CHECK(alloc((size_t)ex->batch * ft::stash_words(ex->H, ex->W) * 4, (void**)&pl.stash));
+    DODT_HIP_CHECK(alloc((size_t)ex->batch * words * 4, (void**)&ex->d_frame_bits));
+    DODT_HIP_CHECK(alloc(ft::kTables * sizeof(int), (void**)&ex->d_frame_counts));
+    for (size_t li = 0; li < ex->layers.size(); ++li) {
+        Layer& l = ex->layers[li];
+        int j = 0;
+        for (Launch* ln : {&l.main, &l.tail}) {
+            ft::Table& t = pl.t[2 * li + j];
+            const int jj = j++;
+            if (ln->n_skip <= 0) continue;
+            const KernelVariant& v = variants()[ln->variant];
+            t.items = ln->d_skip;
+            t.n = ln->n_skip;
+            t.f = l.deconv ? 2 : 1;
+            t.th = t.f * v.TH;
+            t.tw = t.f * v.TW;
+            DODT_HIP_CHECK(alloc(t.n, (void**)&t.now));
+            if (li + 1 == ex->layers.size()) {     // pyramid_fusion1: a set per remembered output pair
+                for (int k = 0; k < 8; ++k) DODT_HIP_CHECK(alloc(t.n, (void**)&ex->out_prev[k][jj]));
+            } else {
+                DODT_HIP_CHECK(alloc(t.n, (void**)&t.prev));
+            }
+            DODT_HIP_CHECK(alloc(t.n * sizeof(int4), (void**)&t.run));
+            t.count = ex->d_frame_counts + 2 * li + jj;
+            ln->d_run = t.run;
+            ln->d_count = t.count;
+        }
+    }
+    DODT_HIP_CHECK(alloc(sizeof(ft::Plan), (void**)&ex->d_frame_plan));
+    DODT_HIP_CHECK(hipMemcpy(ex->d_frame_plan, &pl, sizeof(ft::Plan), hipMemcpyHostToDevice));
+    // the next forward runs full tables and records its input's items
+    ex->primed = false;
+    ex->primed_out.clear();
+    ex->frame_on = true;
+    if (enabled) *enabled = 1;
+    return DODT_OK;
+}
+
+int dodt_extractor_frame_items(dodt_extractor* ex, int* items, int n) {
+    DODT_REQUIRE(ex && items && n >= (int)ex->layers.size(),
+                 "dodt_extractor_frame_items: items must hold dodt_extractor_layer_count() entries");
+    int counts[dodt::ft::kTables];
+    const bool have = read_frame_counts(ex, counts);
+    for (size_t i = 0; i < ex->layers.size(); ++i) {
+        const Layer& l = ex->layers[i];
+        const bool pf = have && i < ex->skipping.size() && ex->skipping[i] == 2;
+        items[i] = pf ? (l.main.d_count ? counts[2 * i] : 0) + (l.tail.d_count ? counts[2 * i + 1] : 0) : -1;
+    }
+    return DODT_OK;
+}
+
+int dodt_frame_tables_host(const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
+                           const int* items, int n_items, const uint8_t* prev, int* run, int* n_run) {
+    namespace ft = dodt::ft;
+    DODT_REQUIRE(masks && items && run && n_run && frames >= 1 && n_items >= 0,
+                 "dodt_frame_tables_host: NULL argument");
+    DODT_REQUIRE(rows > 0 && cols > 0 && rows % 8 == 0 && cols % 8 == 0,
+                 "dodt_frame_tables_host: masks of %dx%d, not divisible by 8", rows, cols);
+    DODT_REQUIRE(layer >= 0 && layer < ft::kLayers && th > 0 && tw > 0, "dodt_frame_tables_host: bad layer or tile");
+    for (int i = 0; i < n_items; ++i)
+        DODT_REQUIRE(items[4 * i] >= 0 && items[4 * i] < frames, "dodt_frame_tables_host: item %d names frame %d", i,
+                     items[4 * i]);
+    const bool deconv = layer == 10 || layer == 12 || layer == 14;
+    std::vector<uint8_t> now((size_t)n_items, 0), pv((size_t)n_items, 0);
+    if (prev) pv.assign(prev, prev + n_items);
+    int count = 0;
+    ft::Plan pl;
+    pl.H = rows; pl.W = cols; pl.frames = frames;
+    std::vector<uint32_t> stash((size_t)ft::stash_words(rows, cols) * frames);
+    pl.stash = stash.data();
+    ft::Table& t = pl.t[2 * layer];
+    t.items = reinterpret_cast<const int4*>(items);
+    t.n = n_items;
+    t.f = deconv ? 2 : 1;
+    t.th = t.f * th;
+    t.tw = t.f * tw;
+    t.now = now.data();
+    t.prev = pv.data();
+    t.run = reinterpret_cast<int4*>(run);
+    t.count = &count;
+    const int words = ft::level_words(rows, cols, 0), p = ft::pitch(cols);
+    std::vector<uint32_t> a(words), b(words);
+    for (int f = 0; f < frames; ++f) {
+        std::fill(a.begin(), a.end(), 0u);
+        for (int y = 0; y < rows; ++y)
+            for (int x = 0; x < cols; ++x)
+                if (masks[((size_t)f * rows + y) * cols + x]) a[y * p + (x >> 5)] |= 1u << (x & 31);
+        ft::walk(pl, f, a.data(), b.data(), 0, 1, [] {});
+    }
+    int scan[2];
+    if (n_items > 0) ft::compact(t, pv.data(), scan, 0, 1, [] {});
+    *n_run = count;
+    return DODT_OK;
+}
+
 int dodt_extractor_output_shape(const dodt_extractor* ex, int* h, int* w, int* c) {
     DODT_REQUIRE(ex, "dodt_extractor_output_shape: NULL argument");
     if (h) *h = ex->out_h;
@@ -1468,7 +1756,8 @@ int dodt_extractor_read_activation(dodt_extractor* ex, const char* name, float* 
 double dodt_extractor_bytes(const dodt_extractor* ex) {
     if (!ex) return 0.0;
     double b = 0.0;
-    for (const Layer& l : ex->layers) b += layer_bytes(ex, l, steady_frac(ex, l));
+    const WorkShare share(ex);
+    for (const Layer& l : ex->layers) b += layer_bytes(ex, l, share.of(ex, l));
     if (ex->kind == DODT_EXTRACTOR_VGG)   // upsampling: conv4_3 read, the feature map written
         b += (double)ex->batch * ((double)ex->buf[C4C].H * ex->buf[C4C].W * 256 +
                                   (double)ex->out_h * ex->out_w * 256) * 4.0;
@@ -1479,7 +1768,8 @@ double dodt_extractor_bytes(const dodt_extractor* ex) {
 double dodt_extractor_mfma_flops(const dodt_extractor* ex) {
     if (!ex) return 0.0;
     double f = 0.0;
-    for (const Layer& l : ex->layers) f += layer_executed_flops(ex, l, steady_frac(ex, l));
+    const WorkShare share(ex);
+    for (const Layer& l : ex->layers) f += layer_executed_flops(ex, l, share.of(ex, l));
     return f;
 }
 
@@ -1498,6 +1788,7 @@ int dodt_extractor_forward_timed(dodt_extractor* ex, const float* d_in, float* d
     ex->timed = false;
     if (rc) return rc;
     DODT_HIP_CHECK(hipStreamSynchronize(ex->ctx->stream));
+    const WorkShare share(ex);
     for (size_t i = 0; i < ex->layers.size(); ++i) {
         const Layer& l = ex->layers[i];
         dodt_layer_info& o = info[i];
@@ -1507,9 +1798,10 @@ int dodt_extractor_forward_timed(dodt_extractor* ex, const float* d_in, float* d
         snprintf(o.kernel, sizeof(o.kernel), "%s", kernel_name(variants()[folded ? ex->first2_variant : l.main.variant]));
         // (what this forward ran: the skip tables of a layer that skipped)
         const bool sk = i < ex->skipping.size() && ex->skipping[i];
-        const double frac = sk ? l.skip_frac : 1.0;
-        const int n_main = sk && l.main.n_skip >= 0 ? l.main.n_skip : l.main.n_items;
-        const int n_tail = sk && l.tail.n_skip >= 0 ? l.tail.n_skip : l.tail.n_items;
+        const bool pf = share.per_frame(ex, i);     // (per-frame tables: the counts the builder wrote)
+        const double frac = pf ? share.of(ex, l) : sk ? l.skip_frac : 1.0;
+        const int n_main = pf ? share.items(ex, i, 0) : sk && l.main.n_skip >= 0 ? l.main.n_skip : l.main.n_items;
+        const int n_tail = pf ? share.items(ex, i, 1) : sk && l.tail.n_skip >= 0 ? l.tail.n_skip : l.tail.n_items;
         o.launches = folded && i == 0 ? 0 : (n_main > 0) + (n_tail > 0);
         o.items = n_main + n_tail;
         o.flops_direct = layer_direct_flops(ex, l, frac);
@@ -1523,7 +1815,8 @@ int dodt_extractor_forward_timed(dodt_extractor* ex, const float* d_in, float* d
 double dodt_extractor_flops(const dodt_extractor* ex) {
     if (!ex) return 0.0;
     double f = 0.0;  // 2*M*N*K per layer; transposed convs counted on input pixels; skipped items not counted
-    for (const Layer& l : ex->layers) f += layer_direct_flops(ex, l, steady_frac(ex, l));
+    const WorkShare share(ex);
+    for (const Layer& l : ex->layers) f += layer_direct_flops(ex, l, share.of(ex, l));
     return f;
 }
 

@@ -94,6 +94,10 @@ struct ConvArgs {
     const float* first_w;
     const float* first_scale;
     const float* first_shift;
+    // per-frame skip tables (frame_tables.h; fp32 kernels): != NULL: the launch walks that many items of the table,
+    // a count an earlier launch of the stream wrote (0: every workgroup leaves at once); n_items is then the
+    // table's capacity, which the host sized the grid by
+    const int* n_items_dev;
 };
 
 constexpr int kCK = 8;          // input channels per K chunk = one CB8 plane
@@ -437,8 +441,11 @@ conv3x3_mfma_kernel(const ConvArgs a) {
     //            epilogue if chunk k ends an item; ONE barrier.
     // The chunk sequence runs across item boundaries, so neither the first loads of an
     // item nor its stores ever leave the matrix pipe idle.
+    int n_items = a.n_items;
+    if constexpr (!BF16 && PARTS == 1)
+        if (a.n_items_dev) n_items = *a.n_items_dev;   // per-frame table: this forward's count
     int comp_item = blockIdx.x, comp_ch = 0;   // chunk the MFMAs work on
-    if (comp_item >= a.n_items) return;        // uniform per workgroup
+    if (comp_item >= n_items) return;        // uniform per workgroup
     // diagnostic build switch (debug & 8): shader clock of workgroup 0, written to words
     // that nothing else reads (counter[32..35]); see MI355X_MICROARCH 'DVFS give-back'
     unsigned long long dbg_t0 = 0, dbg_r0 = 0;
@@ -454,7 +461,7 @@ conv3x3_mfma_kernel(const ConvArgs a) {
     // before the prologue's barrier and each later fetch is the item behind it, q1 ("deep").
     // Claiming no further ahead than necessary keeps the last round even.
     const bool deep = BF16 && nchunks < 4;
-    int q0 = a.n_items, q1 = a.n_items;
+    int q0 = n_items, q1 = n_items;
     if (deep && tid == 0) s_ctrl[0] = (int)gridDim.x + atomicAdd(a.counter, 1);
     setup_loads(decode(load_item));
     unsigned ok_regs = ok_issue;               // mask of the data sitting in pre[]
@@ -464,7 +471,7 @@ conv3x3_mfma_kernel(const ConvArgs a) {
         if (++load_ch == nchunks) {                                                           \
             load_ch = 0;                                                                      \
             load_item = (load_item == comp_item) ? q0 : q1;                                   \
-            if (load_item < a.n_items) setup_loads(decode(load_item));                        \
+            if (load_item < n_items) setup_loads(decode(load_item));                        \
         }                                                                                     \
     }
 #define DODT_FOR_SLOTS(BODY) \
@@ -487,7 +494,7 @@ conv3x3_mfma_kernel(const ConvArgs a) {
 #define DODT_PRO_LOAD1(J) DODT_LOAD_SLOT(J, ch_)
         DODT_FOR_SLOTS(DODT_PRO_LOAD1)   // harmless re-read of a valid address if no chunk is left
     }
-    bool more_loads = load_item < a.n_items;   // pre[] holds a real chunk
+    bool more_loads = load_item < n_items;   // pre[] holds a real chunk
     if (more_loads) DODT_ADVANCE_LOAD()
 
     f32x16 acc[NACC];
@@ -497,14 +504,14 @@ conv3x3_mfma_kernel(const ConvArgs a) {
         for (int r = 0; r < 16; ++r) acc[k][r] = 0.0f;
 
     int buf = 0;
-    while (comp_item < a.n_items) {
+    while (comp_item < n_items) {
         const float* bP = sP + buf * Cfg::kBufFloats;
         const float* bW = sW + buf * Cfg::kBufFloats;
         // staging plan of this step: write the registers (chunk k+1) to buffer buf^1, then
         // refill them with chunk k+2 = (load_item, load_ch) -- all unconditional
         const unsigned ok_store = ok_regs;
         const int ld_ch = load_ch;
-        const bool more = load_item < a.n_items;   // a real chunk is left to load
+        const bool more = load_item < n_items;   // a real chunk is left to load
         const bool issue = !(a.debug & 2);         // production: always (a surplus load
                                                    // re-reads a valid address, no branch)
         if (comp_ch == 0 && tid == 0)   // fetch the successor (deep: the item behind q0)
@@ -817,7 +824,7 @@ conv3x3_small_cin_kernel(const ConvArgs a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wm = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
-    const int n_items = a.n_items;
+    const int n_items = a.n_items_dev ? *a.n_items_dev : a.n_items;   // (per-frame table: this forward's count)
     constexpr int CG = CK / VEC;
     constexpr int ITEMS = PH * PW * CG;
     constexpr int NIT = (ITEMS + 255) / 256;

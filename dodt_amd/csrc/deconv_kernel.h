@@ -136,21 +136,24 @@ deconv3x3_dma_kernel(const ConvArgs a) {
 
     // the queue: one counter for the launch, or (a.xcd_counters, bf16 layers: conv_bf16_dma.h) one per group of
     // blocks that share an XCD, each walking its own eighth [q_lo, q_hi) of the table
+    int n_items = a.n_items;
+    if constexpr (!BF16)
+        if (a.n_items_dev) n_items = *a.n_items_dev;   // per-frame table: this forward's count
     const bool grouped = a.xcd_counters != nullptr;
     const int vx = grouped ? (int)(blockIdx.x & 7) : 0;
-    const int q_lo = grouped ? vx * (a.n_items / 8) + min(vx, a.n_items % 8) : 0;
-    const int q_hi = grouped ? q_lo + a.n_items / 8 + (vx < a.n_items % 8 ? 1 : 0) : a.n_items;
+    const int q_lo = grouped ? vx * (n_items / 8) + min(vx, n_items % 8) : 0;
+    const int q_hi = grouped ? q_lo + n_items / 8 + (vx < n_items % 8 ? 1 : 0) : n_items;
     const int q_first = q_lo + (grouped ? ((int)gridDim.x - vx + 7) / 8 : (int)gridDim.x);      // item of ticket 0
     int* const q_counter = grouped ? a.xcd_counters + 16 * vx : a.counter;
     int comp_item = q_lo + (grouped ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
     if (comp_item >= q_hi) return;
-    int q0 = a.n_items;
+    int q0 = n_items;
     auto advance = [&](int& it, int& ch, bool patch) {
-        if (it >= a.n_items) return;
+        if (it >= n_items) return;
         if (++ch == nchunks) {
             ch = 0;
-            it = (it == comp_item) ? q0 : a.n_items;
-            if (it < a.n_items) {
+            it = (it == comp_item) ? q0 : n_items;
+            if (it < n_items) {
                 if (patch) setup_patch(decode(it));
                 else setup_w(decode(it));
             } else if (patch) {
@@ -195,7 +198,7 @@ deconv3x3_dma_kernel(const ConvArgs a) {
         constexpr bool FIRST = decltype(first)::value;       // the item's first chunk
         if (comp_ch == 0 && tid == 0) {
             const int t = q_first + atomicAdd(q_counter, 1);
-            s_ctrl[0] = t < q_hi ? t : a.n_items;
+            s_ctrl[0] = t < q_hi ? t : n_items;
         }
         // inputs: patch rows 4w .. 4w + 4 (input rows 4w - 1 .. 4w + 3) x column shifts 0, 1
         f32x2_t xin[5][2];
@@ -245,7 +248,7 @@ deconv3x3_dma_kernel(const ConvArgs a) {
         advance(wit, wch, false);
     };
 
-    while (comp_item < a.n_items) {
+    while (comp_item < n_items) {
         f32x4 acc[4][4][CB];
         using T0 = std::integral_constant<int, 0>;
         using T1 = std::integral_constant<int, 1>;

@@ -177,21 +177,22 @@ wino3x3_f32_kernel(const ConvArgs a) {
 
     // the queue: one counter for the launch, or (a.xcd_counters: see conv_bf16_dma.h) one per group of blocks that
     // share an XCD, each walking its own eighth [q_lo, q_hi) of the table
+    const int n_items = a.n_items_dev ? *a.n_items_dev : a.n_items;   // (per-frame table: this forward's count)
     const bool grouped = a.xcd_counters != nullptr;
     const int vx = grouped ? (int)(blockIdx.x & 7) : 0;
-    const int q_lo = grouped ? vx * (a.n_items / 8) + min(vx, a.n_items % 8) : 0;
-    const int q_hi = grouped ? q_lo + a.n_items / 8 + (vx < a.n_items % 8 ? 1 : 0) : a.n_items;
+    const int q_lo = grouped ? vx * (n_items / 8) + min(vx, n_items % 8) : 0;
+    const int q_hi = grouped ? q_lo + n_items / 8 + (vx < n_items % 8 ? 1 : 0) : n_items;
     const int q_first = q_lo + (grouped ? ((int)gridDim.x - vx + 7) / 8 : (int)gridDim.x);      // item of ticket 0
     int* const q_counter = grouped ? a.xcd_counters + 16 * vx : a.counter;
     int comp_item = q_lo + (grouped ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
     if (comp_item >= q_hi) return;
-    int q0 = a.n_items;                          // successor of comp_item (fetched in its step 0)
+    int q0 = n_items;                          // successor of comp_item (fetched in its step 0)
     auto advance = [&](int& it, int& ch, bool patch) {
-        if (it >= a.n_items) return;
+        if (it >= n_items) return;
         if (++ch == nchunks) {
             ch = 0;
-            it = (it == comp_item) ? q0 : a.n_items;
-            if (it < a.n_items) {
+            it = (it == comp_item) ? q0 : n_items;
+            if (it < n_items) {
                 if (patch) setup_patch(decode(it));
                 else setup_w(decode(it));
             } else if (patch) {
@@ -281,7 +282,7 @@ wino3x3_f32_kernel(const ConvArgs a) {
         constexpr int PAR = decltype(par)::value;
         if (comp_ch == 0 && tid == 0) {
             const int t = q_first + atomicAdd(q_counter, 1);
-            s_ctrl[0] = t < q_hi ? t : a.n_items;
+            s_ctrl[0] = t < q_hi ? t : n_items;
         }
         const float* sW = sWB + PAR * Cfg::kWFloats + w_lane;
         f32x2_t d[4][4];
@@ -407,7 +408,7 @@ wino3x3_f32_kernel(const ConvArgs a) {
         advance(wit, wch, false);
     };
 
-    while (comp_item < a.n_items) {
+    while (comp_item < n_items) {
         f32x4 acc[TB][CB][16];
 #pragma unroll
         for (int tb = 0; tb < TB; ++tb)

@@ -80,6 +80,24 @@ def bev_support_mask(bev_params, pad_top=0, lib=None):
     return out
 
 
+def frame_tables_host(masks, layer, th, tw, items, prev=None, lib=None):
+    """The per-frame skip-table rule of the fp32 pyramid net on the host (dodt_frame_tables_host): masks (frames, rows,
+    cols) non-zero where each frame's padded input is, layer 0 .. 15 in launch order, items (n, 4) int32 {frame,
+    channel tile, y0, x0} in table order with th x tw tiles; prev (n,) uint8: the items the last forward reached.
+    Returns the (k, 4) items the forward runs, in table order."""
+    lib = lib or _lib.load()
+    masks = np.ascontiguousarray(masks, dtype=np.uint8)
+    items = np.ascontiguousarray(items, dtype=np.int32).reshape(-1, 4)
+    prev = None if prev is None else np.ascontiguousarray(prev, dtype=np.uint8)
+    run = np.zeros((max(len(items), 1), 4), np.int32)
+    n = C.c_int()
+    _lib.check(lib.dodt_frame_tables_host(masks.ctypes.data, masks.shape[0], masks.shape[1], masks.shape[2], int(layer),
+                                          int(th), int(tw), items.ctypes.data, len(items),
+                                          None if prev is None else prev.ctypes.data, run.ctypes.data, C.byref(n)),
+               'dodt_frame_tables_host')
+    return run[:n.value].copy()
+
+
 def bev_status(ctx):
     f = C.c_int()
     _lib.check(ctx.lib.dodt_bev_status(ctx.handle, C.byref(f)), 'dodt_bev_status')

@@ -61,7 +61,7 @@ class FramePairPipeline(object):
                  image_wh=_config.KITTI_IMAGE_WH, n_points_max=120000, rpn_nms_size=1024,
                  pairs_per_step=1, side_streams=None, head_params=None, conv_dtype='f32',
                  head_dtype='f32', reuse_streams_of=None, tail_sets=None, temporal=None, tracker=None,
-                 bev_input_skip=True):
+                 bev_input_skip=True, bev_frame_tables=True):
         """temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
         module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it.
         tracker: None, or dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3, classes=('Car',),
@@ -69,7 +69,9 @@ class FramePairPipeline(object):
         are one sequence until end_sequence() (see _tracker_step, tracks_so_far()); None enqueues and allocates nothing
         for it.
         bev_input_skip: the fp32 BEV net skips the tiles that no BEV cell inside the camera's frustum reaches (their
-        values depend on the weights alone, dodt_extractor_set_input_support); False: full tables."""
+        values depend on the weights alone, dodt_extractor_set_input_support); False: full tables.
+        bev_frame_tables: with bev_input_skip, every step also filters those tables on the device by the cells that are
+        non-zero in its own BEV maps (dodt_extractor_set_frame_tables); False: the static tables alone."""
         self.ctx = ctx
         self.cfg = cfg
         self.p2 = np.asarray(p2, dtype=np.float64)
@@ -160,7 +162,7 @@ class FramePairPipeline(object):
         if bev_input_skip and conv_dtype == 'f32' and hasattr(self.bev_net, 'set_input_support') \
                 and self.bp.point_format == _lib.PTS_VELO_XYZI:
             self.bev_skipped_items = self.bev_net.set_input_support(
-                ops.bev_support_mask(self.bp, self.bev_net.PAD_TOP, ctx.lib))
+                ops.bev_support_mask(self.bp, self.bev_net.PAD_TOP, ctx.lib), frame_tables=bev_frame_tables)
         self.img_net = img_cls(ctx=self.img_ctx, shared_gpu=True, conv_dtype=conv_dtype)
         self.img_net.load_params(img_params)
         self.img_net._ensure(self.nf, self.img_h, self.img_w, 4)

@@ -279,6 +279,29 @@ int dodt_extractor_set_input(dodt_extractor* ex, const float* d_x0);
  * sizes).  *skipped_items (may be NULL): work items dropped per forward in steady state. */
 int dodt_extractor_set_input_support(dodt_extractor* ex, const uint8_t* mask, int rows, int cols,
                                      long long* skipped_items);
+/* Per-frame tables for an extractor with an input support set (on = 0: the static skip tables again).  Every forward
+ * then builds its tables on the device, ahead of the layers on the extractor's stream and without a host round trip:
+ * the non-zero cells of the input map (any channel) as a bit mask per frame, propagated by the same geometry at cell
+ * resolution, keep the items of each skip table this input reaches, in the table's order; the kernels read the item
+ * count from device memory.  A launch runs these items and the ones the last forward into the same buffer ran, so
+ * every output that was input-dependent then goes back to the value a full forward writes; after every forward each
+ * layer buffer holds what a forward on full tables would have written.  The forwards that run full tables (see
+ * above) record their input's items the same way; pyramid_fusion1 keeps the items per remembered output pair.
+ * *enabled (may be NULL): 1 if the tables are on; 0 if the extractor has no skip tables or runs F(4x4,3x3) layers
+ * (DODT_CONV_WINO=4: those reach block-wise), which keeps the static tables.  dodt_extractor_set_input_support
+ * turns the per-frame tables off again.  While they are on, dodt_extractor_flops / _mfma_flops / _bytes wait for
+ * the stream and count the items of the last finished forward. */
+int dodt_extractor_set_frame_tables(dodt_extractor* ex, int on, int* enabled);
+/* The work items each layer of the last forward ran from per-frame tables (waits for the stream): items[layer] in
+ * launch order, n >= dodt_extractor_layer_count(); -1 for a layer that ran a full or static table. */
+int dodt_extractor_frame_items(dodt_extractor* ex, int* items, int n);
+/* Host only: the per-frame rule of dodt_extractor_set_frame_tables on host masks, for one layer (0 .. 15 in launch
+ * order) of the pyramid net.  masks: frames x rows x cols bytes, non-zero where the frame's padded input is; items:
+ * n_items x {frame, channel tile, y0, x0} in table order, each writing th x tw outputs of the layer's GEMM grid
+ * (transposed convs: 2 th x 2 tw outputs); prev (may be NULL): n_items bytes, the items the last forward reached.
+ * run (room for n_items x 4 ints) receives the items of this input or of prev, in table order, *n_run their count. */
+int dodt_frame_tables_host(const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
+                           const int* items, int n_items, const uint8_t* prev, int* run, int* n_run);
 /* Size of the feature map forward() returns: (in_h, in_w, 32) for the pyramid,
  * (in_h / 8 * 4, in_w / 8 * 4, 256) for DODT_EXTRACTOR_VGG. */
 int dodt_extractor_output_shape(const dodt_extractor* ex, int* h, int* w, int* c);
