@@ -817,8 +817,10 @@ Support wino_blocks(const Support& a, int m) {
 // ---------------------------------------------------------------------------
 // per-frame tables (frame_tables.h): three launches at the head of a forward
 // ---------------------------------------------------------------------------
-// the non-zero cells of the frames' input maps (NHWC, any channel; -0.0 counts as non-zero: it is not the +0.0 the
-// skipped outputs were computed from) as bit masks: half a wave per word
+// the non-zero cells of the frames' input maps (NHWC, any channel) as bit masks: half a wave per word.  A cell that
+// holds only -0.0 counts as empty (the sign bit is masked off): every conv form starts its accumulators at +0.0 and
+// x w with x = -0.0 adds +-0.0, so its outputs are bit for bit those of +0.0, the value the skipped outputs were
+// computed from (tests/test_gpu_bev_skip_adversarial.py).  A denormal counts as non-zero.
 __global__ void __launch_bounds__(256)
 frame_support_kernel(const float* __restrict__ x, long long frame_stride, int H, int W, int C, uint32_t* __restrict__ bits) {
     const int p = dodt::ft::pitch(W), words = H * p;
