@@ -136,6 +136,14 @@ def test_bev_is_deterministic(ctx):
                     synth.IMAGE_WH)
     assert np.array_equal(a[:, :, 5], c[:, :, 5])
     assert np.array_equal(a != 0, c != 0)
+    # the heights follow "lowest y-bin, then lowest original index": all six channels of the
+    # permuted run equal the oracle on the permuted rows (b above repeats a: the repeatability check)
+    cloud = opoints.lidar_in_camera_view(xyzi[perm], synth.R0_RECT, synth.TR_VELO_TO_CAM,
+                                         synth.P2, synth.IMAGE_WH)
+    want = opoints.bev_input(cloud, C['ground_plane'], C['area_extents'], C['voxel_size'],
+                             C['height_lo'], C['height_hi'], C['num_slices'])
+    _compare_bev(c, want)
+    assert np.count_nonzero(a[:, :, :5] != c[:, :, :5]) > 0         # the order does matter here
 
 
 def test_bev_empty_cloud(ctx):
