@@ -113,7 +113,11 @@ SIGNATURES = {
     'dodt_extractor_set_input_support': (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_longlong)]),
     'dodt_extractor_set_frame_tables': (_i, [_vp, _i, C.POINTER(_i)]),
     'dodt_extractor_frame_items': (_i, [_vp, C.POINTER(_i), _i]),
+    'dodt_extractor_frame_split': (_i, [_vp, C.POINTER(_i), C.POINTER(_i), _i]),
+    'dodt_extractor_store_bytes': (C.c_longlong, [_vp]),
     'dodt_frame_tables_host': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, C.POINTER(_i)]),
+    'dodt_frame_restore_host': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'dodt_frame_lists_host': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, C.POINTER(_i), _vp, C.POINTER(_i)]),
     'dodt_extractor_read_activation': (_i, [_vp, C.c_char_p, _vp,
                                             C.POINTER(_i), C.POINTER(_i),
                                             C.POINTER(_i)]),

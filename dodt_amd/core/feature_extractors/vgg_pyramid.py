@@ -126,12 +126,25 @@ class _VggPyr(object):
         return n.value
 
     def frame_items(self):
-        """Work items each layer of the last forward ran from per-frame tables, in launch order; -1 for a layer that
-        ran a full or static table (dodt_extractor_frame_items; waits for the stream)."""
+        """Work items each layer of the last forward touched from per-frame tables (computed or restored), in launch
+        order; -1 for a layer that ran a full or static table (dodt_extractor_frame_items; waits for the stream)."""
         n = self._ctx.lib.dodt_extractor_layer_count(self._handle)
         items = (C.c_int * n)()
         _lib.check(self._ctx.lib.dodt_extractor_frame_items(self._handle, items, n), 'dodt_extractor_frame_items')
         return list(items)
+
+    def frame_split(self):
+        """(computed, restored): per layer of the last forward the items its kernels ran and the items copied back from
+        the constants store; -1 / -1 for a layer that ran a full or static table (dodt_extractor_frame_split)."""
+        n = self._ctx.lib.dodt_extractor_layer_count(self._handle)
+        computed, restored = (C.c_int * n)(), (C.c_int * n)()
+        _lib.check(self._ctx.lib.dodt_extractor_frame_split(self._handle, computed, restored, n),
+                   'dodt_extractor_frame_split')
+        return list(computed), list(restored)
+
+    def store_bytes(self):
+        """Device memory the constants store of the per-frame tables holds (0 until a forward has restored)."""
+        return self._ctx.lib.dodt_extractor_store_bytes(self._handle)
 
     def set_input(self, d_x0):
         """Forwards without an input argument read d_x0 (extractor input layout) from now on; None: the extractor's

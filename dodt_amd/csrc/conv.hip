@@ -441,6 +441,16 @@ struct dodt_extractor {
     std::vector<void*> frame_allocs;
     uint8_t* out_prev[8][2] = {};
     std::vector<int> out_slot;
+    // constants store (per-frame tables): one frame of every layer buffer and of the (feature, bottleneck) pair as a
+    // forward on zeros writes them -- what an output holds that no input reaches.  Taken by the first forward that
+    // restores from it (take_store), again after new weights; freed with the per-frame tables.
+    float* store[NBUF] = {};
+    float* store_feat = nullptr;
+    float* store_bneck = nullptr;
+    dodt::ft::RestorePlan* d_restore_plan = nullptr;
+    bool store_valid = false;
+    bool restoring = false;   // the last forward ran the restore launch
+    size_t store_bytes = 0;
 };
 
 namespace {
@@ -495,6 +505,8 @@ int run_launch(dodt_extractor* ex, const Layer& l, const Launch& ln, int which,
     const bool skip = li < ex->skipping.size() && ex->skipping[li] && ln.n_skip >= 0;
     a.items = skip ? ln.d_skip : ln.d_items;
     a.n_items = skip ? ln.n_skip : ln.n_items;
+    // the first-layer kernel derives a full table's coordinates from the item index (no table load ahead of its patch)
+    if (v.small_cin && !skip && a.n_items == a.tiles_x * a.tiles_y * ex->batch) a.items = nullptr;
     if (a.n_items == 0) return DODT_OK;   // every item of the launch skipped
     // per-frame tables: the builder's launches ahead in the stream wrote this forward's items and their count
     const bool per_frame = skip && ex->skipping[li] == 2 && ln.d_run;
@@ -866,7 +878,54 @@ frame_compact_kernel(const dodt::ft::Plan* __restrict__ pl, uint8_t* last_prev_m
     dodt::ft::compact(t, prev, scan, (int)threadIdx.x, (int)blockDim.x, [] { __syncthreads(); });
 }
 
+}  // namespace
+
+using dodt::ft::RestoreTable;
+using dodt::ft::RestorePlan;
+
+namespace {
+
+// Every table's restore list in one launch (ahead of conv1_1 on the extractor's stream): the outputs of an item that
+// the last forward into the same buffer reached and this one does not go back to the store's values.  Workgroups
+// stride over the lists end to end; one that finds nothing leaves at once.  last_on: pyramid_fusion1's list counts
+// (the output pair is one the layer remembers).
+__global__ void __launch_bounds__(256)
+frame_restore_kernel(const RestorePlan* __restrict__ pl, float* __restrict__ feat, float* __restrict__ bneck, int last_on) {
+    __shared__ int start[dodt::ft::kTables + 1];
+    if (threadIdx.x == 0) {
+        int sum = 0;
+        for (int k = 0; k < dodt::ft::kTables; ++k) {
+            start[k] = sum;
+            const bool on = pl->t[k].list && (k / 2 != dodt::ft::kLayers - 1 || last_on);
+            sum += on ? *pl->t[k].count : 0;
+        }
+        start[dodt::ft::kTables] = sum;
+    }
+    __syncthreads();
+    const int total = start[dodt::ft::kTables];
+    int k = 0;
+    for (int i = blockIdx.x; i < total; i += gridDim.x) {
+        while (i >= start[k + 1]) ++k;
+        dodt::ft::restore_item(*pl, pl->t[k], pl->t[k].list[i - start[k]], feat, bneck, (int)threadIdx.x, (int)blockDim.x);
+    }
+}
+
+void free_store(dodt_extractor* ex) {
+    for (int i = 0; i < NBUF; ++i) {
+        if (ex->store[i]) (void)hipFree(ex->store[i]);
+        ex->store[i] = nullptr;
+    }
+    if (ex->store_feat) (void)hipFree(ex->store_feat);
+    if (ex->store_bneck) (void)hipFree(ex->store_bneck);
+    if (ex->d_restore_plan) (void)hipFree(ex->d_restore_plan);
+    ex->store_feat = ex->store_bneck = nullptr;
+    ex->d_restore_plan = nullptr;
+    ex->store_valid = false;
+    ex->store_bytes = 0;
+}
+
 void free_frame_tables(dodt_extractor* ex) {
+    free_store(ex);
     for (void* p : ex->frame_allocs) (void)hipFree(p);
     ex->frame_allocs.clear();
     for (Layer& l : ex->layers)
@@ -900,16 +959,28 @@ int build_frame_tables(dodt_extractor* ex, int slot) {
 }
 
 // the per-frame counts of the last forward (waits for the stream); false: per-frame tables are off
-bool read_frame_counts(const dodt_extractor* ex, int (&counts)[dodt::ft::kTables]) {
+bool read_frame_counts(const dodt_extractor* ex, int (&counts)[2 * dodt::ft::kTables]) {
     if (!ex->frame_on) return false;
     if (hipStreamSynchronize(ex->ctx->stream) != hipSuccess) return false;
     return hipMemcpy(counts, ex->d_frame_counts, sizeof(counts), hipMemcpyDeviceToHost) == hipSuccess;
 }
 
+// the buffer a layer's epilogue pools into (conv1_2, conv2_2, conv3_3 where the tiling allows), or -1
+int fused_pool_buffer(const Layer& l) {
+    static const bool no_fuse = getenv("DODT_CONV_NO_POOL_FUSE") != nullptr;
+    if (no_fuse || !layer_can_pool(l)) return -1;
+    return l.name == "conv1_2" ? P1 : l.name == "conv2_2" ? P2 : l.name == "conv3_3" ? P3 : -1;
+}
+
+// pyramid_fusion1 computes the 1x1 bottleneck in its epilogue (32-channel tiles)
+bool bneck_fused(const Layer& last) {
+    return variants()[last.main.variant].BN == 32 && (last.tail.n_items == 0 || variants()[last.tail.variant].BN == 32);
+}
+
 // The share of a layer's work that is counted: the steady state's (steady_frac), or with per-frame tables what the
 // last finished forward ran of a layer that took them (waits for the stream).
 struct WorkShare {
-    int counts[dodt::ft::kTables];
+    int counts[2 * dodt::ft::kTables];   // computed items per table, then restored items per table
     bool have;
     explicit WorkShare(const dodt_extractor* ex) : have(read_frame_counts(ex, counts)) {}
     bool per_frame(const dodt_extractor* ex, size_t li) const {
@@ -918,6 +989,28 @@ struct WorkShare {
     int items(const dodt_extractor* ex, size_t li, int j) const {
         const Layer& l = ex->layers[li];
         return (j ? l.tail : l.main).d_count ? counts[2 * li + j] : 0;
+    }
+    // the items of the launch whose outputs the forward copied back from the store (none where a full table ran)
+    int restored(const dodt_extractor* ex, size_t li, int j) const {
+        const Layer& l = ex->layers[li];
+        return per_frame(ex, li) && ex->restoring && (j ? l.tail : l.main).d_count ? counts[dodt::ft::kTables + 2 * li + j] : 0;
+    }
+    // HBM bytes of those copies, read from the store and written: the item's outputs, their pooled copy where the
+    // pool is fused, the bottleneck cells of a pyramid_fusion1 tile where the bottleneck is
+    double restore_bytes(const dodt_extractor* ex, const Layer& l) const {
+        const size_t li = &l - ex->layers.data();
+        const bool pooled = fused_pool_buffer(l) >= 0;
+        const bool bneck = &l == &ex->layers.back() && ex->bneck_loaded && bneck_fused(l);
+        double b = 0.0;
+        int j = 0;
+        for (const Launch* ln : {&l.main, &l.tail}) {
+            const int jj = j++;
+            if (ln->h_items.empty()) continue;
+            const KernelVariant& v = variants()[ln->variant];
+            const double px = (l.deconv ? 4.0 : 1.0) * v.TH * v.TW;
+            b += 2.0 * 4.0 * (px * v.BN * (pooled ? 1.25 : 1.0) + (bneck ? px : 0.0)) * restored(ex, li, jj);
+        }
+        return b;
     }
     double of(const dodt_extractor* ex, const Layer& l) const {
         const size_t li = &l - ex->layers.data();
@@ -948,6 +1041,9 @@ void free_skip_tables(dodt_extractor* ex) {
     }
     ex->skip_on = false;
 }
+
+int run_layers(dodt_extractor* ex, float* d_feat_out, float* d_bottleneck_out);
+int take_store(dodt_extractor* ex);
 
 }  // namespace
 
@@ -1145,6 +1241,7 @@ int dodt_extractor_set_layer(dodt_extractor* ex, const char* name, const float* 
     // new weights: the input-independent outputs the skip tables leave alone change (the next forward primes)
     ex->primed = false;
     ex->primed_out.clear();
+    ex->store_valid = false;
     if (std::strcmp(name, "bottleneck") == 0) {
         const int fc = ex->out_c;   // 32 (pyramid) or 256 (plain VGG: rpn_model.py:251-267)
         DODT_REQUIRE(kh == 1 && kw == 1 && c_a == fc && c_b == 1,
@@ -1404,11 +1501,13 @@ int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_
     if (ex->kind == DODT_EXTRACTOR_VGG_PYR)
         ex->skipping[find_layer(ex, "pyramid_fusion1")] = last_skip ? (ex->frame_on ? 2 : 1) : 0;
     int rc;
+    ex->restoring = false;
     if (ex->frame_on) {
-        // Per-frame tables: every launch runs the items this input reaches and the ones the last forward into the
-        // same buffer reached (those go back to their input-independent values), and the builder keeps this input's
-        // set for the next forward.  A forward on full tables (priming; pyramid_fusion1 into a pair it has not
-        // written) records its set the same way.  A new pair takes the set of the pair it evicts, or a free one.
+        // Per-frame tables: every launch runs the items this input reaches; the ones the last forward into the same
+        // buffer reached and this one does not go back to their input-independent values (frame_restore_kernel), and
+        // the builder keeps this input's set for the next forward.  A forward on full tables (priming; pyramid_fusion1
+        // into a pair it has not written) records its set the same way.  A new pair takes the set of the pair it
+        // evicts, or a free one.
         if (ex->primed_out.empty()) ex->out_slot.clear();
         int slot = 0;
         if (known_pair) {
@@ -1420,12 +1519,43 @@ int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_
         } else {
             slot = ex->out_slot[0];
         }
+        // the stale items go back to their values by copy, not by arithmetic: one launch for all tables, behind the
+        // builder and ahead of conv1_1 (a forward that primes has nothing to restore)
+        ex->restoring = skip;
+        if (skip && !ex->store_valid) {
+            if ((rc = take_store(ex))) return rc;
+            DODT_HIP_CHECK(hipMemsetAsync(ex->d_counters, 0, 4096 * sizeof(int), s));
+        }
         if ((rc = build_frame_tables(ex, slot))) return rc;
+        if (skip) {
+            hipLaunchKernelGGL(frame_restore_kernel, dim3((unsigned)(4 * ex->ctx->num_cus)), dim3(256), 0, s,
+                               ex->d_restore_plan, d_feat_out, d_bottleneck_out, last_skip ? 1 : 0);
+            DODT_LAUNCH_CHECK();
+        }
         if (!known_pair) {
             if (ex->primed_out.size() >= 8) ex->out_slot.erase(ex->out_slot.begin());
             ex->out_slot.push_back(slot);
         }
     }
+    if ((rc = run_layers(ex, d_feat_out, d_bottleneck_out))) return rc;
+    if (ex->skip_on) {
+        ex->primed = true;
+        if (!known_pair) {
+            ex->primed_out.emplace_back(d_feat_out, d_bottleneck_out);
+            if (ex->primed_out.size() > 8) ex->primed_out.erase(ex->primed_out.begin());   // (re-primed when back)
+        }
+    }
+    return DODT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the layers of one forward on the extractor's stream, with the tables ex->skipping selects
+int run_layers(dodt_extractor* ex, float* d_feat_out, float* d_bottleneck_out) {
+    hipStream_t s = ex->ctx->stream;
+    int rc;
     auto L = [&](const char* n) -> const Layer& { return ex->layers[find_layer(ex, n)]; };
 #define RUN(name)                                           \
     if ((rc = run_layer(ex, L(name), nullptr, 0, 0))) return rc;
@@ -1484,15 +1614,120 @@ int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_
                            ex->bneck_shift, d_bottleneck_out);
         DODT_LAUNCH_CHECK();
     }
-    if (ex->skip_on) {
-        ex->primed = true;
-        if (!known_pair) {
-            ex->primed_out.emplace_back(d_feat_out, d_bottleneck_out);
-            if (ex->primed_out.size() > 8) ex->primed_out.erase(ex->primed_out.begin());   // (re-primed when back)
-        }
-    }
     return DODT_OK;
 }
+
+// The constants store: frame 0 of a forward on a zero input, through the same kernels and the full tables, written into
+// the store's maps in place of the layer buffers.  Neither the caller's input nor any live buffer is touched.  Waits
+// for the stream (once per weight load).
+int take_store(dodt_extractor* ex) {
+    hipStream_t s = ex->ctx->stream;
+    const bool fresh = ex->d_restore_plan == nullptr;
+    if (fresh) {
+        size_t total = 0;
+        hipError_t ea = hipSuccess;
+        for (int i = 0; i < NBUF && ea == hipSuccess; ++i) {
+            if (i == X0 || i == F1 || !ex->buf[i].ptr) continue;
+            const size_t bytes = ex->buf[i].frame_floats() * sizeof(float);
+            ea = hipMalloc(&ex->store[i], bytes);
+            total += bytes;
+        }
+        const size_t px = (size_t)ex->out_h * ex->out_w;
+        if (ea == hipSuccess) ea = hipMalloc(&ex->store_feat, px * ex->out_c * sizeof(float));
+        if (ea == hipSuccess) ea = hipMalloc(&ex->store_bneck, px * sizeof(float));
+        if (ea == hipSuccess) ea = hipMalloc(&ex->d_restore_plan, sizeof(RestorePlan));
+        if (ea != hipSuccess) free_store(ex);     // (nothing half-allocated stays behind)
+        DODT_HIP_CHECK(ea);
+        ex->store_bytes = total + px * (ex->out_c + 1) * sizeof(float);
+    }
+    // a zero input frame, and every launch's items of frame 0
+    float* zeros = nullptr;
+    const size_t in_bytes = ex->buf[X0].frame_floats() * sizeof(float);
+    DODT_HIP_CHECK(hipMalloc(&zeros, in_bytes));
+    DODT_HIP_CHECK(hipMemsetAsync(zeros, 0, in_bytes, s));
+    struct Saved { Launch* ln; int4* d_items; int n_items; };
+    std::vector<Saved> saved;
+    std::vector<void*> temps = {zeros};
+    hipError_t e = hipSuccess;
+    for (Layer& l : ex->layers)
+        for (Launch* ln : {&l.main, &l.tail}) {
+            if (ln->h_items.empty()) continue;
+            std::vector<int4> first;
+            for (const int4& it : ln->h_items)
+                if (it.x == 0) first.push_back(it);
+            int4* d = nullptr;
+            if (!first.empty() && e == hipSuccess) e = hipMalloc(&d, first.size() * sizeof(int4));
+            if (d) temps.push_back(d);
+            if (d && e == hipSuccess) e = hipMemcpy(d, first.data(), first.size() * sizeof(int4), hipMemcpyHostToDevice);
+            saved.push_back({ln, ln->d_items, ln->n_items});
+            ln->d_items = d;
+            ln->n_items = (int)first.size();
+        }
+    float* live[NBUF];
+    for (int i = 0; i < NBUF; ++i) {
+        live[i] = ex->buf[i].ptr;
+        if (ex->store[i]) ex->buf[i].ptr = ex->store[i];
+    }
+    ex->buf[X0].ptr = zeros;
+    const std::vector<char> skipping = ex->skipping;
+    const int batch = ex->batch;
+    const bool timed = ex->timed;
+    ex->skipping.assign(ex->layers.size(), 0);
+    ex->batch = 1;
+    ex->timed = false;
+    int rc = DODT_OK;
+    if (e == hipSuccess) e = hipMemsetAsync(ex->d_counters, 0, 4096 * sizeof(int), s);
+    if (e == hipSuccess) rc = run_layers(ex, ex->store_feat, ex->bneck_loaded ? ex->store_bneck : nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    ex->skipping = skipping;
+    ex->batch = batch;
+    ex->timed = timed;
+    for (int i = 0; i < NBUF; ++i) ex->buf[i].ptr = live[i];
+    for (const Saved& sv : saved) {
+        sv.ln->d_items = sv.d_items;
+        sv.ln->n_items = sv.n_items;
+    }
+    for (void* p : temps) (void)hipFree(p);
+    if (rc) return rc;
+    DODT_HIP_CHECK(e);
+    // where each table's items live (the layer buffers never move; the caller's pair comes with the launch)
+    RestorePlan pl;
+    for (size_t li = 0; li < ex->layers.size(); ++li) {
+        const Layer& l = ex->layers[li];
+        const int pool_dst = fused_pool_buffer(l);
+        int j = 0;
+        for (const Launch* ln : {&l.main, &l.tail}) {
+            const dodt::ft::Table& ft = ex->frame_plan.t[2 * li + j];
+            RestoreTable& t = pl.t[2 * li + j++];
+            if (!ft.items) continue;
+            const Buffer& dst = ex->buf[l.dst];
+            t.list = ft.restore;
+            t.count = ft.rcount;
+            t.dst = dst.ptr;                 // (nullptr: pyramid_fusion1)
+            t.src = ex->store[l.dst];
+            t.frame_stride = (long long)dst.frame_floats();
+            t.H = dst.H; t.W = dst.W;
+            t.ch0 = l.dst_coff;
+            t.bn = variants()[ln->variant].BN;
+            t.f = ft.f; t.th = ft.th; t.tw = ft.tw;
+            if (pool_dst >= 0) {
+                t.pool_dst = ex->buf[pool_dst].ptr;
+                t.pool_src = ex->store[pool_dst];
+                t.pool_frame_stride = (long long)ex->buf[pool_dst].frame_floats();
+            }
+        }
+    }
+    pl.feat = ex->store_feat;
+    pl.bneck = ex->bneck_loaded && bneck_fused(ex->layers.back()) ? ex->store_bneck : nullptr;   // (not fused: a kernel of its own rewrites the map)
+    pl.pad_top = ex->pad_top; pl.out_h = ex->out_h; pl.out_c = ex->out_c;
+    DODT_HIP_CHECK(hipMemcpy(ex->d_restore_plan, &pl, sizeof(pl), hipMemcpyHostToDevice));
+    ex->store_valid = true;
+    return DODT_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int dodt_extractor_forward_padded(dodt_extractor* ex, const float* d_x0, float* d_feat_out,
                                   float* d_bottleneck_out) {
@@ -1600,7 +1835,7 @@ int dodt_extractor_set_frame_tables(dodt_extractor* ex, int on, int* enabled) {
     pl.H = ex->H; pl.W = ex->W; pl.frames = ex->batch;
     DODT_HIP_CHECK(alloc((size_t)ex->batch * ft::stash_words(ex->H, ex->W) * 4, (void**)&pl.stash));
     DODT_HIP_CHECK(alloc((size_t)ex->batch * words * 4, (void**)&ex->d_frame_bits));
-    DODT_HIP_CHECK(alloc(ft::kTables * sizeof(int), (void**)&ex->d_frame_counts));
+    DODT_HIP_CHECK(alloc(2 * ft::kTables * sizeof(int), (void**)&ex->d_frame_counts));
     for (size_t li = 0; li < ex->layers.size(); ++li) {
         Layer& l = ex->layers[li];
         int j = 0;
@@ -1622,6 +1857,8 @@ int dodt_extractor_set_frame_tables(dodt_extractor* ex, int on, int* enabled) {
             }
             DODT_HIP_CHECK(alloc(t.n * sizeof(int4), (void**)&t.run));
             t.count = ex->d_frame_counts + 2 * li + jj;
+            DODT_HIP_CHECK(alloc(t.n * sizeof(int4), (void**)&t.restore));
+            t.rcount = ex->d_frame_counts + ft::kTables + 2 * li + jj;
             ln->d_run = t.run;
             ln->d_count = t.count;
         }
@@ -1639,31 +1876,46 @@ int dodt_extractor_set_frame_tables(dodt_extractor* ex, int on, int* enabled) {
 int dodt_extractor_frame_items(dodt_extractor* ex, int* items, int n) {
     DODT_REQUIRE(ex && items && n >= (int)ex->layers.size(),
                  "dodt_extractor_frame_items: items must hold dodt_extractor_layer_count() entries");
-    int counts[dodt::ft::kTables];
-    const bool have = read_frame_counts(ex, counts);
+    const WorkShare share(ex);
+    for (size_t i = 0; i < ex->layers.size(); ++i)
+        items[i] = share.per_frame(ex, i) ? share.items(ex, i, 0) + share.items(ex, i, 1) + share.restored(ex, i, 0) +
+                                                share.restored(ex, i, 1)
+                                          : -1;
+    return DODT_OK;
+}
+
+int dodt_extractor_frame_split(dodt_extractor* ex, int* computed, int* restored, int n) {
+    DODT_REQUIRE(ex && computed && restored && n >= (int)ex->layers.size(),
+                 "dodt_extractor_frame_split: computed and restored must hold dodt_extractor_layer_count() entries");
+    const WorkShare share(ex);
     for (size_t i = 0; i < ex->layers.size(); ++i) {
-        const Layer& l = ex->layers[i];
-        const bool pf = have && i < ex->skipping.size() && ex->skipping[i] == 2;
-        items[i] = pf ? (l.main.d_count ? counts[2 * i] : 0) + (l.tail.d_count ? counts[2 * i + 1] : 0) : -1;
+        const bool pf = share.per_frame(ex, i);
+        computed[i] = pf ? share.items(ex, i, 0) + share.items(ex, i, 1) : -1;
+        restored[i] = pf ? share.restored(ex, i, 0) + share.restored(ex, i, 1) : -1;
     }
     return DODT_OK;
 }
 
-int dodt_frame_tables_host(const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
-                           const int* items, int n_items, const uint8_t* prev, int* run, int* n_run) {
+long long dodt_extractor_store_bytes(const dodt_extractor* ex) { return ex ? (long long)ex->store_bytes : 0; }
+
+}  // extern "C"
+
+namespace {
+
+// the host rule for one layer: restore != nullptr: the two lists; nullptr: run receives their union, in table order
+int frame_lists_host(const char* who, const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
+                     const int* items, int n_items, const uint8_t* prev, int* run, int* n_run, int* restore, int* n_restore) {
     namespace ft = dodt::ft;
-    DODT_REQUIRE(masks && items && run && n_run && frames >= 1 && n_items >= 0,
-                 "dodt_frame_tables_host: NULL argument");
-    DODT_REQUIRE(rows > 0 && cols > 0 && rows % 8 == 0 && cols % 8 == 0,
-                 "dodt_frame_tables_host: masks of %dx%d, not divisible by 8", rows, cols);
-    DODT_REQUIRE(layer >= 0 && layer < ft::kLayers && th > 0 && tw > 0, "dodt_frame_tables_host: bad layer or tile");
+    DODT_REQUIRE(masks && items && run && n_run && frames >= 1 && n_items >= 0, "%s: NULL argument", who);
+    DODT_REQUIRE(rows > 0 && cols > 0 && rows % 8 == 0 && cols % 8 == 0, "%s: masks of %dx%d, not divisible by 8", who, rows,
+                 cols);
+    DODT_REQUIRE(layer >= 0 && layer < ft::kLayers && th > 0 && tw > 0, "%s: bad layer or tile", who);
     for (int i = 0; i < n_items; ++i)
-        DODT_REQUIRE(items[4 * i] >= 0 && items[4 * i] < frames, "dodt_frame_tables_host: item %d names frame %d", i,
-                     items[4 * i]);
+        DODT_REQUIRE(items[4 * i] >= 0 && items[4 * i] < frames, "%s: item %d names frame %d", who, i, items[4 * i]);
     const bool deconv = layer == 10 || layer == 12 || layer == 14;
     std::vector<uint8_t> now((size_t)n_items, 0), pv((size_t)n_items, 0);
     if (prev) pv.assign(prev, prev + n_items);
-    int count = 0;
+    int count = 0, rcount = 0;
     ft::Plan pl;
     pl.H = rows; pl.W = cols; pl.frames = frames;
     std::vector<uint32_t> stash((size_t)ft::stash_words(rows, cols) * frames);
@@ -1678,6 +1930,8 @@ int dodt_frame_tables_host(const uint8_t* masks, int frames, int rows, int cols,
     t.prev = pv.data();
     t.run = reinterpret_cast<int4*>(run);
     t.count = &count;
+    t.restore = reinterpret_cast<int4*>(restore);
+    t.rcount = &rcount;
     const int words = ft::level_words(rows, cols, 0), p = ft::pitch(cols);
     std::vector<uint32_t> a(words), b(words);
     for (int f = 0; f < frames; ++f) {
@@ -1687,10 +1941,59 @@ int dodt_frame_tables_host(const uint8_t* masks, int frames, int rows, int cols,
                 if (masks[((size_t)f * rows + y) * cols + x]) a[y * p + (x >> 5)] |= 1u << (x & 31);
         ft::walk(pl, f, a.data(), b.data(), 0, 1, [] {});
     }
+    if (!restore) {     // what a forward touches, computed or restored
+        for (int i = 0; i < n_items; ++i)
+            if (now[i] | pv[i]) memcpy(run + 4 * count++, items + 4 * i, 16);
+        *n_run = count;
+        return DODT_OK;
+    }
     int scan[2];
     if (n_items > 0) ft::compact(t, pv.data(), scan, 0, 1, [] {});
     *n_run = count;
+    *n_restore = rcount;
     return DODT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dodt_frame_tables_host(const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
+                           const int* items, int n_items, const uint8_t* prev, int* run, int* n_run) {
+    return frame_lists_host("dodt_frame_tables_host", masks, frames, rows, cols, layer, th, tw, items, n_items, prev, run,
+                            n_run, nullptr, nullptr);
+}
+
+int dodt_frame_restore_host(const int* item, int f, int th, int tw, int bn, int ch0, int rows, int cols, int channels,
+                            int pad_top, float* dst, const float* src, float* dst2, const float* src2) {
+    DODT_REQUIRE(item && dst && src && (!dst2 == !src2), "dodt_frame_restore_host: NULL argument");
+    DODT_REQUIRE(f >= 1 && th > 0 && tw > 0 && tw % 4 == 0 && bn > 0 && bn % 8 == 0 && ch0 % 8 == 0 && rows > 0 && cols > 0 &&
+                     cols % 4 == 0 && ch0 + (item[1] + 1) * bn <= channels && item[0] >= 0 && item[2] >= 0 && item[3] >= 0,
+                 "dodt_frame_restore_host: bad geometry");
+    namespace ft = dodt::ft;
+    ft::RestorePlan pl;
+    ft::RestoreTable& t = pl.t[0];
+    t.H = rows; t.W = cols; t.ch0 = ch0; t.bn = bn; t.f = f; t.th = f * th; t.tw = f * tw;
+    if (pad_top < 0) {
+        t.dst = dst; t.src = src;
+        t.frame_stride = (long long)rows * cols * channels;
+        t.pool_dst = dst2; t.pool_src = src2;
+        t.pool_frame_stride = (long long)(rows / 2) * (cols / 2) * channels;
+    } else {
+        DODT_REQUIRE(pad_top < rows, "dodt_frame_restore_host: bad geometry");
+        pl.feat = src; pl.bneck = src2;
+        pl.pad_top = pad_top; pl.out_h = rows - pad_top; pl.out_c = channels;
+    }
+    ft::restore_item(pl, t, make_int4(item[0], item[1], item[2], item[3]), dst, dst2, 0, 1);
+    return DODT_OK;
+}
+
+int dodt_frame_lists_host(const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
+                          const int* items, int n_items, const uint8_t* prev, int* run, int* n_run, int* restore,
+                          int* n_restore) {
+    DODT_REQUIRE(restore && n_restore, "dodt_frame_lists_host: NULL argument");
+    return frame_lists_host("dodt_frame_lists_host", masks, frames, rows, cols, layer, th, tw, items, n_items, prev, run,
+                            n_run, restore, n_restore);
 }
 
 int dodt_extractor_output_shape(const dodt_extractor* ex, int* h, int* w, int* c) {
@@ -1709,12 +2012,34 @@ int dodt_extractor_first_layers_folded(const dodt_extractor* ex) {
 int dodt_extractor_read_activation(dodt_extractor* ex, const char* name, float* dst, int* h,
                                    int* w, int* c) {
     DODT_REQUIRE(ex && name, "dodt_extractor_read_activation: NULL argument");
+    // "store:<layer>": the constants store's map of the layer (one frame, returned for every frame of the batch);
+    // "store:pyramid_fusion1" and "store:bottleneck": the store's output pair
+    const bool stored = std::strncmp(name, "store:", 6) == 0;
+    if (stored) {
+        name += 6;
+        DODT_REQUIRE(ex->store_valid, "dodt_extractor_read_activation: no constants store (no forward has restored yet)");
+        const bool bn = std::strcmp(name, "bottleneck") == 0;
+        if (bn || std::strcmp(name, "pyramid_fusion1") == 0) {
+            DODT_REQUIRE(!bn || ex->bneck_loaded, "dodt_extractor_read_activation: the store holds no bottleneck map");
+            const int cc = bn ? 1 : ex->out_c;
+            if (h) *h = ex->out_h;
+            if (w) *w = ex->out_w;
+            if (c) *c = cc;
+            if (!dst) return DODT_OK;
+            const size_t n = (size_t)ex->out_h * ex->out_w * cc;
+            for (int f = 0; f < ex->batch; ++f)
+                DODT_HIP_CHECK(hipMemcpy(dst + f * n, bn ? ex->store_bneck : ex->store_feat, n * sizeof(float), hipMemcpyDeviceToHost));
+            return DODT_OK;
+        }
+    }
     const int li = find_layer(ex, name);
     DODT_REQUIRE(li >= 0, "dodt_extractor_read_activation: unknown layer '%s'", name);
     const Layer& l = ex->layers[li];
     DODT_REQUIRE(!(li == 0 && ex->first2_variant >= 0),
                  "layer %s runs folded into conv1_2's launch: its map is not stored (DODT_CONV_BF16_FIRST2=0 keeps it)", name);
-    const Buffer& b = ex->buf[buffer_for_layer_output(l)];
+    Buffer b = ex->buf[buffer_for_layer_output(l)];
+    if (stored) b.ptr = ex->store[buffer_for_layer_output(l)];
+    const size_t frame_step = stored ? 0 : b.frame_floats();
     DODT_REQUIRE(b.ptr != nullptr,
                  "layer %s is written straight into the caller's output buffer", name);
     const int oh = l.deconv ? 2 * l.H : l.H, ow = l.deconv ? 2 * l.W : l.W;
@@ -1731,7 +2056,7 @@ int dodt_extractor_read_activation(dodt_extractor* ex, const char* name, float* 
     const uint16_t* tmp16 = reinterpret_cast<const uint16_t*>(tmp.data());
     for (int f = 0; f < ex->batch; ++f) {
         DODT_HIP_CHECK(hipMemcpy(tmp.data(),
-                                 b.ptr + (size_t)f * b.frame_floats() + (size_t)(l.dst_coff / pc) * plane,
+                                 b.ptr + (size_t)f * frame_step + (size_t)(l.dst_coff / pc) * plane,
                                  tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
         float* o = dst + (size_t)f * oh * ow * l.Cout;
         for (int pl = 0; pl < planes; ++pl)
@@ -1759,7 +2084,7 @@ double dodt_extractor_bytes(const dodt_extractor* ex) {
     if (!ex) return 0.0;
     double b = 0.0;
     const WorkShare share(ex);
-    for (const Layer& l : ex->layers) b += layer_bytes(ex, l, share.of(ex, l));
+    for (const Layer& l : ex->layers) b += layer_bytes(ex, l, share.of(ex, l)) + share.restore_bytes(ex, l);
     if (ex->kind == DODT_EXTRACTOR_VGG)   // upsampling: conv4_3 read, the feature map written
         b += (double)ex->batch * ((double)ex->buf[C4C].H * ex->buf[C4C].W * 256 +
                                   (double)ex->out_h * ex->out_w * 256) * 4.0;

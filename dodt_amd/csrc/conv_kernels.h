@@ -832,9 +832,17 @@ conv3x3_small_cin_kernel(const ConvArgs a) {
     float v[NIT][VEC];
     // every load of the thread is issued before the first LDS write (a loop with a load and its write per trip ran
     // one global-memory latency per trip)
-    // work item bid of the table: (frame, channel tile = 0, ty0, tx0) -- the host may leave tiles out
+    // work item bid of the table: (frame, channel tile = 0, ty0, tx0) -- the host may leave tiles out; a full table
+    // comes as items = nullptr and its coordinates from the index (frame-major, rows of tiles): no load ahead of the
+    // patch's loads
+    const int tiles = a.tiles_x * a.tiles_y;
+    auto item_of = [&](int bid) {
+        if (a.items) return a.items[bid];
+        const int frame = bid / tiles, t2 = bid - frame * tiles;
+        return make_int4(frame, 0, (t2 / a.tiles_x) * Cfg::TH, (t2 % a.tiles_x) * TW);
+    };
     auto load_patch = [&](int bid) {
-        const int4 item = a.items[bid];
+        const int4 item = item_of(bid);
         const int frame = item.x, ty0 = item.z, tx0 = item.w;
         const float* in = a.in + (size_t)frame * a.in_frame_stride;
 #pragma unroll
@@ -909,7 +917,7 @@ conv3x3_small_cin_kernel(const ConvArgs a) {
                 }
             }
         }
-        const int4 item = a.items[bid];
+        const int4 item = item_of(bid);
         const int frame = item.x, ty0 = item.z, tx0 = item.w;
         float* out = a.out + (size_t)frame * a.out_frame_stride;
 #pragma unroll

@@ -30,8 +30,10 @@ struct Table {
     int f = 1;                     // a transposed conv (th, tw at the output resolution)
     uint8_t* now = nullptr;        // [n] 1: the item's outputs may depend on this forward's input
     uint8_t* prev = nullptr;       // [n] the same for the last forward into the same buffer
-    int4* run = nullptr;           // [n] compacted: the items with now | prev, in the table's order
+    int4* run = nullptr;           // [n] compacted: the items with now, in the table's order (the launch computes them)
     int* count = nullptr;          // how many
+    int4* restore = nullptr;       // [n] compacted: the items with prev and not now, in the table's order (their outputs
+    int* rcount = nullptr;         // go back to the input-independent values by copy); how many
 };
 
 struct Plan {
@@ -220,18 +222,20 @@ DODT_FT_HD void walk(const Plan& pl, int frame, uint32_t* a, uint32_t* b, int ti
     }
 }
 
-// Compaction of one table by a team: run = the items with now | prev in the table's order, count = how many, and
-// prev = now for the next forward.  scan: [nthr + 1] ints the team shares.  prev: the table's own or, for the layer
-// that writes the caller's buffers, that buffer pair's.
+// Compaction of one table by a team into two lists, both in the table's order: run = the items with now (count of
+// them), restore = the items with prev and not now (rcount), and prev = now for the next forward.  scan: [nthr + 1]
+// ints the team shares (a kept item adds 1, a restored one 1 << 16: both prefix sums in one scan; nthr <= 32768).
+// prev: the table's own or, for the layer that writes the caller's buffers, that buffer pair's.
 template <class Sync>
 DODT_FT_HD void compact(const Table& t, uint8_t* prev, int* scan, int tid, int nthr, Sync sync) {
-    int base = 0;
+    int base = 0, rbase = 0;
     for (int i0 = 0; i0 < t.n; i0 += nthr) {
         const int i = i0 + tid;
         const uint8_t now = i < t.n ? t.now[i] : 0;
-        const int keep = i < t.n && (now | prev[i]) ? 1 : 0;
+        const int keep = i < t.n && now ? 1 : 0;
+        const int back = i < t.n && !now && prev[i] ? 1 : 0;
         if (i < t.n) prev[i] = now;
-        scan[tid + 1] = keep;
+        scan[tid + 1] = keep | (back << 16);
         if (tid == 0) scan[0] = 0;
         sync();
         for (int d = 1; d < nthr; d <<= 1) {      // inclusive scan of scan[1 .. nthr]
@@ -240,11 +244,94 @@ DODT_FT_HD void compact(const Table& t, uint8_t* prev, int* scan, int tid, int n
             scan[tid + 1] += v;
             sync();
         }
-        if (keep) t.run[base + scan[tid]] = t.items[i];
-        base += scan[nthr];
+        if (keep) t.run[base + (scan[tid] & 0xffff)] = t.items[i];
+        if (back) t.restore[rbase + (scan[tid] >> 16)] = t.items[i];
+        base += scan[nthr] & 0xffff;
+        rbase += scan[nthr] >> 16;
         sync();
     }
-    if (tid == 0) *t.count = base;
+    if (tid == 0) {
+        *t.count = base;
+        *t.rcount = rbase;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Restoring: the outputs of a table's restore items go back to the constants store's values by copy
+// ---------------------------------------------------------------------------------------------------------------
+// one table's restore list and where its items' outputs live
+struct RestoreTable {
+    const int4* list = nullptr;    // {frame, channel tile, y0, x0} (nullptr: no such launch)
+    const int* count = nullptr;
+    float* dst = nullptr;          // the live CB8 map; nullptr: the caller's NHWC pair (pyramid_fusion1)
+    const float* src = nullptr;    // the store's map (one frame)
+    long long frame_stride = 0;    // of dst, floats
+    int H = 0, W = 0;              // the map's size
+    int ch0 = 0, bn = 0;           // channel tile n holds channels ch0 + n bn ..
+    int f = 1, th = 0, tw = 0;     // an item writes th x tw outputs from (f y0, f x0)
+    float* pool_dst = nullptr;     // the fused 2x2 pool's map (channel tile n: channels n bn ..), or nullptr
+    const float* pool_src = nullptr;
+    long long pool_frame_stride = 0;
+};
+struct RestorePlan {
+    RestoreTable t[kTables];
+    const float* feat = nullptr;   // the store's (feature, bottleneck) pair, one frame, pad rows sliced off
+    const float* bneck = nullptr;
+    int pad_top = 0, out_h = 0, out_c = 0;
+};
+
+struct alignas(16) Quad { float v[4]; };   // 16 bytes per load and store
+
+// th x tw cells of nch channels from (y0, x0) of a CB8 map ([C / 8][H][W][8]), clipped to the map
+DODT_FT_HD void restore_cb8(float* dst, const float* src, int H, int W, int ch0, int nch, int y0, int x0, int th, int tw,
+                            int tid, int nthr) {
+    const int tw2 = tw * 2, per_plane = th * tw2, n = (nch >> 3) * per_plane;
+    const Quad* s4 = reinterpret_cast<const Quad*>(src);
+    Quad* d4 = reinterpret_cast<Quad*>(dst);
+    for (int i = tid; i < n; i += nthr) {
+        const int p = i / per_plane, r = (i - p * per_plane) / tw2, c = i - p * per_plane - r * tw2;
+        const int y = y0 + r, x2 = x0 * 2 + c;
+        if (y >= H || x2 >= W * 2) continue;
+        const size_t off = ((size_t)((ch0 >> 3) + p) * H + y) * (W * 2) + x2;
+        d4[off] = s4[off];
+    }
+}
+
+// One restore item by a team.  A layer buffer: the tile's channels and, where the pool is fused, the pooled tile.
+// pyramid_fusion1 (t.dst == nullptr): the rows of the caller's NHWC feature map (row pad_top of the layer's grid is its
+// row 0) and, for channel tile 0, the same cells of the bottleneck map.
+DODT_FT_HD void restore_item(const RestorePlan& pl, const RestoreTable& t, int4 it, float* feat, float* bneck, int tid,
+                             int nthr) {
+    const int y0 = t.f * it.z, x0 = t.f * it.w;
+    if (t.dst) {
+        restore_cb8(t.dst + (size_t)it.x * t.frame_stride, t.src, t.H, t.W, t.ch0 + it.y * t.bn, t.bn, y0, x0, t.th, t.tw,
+                    tid, nthr);
+        if (t.pool_dst)
+            restore_cb8(t.pool_dst + (size_t)it.x * t.pool_frame_stride, t.pool_src, t.H >> 1, t.W >> 1, it.y * t.bn, t.bn,
+                        y0 >> 1, x0 >> 1, t.th >> 1, t.tw >> 1, tid, nthr);
+        return;
+    }
+    const int c4n = t.bn >> 2, row4 = t.W * (pl.out_c >> 2), n = t.th * t.tw * c4n;
+    const Quad* s4 = reinterpret_cast<const Quad*>(pl.feat);
+    Quad* d4 = reinterpret_cast<Quad*>(feat) + (size_t)it.x * pl.out_h * row4;
+    for (int j = tid; j < n; j += nthr) {
+        const int r = j / (t.tw * c4n), x = (j - r * t.tw * c4n) / c4n, c = j - (r * t.tw + x) * c4n;
+        const int y = y0 + r - pl.pad_top;
+        if (y < 0 || y >= pl.out_h || x0 + x >= t.W) continue;
+        const size_t off = (size_t)y * row4 + (size_t)(x0 + x) * (pl.out_c >> 2) + ((t.ch0 + it.y * t.bn) >> 2) + c;
+        d4[off] = s4[off];
+    }
+    if (bneck && pl.bneck && it.y == 0) {
+        const int tw4 = t.tw >> 2, w4 = t.W >> 2;
+        const Quad* b4 = reinterpret_cast<const Quad*>(pl.bneck);
+        Quad* o4 = reinterpret_cast<Quad*>(bneck) + (size_t)it.x * pl.out_h * w4;
+        for (int j = tid; j < t.th * tw4; j += nthr) {
+            const int r = j / tw4, c = (x0 >> 2) + j - r * tw4;
+            const int y = y0 + r - pl.pad_top;
+            if (y < 0 || y >= pl.out_h || c >= w4) continue;
+            o4[(size_t)y * w4 + c] = b4[(size_t)y * w4 + c];
+        }
+    }
 }
 
 #undef DODT_FT_HD

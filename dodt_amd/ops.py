@@ -98,6 +98,42 @@ def frame_tables_host(masks, layer, th, tw, items, prev=None, lib=None):
     return run[:n.value].copy()
 
 
+def frame_lists_host(masks, layer, th, tw, items, prev=None, lib=None):
+    """The two lists of frame_tables_host's union (dodt_frame_lists_host), each (k, 4) in table order: the items this
+    input reaches (computed) and the items of prev it does not reach (restored from the constants store)."""
+    lib = lib or _lib.load()
+    masks = np.ascontiguousarray(masks, dtype=np.uint8)
+    items = np.ascontiguousarray(items, dtype=np.int32).reshape(-1, 4)
+    prev = None if prev is None else np.ascontiguousarray(prev, dtype=np.uint8)
+    run = np.zeros((max(len(items), 1), 4), np.int32)
+    restore = np.zeros((max(len(items), 1), 4), np.int32)
+    n, nr = C.c_int(), C.c_int()
+    _lib.check(lib.dodt_frame_lists_host(masks.ctypes.data, masks.shape[0], masks.shape[1], masks.shape[2], int(layer),
+                                         int(th), int(tw), items.ctypes.data, len(items),
+                                         None if prev is None else prev.ctypes.data, run.ctypes.data, C.byref(n),
+                                         restore.ctypes.data, C.byref(nr)),
+               'dodt_frame_lists_host')
+    return run[:n.value].copy(), restore[:nr.value].copy()
+
+
+def frame_restore_host(item, f, th, tw, bn, ch0, dst, src, dst2=None, src2=None, pad_top=-1, lib=None):
+    """The copy the restore launch makes for one item, on host arrays and in place (dodt_frame_restore_host).  pad_top
+    < 0: dst (frames, C / 8, rows, cols, 8) channel-blocked, src one frame of it, dst2 / src2 the pooled maps.
+    pad_top >= 0: dst (frames, rows - pad_top, cols, C) NHWC, src one frame of it, dst2 / src2 the bottleneck maps."""
+    lib = lib or _lib.load()
+    for a in (dst, src, dst2, src2):
+        assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous)
+    item = np.ascontiguousarray(item, dtype=np.int32)
+    if pad_top < 0:
+        rows, cols, channels = dst.shape[2], dst.shape[3], dst.shape[1] * 8
+    else:
+        rows, cols, channels = dst.shape[1] + pad_top, dst.shape[2], dst.shape[3]
+    _lib.check(lib.dodt_frame_restore_host(item.ctypes.data, int(f), int(th), int(tw), int(bn), int(ch0), rows, cols,
+                                           channels, int(pad_top), dst.ctypes.data, src.ctypes.data,
+                                           None if dst2 is None else dst2.ctypes.data,
+                                           None if src2 is None else src2.ctypes.data), 'dodt_frame_restore_host')
+
+
 def bev_status(ctx):
     f = C.c_int()
     _lib.check(ctx.lib.dodt_bev_status(ctx.handle, C.byref(f)), 'dodt_bev_status')

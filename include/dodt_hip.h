@@ -283,18 +283,29 @@ int dodt_extractor_set_input_support(dodt_extractor* ex, const uint8_t* mask, in
  * then builds its tables on the device, ahead of the layers on the extractor's stream and without a host round trip:
  * the non-zero cells of the input map (any channel) as a bit mask per frame, propagated by the same geometry at cell
  * resolution, keep the items of each skip table this input reaches, in the table's order; the kernels read the item
- * count from device memory.  A launch runs these items and the ones the last forward into the same buffer ran, so
- * every output that was input-dependent then goes back to the value a full forward writes; after every forward each
- * layer buffer holds what a forward on full tables would have written.  The forwards that run full tables (see
+ * count from device memory.  A launch computes these items.  The items the last forward into the same buffer reached
+ * and this one does not are restored: one launch ahead of the first layer copies their outputs (a conv tile's channels
+ * and its pooled tile, a transposed conv's 2 TH x 2 TW outputs, the NHWC rows of the caller's feature / bottleneck
+ * pair) from a constants store, one frame of every layer buffer and of the output pair as a forward on a zero input
+ * writes them.  The store is taken by the first forward that restores and again after a dodt_extractor_set_layer (that
+ * forward waits for the stream), and freed with the tables.  After every forward each layer buffer holds what a
+ * forward on full tables would have written.  The forwards that run full tables (see
  * above) record their input's items the same way; pyramid_fusion1 keeps the items per remembered output pair.
  * *enabled (may be NULL): 1 if the tables are on; 0 if the extractor has no skip tables or runs F(4x4,3x3) layers
  * (DODT_CONV_WINO=4: those reach block-wise), which keeps the static tables.  dodt_extractor_set_input_support
  * turns the per-frame tables off again.  While they are on, dodt_extractor_flops / _mfma_flops / _bytes wait for
  * the stream and count the items of the last finished forward. */
 int dodt_extractor_set_frame_tables(dodt_extractor* ex, int on, int* enabled);
-/* The work items each layer of the last forward ran from per-frame tables (waits for the stream): items[layer] in
- * launch order, n >= dodt_extractor_layer_count(); -1 for a layer that ran a full or static table. */
+/* The work items each layer of the last forward touched from per-frame tables, computed or restored (waits for the
+ * stream): items[layer] in launch order, n >= dodt_extractor_layer_count(); -1 for a layer that ran a full or static
+ * table. */
 int dodt_extractor_frame_items(dodt_extractor* ex, int* items, int n);
+/* The same split: computed[layer] items the layer's kernels ran, restored[layer] items copied back from the constants
+ * store (-1 / -1 for a layer that ran a full or static table).  dodt_extractor_flops / _mfma_flops count the
+ * computed items, dodt_extractor_bytes also the copies (store read, buffer written). */
+int dodt_extractor_frame_split(dodt_extractor* ex, int* computed, int* restored, int n);
+/* Device memory the constants store holds (0 before the first forward that restores and after it is freed). */
+long long dodt_extractor_store_bytes(const dodt_extractor* ex);
 /* Host only: the per-frame rule of dodt_extractor_set_frame_tables on host masks, for one layer (0 .. 15 in launch
  * order) of the pyramid net.  masks: frames x rows x cols bytes, non-zero where the frame's padded input is; items:
  * n_items x {frame, channel tile, y0, x0} in table order, each writing th x tw outputs of the layer's GEMM grid
@@ -302,6 +313,20 @@ int dodt_extractor_frame_items(dodt_extractor* ex, int* items, int n);
  * run (room for n_items x 4 ints) receives the items of this input or of prev, in table order, *n_run their count. */
 int dodt_frame_tables_host(const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
                            const int* items, int n_items, const uint8_t* prev, int* run, int* n_run);
+/* The two lists a forward takes, each in table order: run = the items of this input (the kernels compute them),
+ * restore = the items of prev that are not of this input (copied back from the constants store); both with room for
+ * n_items x 4 ints. */
+int dodt_frame_lists_host(const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
+                          const int* items, int n_items, const uint8_t* prev, int* run, int* n_run, int* restore,
+                          int* n_restore);
+/* Host only: the copy the restore launch makes for one item {frame, channel tile, y0, x0} of a table with th x tw
+ * tiles (f = 2: a transposed conv's, 2 th x 2 tw outputs from (2 y0, 2 x0)) and bn channels per tile from channel ch0,
+ * run by the functions the device runs.  pad_top < 0: dst is a channel-blocked map of frames x [channels / 8][rows]
+ * [cols][8] floats, src one frame of it; dst2 / src2 (may both be NULL) the 2x2-pooled maps of the same channels.
+ * pad_top >= 0: dst is the NHWC feature map of frames x (rows - pad_top) x cols x channels (row pad_top of the layer's
+ * grid is its row 0), src one frame of it, dst2 / src2 (may both be NULL) the bottleneck maps, one float per cell. */
+int dodt_frame_restore_host(const int* item, int f, int th, int tw, int bn, int ch0, int rows, int cols, int channels,
+                            int pad_top, float* dst, const float* src, float* dst2, const float* src2);
 /* Size of the feature map forward() returns: (in_h, in_w, 32) for the pyramid,
  * (in_h / 8 * 4, in_w / 8 * 4, 256) for DODT_EXTRACTOR_VGG. */
 int dodt_extractor_output_shape(const dodt_extractor* ex, int* h, int* w, int* c);
@@ -311,7 +336,9 @@ int dodt_extractor_output_shape(const dodt_extractor* ex, int* h, int* w, int* c
  * (fp32 / split conv paths, or DODT_CONV_BF16_FIRST2=0); a negative DODT_ERR_* code for a NULL extractor. */
 int dodt_extractor_first_layers_folded(const dodt_extractor* ex);
 /* Debug/test access to an intermediate activation by layer name: copies the
- * (batch, h, w, c) float32 tensor to host memory `dst` (NULL to query shape). */
+ * (batch, h, w, c) float32 tensor to host memory `dst` (NULL to query shape).  "store:<layer>" reads the constants
+ * store of the per-frame tables instead (its one frame for every frame of the batch; "store:pyramid_fusion1" and
+ * "store:bottleneck": the store's output pair). */
 int dodt_extractor_read_activation(dodt_extractor* ex, const char* name, float* dst,
                                    int* h, int* w, int* c);
 /* FLOPs of one forward call (2*M*N*K summed over conv layers, all frames): the ALGORITHMIC
