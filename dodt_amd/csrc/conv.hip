@@ -12,34 +12,22 @@
 // The decoder's concat inputs are single buffers whose channel planes the two
 // producing kernels write directly (conv_k -> planes 0.., upconv_k -> the planes
 // after them), so no concat copy exists.  Both frames of a pair are one batch.
+//
+// This file: the kernel variants and their choice, the small kernels, the extractor's lifecycle, the forward and the
+// work accounting.  conv_weights.hip blocks the weights, conv_skip.hip holds the skip tables, the per-frame tables and
+// the constants store; extractor.h is the state they share.
 #include <cmath>
 #include <cstring>
-#include <string>
-#include <vector>
 
 #include <algorithm>
-#include <array>
 #include <utility>
 
-#include "common.h"
-#include "conv_kernels.h"
 #include "conv_variants.h"
-#include "frame_tables.h"
+#include "extractor.h"
 
-namespace {
+using namespace dodt;
 
-using dodt::ConvArgs;
-
-using dodt::KernelVariant;
-using dodt::Inst;
-using dodt::InstSmall;
-using dodt::InstWino;
-using dodt::InstWino43;
-using dodt::InstDeconvDma;
-using dodt::tail_only;
-using dodt::f32x4;
-
-const std::vector<KernelVariant>& variants() {
+const std::vector<KernelVariant>& dodt::variants() {
     static const std::vector<KernelVariant> v = {
         InstSmall<32, 16, 6>::variant(),
         InstSmall<16, 12, 4>::variant(),
@@ -82,8 +70,6 @@ const std::vector<KernelVariant>& variants() {
     }();
     return all;
 }
-
-}  // namespace
 
 // which form the fp32 3x3 stride-1 layers take in this process (read once)
 extern "C" int dodt_conv_mode(void) {
@@ -359,187 +345,14 @@ upsample_bilinear_cb8_kernel(const float* __restrict__ in, int IH, int IW, long 
     }
 }
 
-// ---------------------------------------------------------------------------
-// extractor object
-// ---------------------------------------------------------------------------
-struct Buffer {
-    int H = 0, W = 0, C = 0;
-    float* ptr = nullptr;
-    bool bf16 = false;   // CB16 bf16 map (2 bytes per element) instead of CB8 / NHWC fp32
-    int parts = 1;       // 2: split mode, [hi map of all frames | lo map of all frames]
-    size_t frame_floats() const { return (size_t)H * W * C / (bf16 ? 2 : 1); }   // one part
-};
-
-// one kernel launch of a layer: a variant and the work items it walks
-struct Launch {
-    int variant = -1;
-    int n_items = 0;
-    int4* d_items = nullptr;
-    float* d_w = nullptr;   // weights blocked for this variant's BN
-    std::vector<int4> h_items;   // the full table on the host (skip tables are filtered from it)
-    int n_skip = -1;             // >= 0: the skip table (dodt_extractor_set_input_support), possibly empty
-    int4* d_skip = nullptr;
-    // per-frame tables (dodt_extractor_set_frame_tables): this forward's items of the skip table and their count
-    int4* d_run = nullptr;
-    int* d_count = nullptr;
-};
-
-struct Layer {
-    std::string name;
-    bool deconv = false;
-    int H = 0, W = 0;  // GEMM grid (conv: output size; deconv: input size)
-    int Cin = 0, Cout = 0;
-    int src = -1, src_coff = 0;
-    int dst = -1, dst_coff = 0;
-    int variant = -1;
-    Launch main, tail;   // tail.n_items == 0: single launch
-    float *d_scale = nullptr, *d_shift = nullptr;
-    bool loaded = false;
-    int real_cin = 0;  // channels that carry data (conv1_1 of the image net: 3 of 4)
-    float* d_first_w = nullptr;   // conv1_1 of a bf16 extractor: hi + lo bf16 MFMA fragments for conv3x3_bf16_first2_kernel
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // dodt_extractor_forward_timed
-    double skip_frac = 1.0;   // share of the layer's MFMA work its skip tables keep
-};
-
-enum Buf { X0, C1A, CAT1, P1, C2A, CAT2, P2, C3A, C3B, CAT3, P3, C4A, C4B, C4C, F3, F2, F1, NBUF };
-
-}  // namespace
-
-struct dodt_extractor {
-    dodt_ctx* ctx = nullptr;
-    int in_h = 0, in_w = 0, in_c = 0, pad_top = 0, batch = 0;
-    int kind = DODT_EXTRACTOR_VGG_PYR;
-    int out_h = 0, out_w = 0, out_c = 32;   // the returned feature map
-    bool bf16 = false;  // conv path on bf16 MFMA (fp32 accumulate, fp32 BN/ReLU, bf16 maps)
-    int parts = 1;      // 2: split mode (hi + lo bf16 maps and weights, three MFMAs per term)
-    int H = 0, W = 0;  // padded input size
-    Buffer buf[NBUF];
-    std::vector<Layer> layers;
-    float* d_bneck_w = nullptr;
-    int* d_counters = nullptr;  // two work-item counters per layer, zeroed every forward
-    float* d_zeros = nullptr;   // a zero page (Winograd kernel: out-of-image pixels)
-    float bneck_scale = 1.0f, bneck_shift = 0.0f;
-    bool bneck_loaded = false;
-    double flops = 0.0;
-    bool timed = false;   // this forward records an event pair around every layer
-    int first2_variant = -1;   // >= 0: conv1_1 runs folded into conv1_2's launch (bf16 conv path; DODT_CONV_BF16_FIRST2=0: not)
-    float* own_x0 = nullptr;   // the extractor's own input buffer while dodt_extractor_set_input points X0 elsewhere
-    // input support (dodt_extractor_set_input_support): skip tables built; a full forward has run since the last
-    // weight load; the (feature, bottleneck) output pairs pyramid_fusion1 has written with full tables since then
-    bool skip_on = false;
-    bool primed = false;
-    std::vector<std::pair<const float*, const float*>> primed_out;
-    std::vector<char> skipping;   // per layer: this forward runs its skip tables (2: the per-frame ones)
-    // per-frame tables (dodt_extractor_set_frame_tables): the builder's plan (frame_tables.h), its device copy, the
-    // frames' input bit masks, every allocation of the tables, and per remembered output pair (primed_out) which
-    // of the eight item sets of pyramid_fusion1's last forward into it is the pair's
-    bool frame_on = false;
-    dodt::ft::Plan frame_plan;
-    dodt::ft::Plan* d_frame_plan = nullptr;
-    uint32_t* d_frame_bits = nullptr;
-    int* d_frame_counts = nullptr;
-    std::vector<void*> frame_allocs;
-    uint8_t* out_prev[8][2] = {};
-    std::vector<int> out_slot;
-    // constants store (per-frame tables): one frame of every layer buffer and of the (feature, bottleneck) pair as a
-    // forward on zeros writes them -- what an output holds that no input reaches.  Taken by the first forward that
-    // restores from it (take_store), again after new weights; freed with the per-frame tables.
-    float* store[NBUF] = {};
-    float* store_feat = nullptr;
-    float* store_bneck = nullptr;
-    dodt::ft::RestorePlan* d_restore_plan = nullptr;
-    bool store_valid = false;
-    bool restoring = false;   // the last forward ran the restore launch
-    size_t store_bytes = 0;
-};
-
-namespace {
-
 int find_layer(dodt_extractor* ex, const char* name) {
     for (size_t i = 0; i < ex->layers.size(); ++i)
         if (ex->layers[i].name == name) return (int)i;
     return -1;
 }
 
-int buffer_for_layer_output(const Layer& l) { return l.dst; }
-
-int run_launch(dodt_extractor* ex, const Layer& l, const Launch& ln, int which,
-               float* override_out, int out_y0, int out_h, float* bneck_out, int pool_dst, const Layer* folded = nullptr) {
-    // folded: conv1_1, computed inside this launch of conv1_2 (same items and weights as conv1_2's streaming kernel)
-    const KernelVariant& v = variants()[folded ? ex->first2_variant : ln.variant];
-    const Buffer& src = ex->buf[folded ? folded->src : l.src];
-    const Buffer& dst = ex->buf[l.dst];
-    ConvArgs a;
-    a.in = src.ptr;
-    a.out = override_out ? override_out : dst.ptr;
-    a.w = ln.d_w ? ln.d_w : l.main.d_w;
-    a.scale = l.d_scale;
-    a.shift = l.d_shift;
-    a.H = l.H;
-    a.W = l.W;
-    a.Cin = l.Cin;
-    a.Cout = l.Cout;
-    a.in_ld = src.C;
-    a.in_coff = folded ? folded->src_coff : l.src_coff;
-    a.out_ld = dst.C;
-    a.out_coff = l.dst_coff;
-    a.in_frame_stride = (long long)src.frame_floats();
-    a.out_frame_stride = override_out ? (long long)out_h * dst.W * dst.C : (long long)dst.frame_floats();
-    a.tiles_x = dodt::ceil_div(l.W, v.TW);
-    a.tiles_y = dodt::ceil_div(l.H, v.TH);
-    a.relu = 1;
-    a.out_y0 = out_y0;
-    a.out_nhwc = override_out ? 1 : 0;
-    {
-        static const int dbg = getenv("DODT_CONV_DEBUG") ? atoi(getenv("DODT_CONV_DEBUG")) : 0;
-        a.debug = dbg;
-        // DODT_CONV_STAMP_LAYER=<name>: in-kernel step stamps of that layer's launch (diagnostic)
-        static const char* stamp_layer = getenv("DODT_CONV_STAMP_LAYER");
-        if (stamp_layer && l.name == stamp_layer) a.debug |= 32;     // (+ DODT_CONV_DEBUG=64: the streaming kernel's producer wave)
-    }
-    a.counter = ex->d_counters + 2 * (&l - ex->layers.data()) + which;
-    a.counter_base = ex->d_counters + 64;
-    // (eight counters, 64 bytes apart, per layer: words 2048.. of the block)
-    a.xcd_counters = variant_xcd_queue(v) ? ex->d_counters + 2048 + 128 * (&l - ex->layers.data()) : nullptr;
-    const size_t li = &l - ex->layers.data();
-    const bool skip = li < ex->skipping.size() && ex->skipping[li] && ln.n_skip >= 0;
-    a.items = skip ? ln.d_skip : ln.d_items;
-    a.n_items = skip ? ln.n_skip : ln.n_items;
-    // the first-layer kernel derives a full table's coordinates from the item index (no table load ahead of its patch)
-    if (v.small_cin && !skip && a.n_items == a.tiles_x * a.tiles_y * ex->batch) a.items = nullptr;
-    if (a.n_items == 0) return DODT_OK;   // every item of the launch skipped
-    // per-frame tables: the builder's launches ahead in the stream wrote this forward's items and their count
-    const bool per_frame = skip && ex->skipping[li] == 2 && ln.d_run;
-    if (per_frame) a.items = ln.d_run;
-    a.n_items_dev = per_frame ? ln.d_count : nullptr;
-    a.in_part_stride = (long long)src.frame_floats() * ex->batch;
-    a.out_part_stride = (long long)dst.frame_floats() * ex->batch;
-    a.pool_part_stride = pool_dst >= 0 ? (long long)ex->buf[pool_dst].frame_floats() * ex->batch : 0;
-    a.pool_out = pool_dst >= 0 ? ex->buf[pool_dst].ptr : nullptr;
-    a.pool_frame_stride = pool_dst >= 0 ? (long long)ex->buf[pool_dst].frame_floats() : 0;
-    a.bneck_w = bneck_out ? ex->d_bneck_w : nullptr;
-    a.bneck_out = bneck_out;
-    a.bneck_scale = ex->bneck_scale;
-    a.bneck_shift = ex->bneck_shift;
-    a.bneck_frame_stride = (long long)out_h * dst.W;
-    a.zeros = ex->d_zeros;
-    a.first_w = folded ? folded->d_first_w : nullptr;
-    a.first_scale = folded ? folded->d_scale : nullptr;
-    a.first_shift = folded ? folded->d_shift : nullptr;
-    // persistent workgroups: as many as stay resident, each walks items with that stride
-    int grid_x = a.n_items;
-    {
-        static const int bpc_env = getenv("DODT_CONV_BPC") ? atoi(getenv("DODT_CONV_BPC")) : 0;
-        // (the first-layer kernel is persistent since round 4: three workgroups per CU by its registers)
-        static const int small_bpc = getenv("DODT_CONV_SMALL_BPC") ? atoi(getenv("DODT_CONV_SMALL_BPC")) : 3;
-        const int vb = v.small_cin ? small_bpc : v.blocks_per_cu;
-        const int bpc = (bpc_env > 0 && bpc_env < vb) ? bpc_env : vb;
-        const int resident = ex->ctx->num_cus * bpc;
-        if (grid_x > resident) grid_x = resident;
-    }
-    dim3 grid(grid_x, 1);
-    v.launch(a, grid, ex->ctx->stream);
-    DODT_LAUNCH_CHECK();
+// DODT_CONV_DEBUG / DODT_CONV_STAMP_LAYER: read back what the launch just left in the diagnostic words (waits for it)
+void report_launch(const dodt_extractor* ex, const Layer& l, const KernelVariant& v, const ConvArgs& a, int grid_x) {
     if (a.debug & 32) {
         int h[74];
         (void)hipStreamSynchronize(ex->ctx->stream);
@@ -585,6 +398,86 @@ int run_launch(dodt_extractor* ex, const Layer& l, const Launch& ln, int which,
             fprintf(stderr, "[dodt] %-16s wg0: %.1f us, shader clock %.3f GHz\n", l.name.c_str(),
                     h[1] / 100.0, (double)h[0] / h[1] * 0.1);
     }
+}
+
+// which: 0 the layer's main launch, 1 its tail
+int run_launch(const dodt_extractor* ex, const Pass& p, const Layer& l, int which,
+               float* override_out, int out_y0, int out_h, float* bneck_out, int pool_dst, const Layer* folded = nullptr) {
+    // folded: conv1_1, computed inside this launch of conv1_2 (same items and weights as conv1_2's streaming kernel)
+    const Launch& ln = which ? l.tail : l.main;
+    const size_t li = &l - ex->layers.data();
+    const ItemTable& t = p.table[li][which];
+    const KernelVariant& v = variants()[folded ? ex->first2_variant : ln.variant];
+    const int src_id = folded ? folded->src : l.src;
+    const Buffer& src = ex->buf[src_id];
+    const Buffer& dst = ex->buf[l.dst];
+    ConvArgs a;
+    a.in = p.map[src_id];
+    a.out = override_out ? override_out : p.map[l.dst];
+    a.w = ln.d_w ? ln.d_w : l.main.d_w;
+    a.scale = l.d_scale;
+    a.shift = l.d_shift;
+    a.H = l.H;
+    a.W = l.W;
+    a.Cin = l.Cin;
+    a.Cout = l.Cout;
+    a.in_ld = src.C;
+    a.in_coff = folded ? folded->src_coff : l.src_coff;
+    a.out_ld = dst.C;
+    a.out_coff = l.dst_coff;
+    a.in_frame_stride = (long long)src.frame_floats();
+    a.out_frame_stride = override_out ? (long long)out_h * dst.W * dst.C : (long long)dst.frame_floats();
+    a.tiles_x = dodt::ceil_div(l.W, v.TW);
+    a.tiles_y = dodt::ceil_div(l.H, v.TH);
+    a.relu = 1;
+    a.out_y0 = out_y0;
+    a.out_nhwc = override_out ? 1 : 0;
+    {
+        static const int dbg = getenv("DODT_CONV_DEBUG") ? atoi(getenv("DODT_CONV_DEBUG")) : 0;
+        a.debug = dbg;
+        // DODT_CONV_STAMP_LAYER=<name>: in-kernel step stamps of that layer's launch (diagnostic)
+        static const char* stamp_layer = getenv("DODT_CONV_STAMP_LAYER");
+        if (stamp_layer && l.name == stamp_layer) a.debug |= 32;     // (+ DODT_CONV_DEBUG=64: the streaming kernel's producer wave)
+    }
+    a.counter = ex->d_counters + 2 * li + which;
+    a.counter_base = ex->d_counters + 64;
+    // (eight counters, 64 bytes apart, per layer: words 2048.. of the block)
+    a.xcd_counters = variant_xcd_queue(v) ? ex->d_counters + 2048 + 128 * li : nullptr;
+    // the first-layer kernel derives a full table's coordinates from the item index (no table load ahead of its patch)
+    a.items = v.small_cin && t.dense && t.n == a.tiles_x * a.tiles_y * p.frames ? nullptr : t.items;
+    a.n_items = t.n;
+    if (a.n_items == 0) return DODT_OK;   // every item of the launch skipped
+    // per-frame tables: the builder's launches ahead in the stream wrote this forward's items and their count
+    a.n_items_dev = t.n_dev;
+    a.in_part_stride = (long long)src.frame_floats() * p.frames;
+    a.out_part_stride = (long long)dst.frame_floats() * p.frames;
+    a.pool_part_stride = pool_dst >= 0 ? (long long)ex->buf[pool_dst].frame_floats() * p.frames : 0;
+    a.pool_out = pool_dst >= 0 ? p.map[pool_dst] : nullptr;
+    a.pool_frame_stride = pool_dst >= 0 ? (long long)ex->buf[pool_dst].frame_floats() : 0;
+    a.bneck_w = bneck_out ? ex->d_bneck_w : nullptr;
+    a.bneck_out = bneck_out;
+    a.bneck_scale = ex->bneck_scale;
+    a.bneck_shift = ex->bneck_shift;
+    a.bneck_frame_stride = (long long)out_h * dst.W;
+    a.zeros = ex->d_zeros;
+    a.first_w = folded ? folded->d_first_w : nullptr;
+    a.first_scale = folded ? folded->d_scale : nullptr;
+    a.first_shift = folded ? folded->d_shift : nullptr;
+    // persistent workgroups: as many as stay resident, each walks items with that stride
+    int grid_x = a.n_items;
+    {
+        static const int bpc_env = getenv("DODT_CONV_BPC") ? atoi(getenv("DODT_CONV_BPC")) : 0;
+        // (the first-layer kernel is persistent since round 4: three workgroups per CU by its registers)
+        static const int small_bpc = getenv("DODT_CONV_SMALL_BPC") ? atoi(getenv("DODT_CONV_SMALL_BPC")) : 3;
+        const int vb = v.small_cin ? small_bpc : v.blocks_per_cu;
+        const int bpc = (bpc_env > 0 && bpc_env < vb) ? bpc_env : vb;
+        const int resident = ex->ctx->num_cus * bpc;
+        if (grid_x > resident) grid_x = resident;
+    }
+    dim3 grid(grid_x, 1);
+    v.launch(a, grid, ex->ctx->stream);
+    DODT_LAUNCH_CHECK();
+    if (a.debug & (32 | 128 | 8)) report_launch(ex, l, v, a, grid_x);
     return DODT_OK;
 }
 
@@ -601,17 +494,17 @@ bool layer_can_pool(const Layer& l) {
 }
 
 // pool_dst >= 0: the layer also writes its 2x2 max pool into that buffer
-int run_layer(dodt_extractor* ex, const Layer& l, float* override_out, int out_y0, int out_h,
+int run_layer(const dodt_extractor* ex, const Pass& p, const Layer& l, float* override_out, int out_y0, int out_h,
               float* bneck_out = nullptr, int pool_dst = -1, const Layer* folded = nullptr) {
-    if (ex->timed && folded) {      // (the folded layer has no time of its own)
+    if (p.timed && folded) {      // (the folded layer has no time of its own)
         DODT_HIP_CHECK(hipEventRecord(folded->ev0, ex->ctx->stream));
         DODT_HIP_CHECK(hipEventRecord(folded->ev1, ex->ctx->stream));
     }
-    if (ex->timed) DODT_HIP_CHECK(hipEventRecord(l.ev0, ex->ctx->stream));
-    int rc = run_launch(ex, l, l.main, 0, override_out, out_y0, out_h, bneck_out, pool_dst, folded);
-    if (rc == DODT_OK && l.tail.n_items > 0)
-        rc = run_launch(ex, l, l.tail, 1, override_out, out_y0, out_h, bneck_out, pool_dst);
-    if (rc == DODT_OK && ex->timed) DODT_HIP_CHECK(hipEventRecord(l.ev1, ex->ctx->stream));
+    if (p.timed) DODT_HIP_CHECK(hipEventRecord(l.ev0, ex->ctx->stream));
+    int rc = run_launch(ex, p, l, 0, override_out, out_y0, out_h, bneck_out, pool_dst, folded);
+    if (rc == DODT_OK && l.tail.variant >= 0)
+        rc = run_launch(ex, p, l, 1, override_out, out_y0, out_h, bneck_out, pool_dst);
+    if (rc == DODT_OK && p.timed) DODT_HIP_CHECK(hipEventRecord(l.ev1, ex->ctx->stream));
     return rc;
 }
 
@@ -631,9 +524,6 @@ double layer_direct_flops(const dodt_extractor* ex, const Layer& l, double frac 
     return 2.0 * l.H * l.W * (double)l.Cout * 9.0 * l.real_cin * ex->batch * frac;
 }
 
-// the share of a layer's work a forward in steady state runs (skip tables once primed)
-double steady_frac(const dodt_extractor* ex, const Layer& l) { return ex->skip_on ? l.skip_frac : 1.0; }
-
 // FLOPs the matrix pipe executes for a layer: the Winograd kernels multiply 36 times per 4x4
 // outputs and channel pair (F(4x4,3x3)) or 16 times per 2x2 (F(2x2,3x3)) where the direct form
 // needs 144 / 36; split mode issues three bf16 MFMAs per product term
@@ -652,14 +542,14 @@ double layer_bytes(const dodt_extractor* ex, const Layer& l, double frac = 1.0) 
     const Buffer& dst = ex->buf[l.dst];
     const double in_e = src.bf16 ? 2.0 * src.parts : 4.0;
     const double out_e = dst.bf16 ? 2.0 * dst.parts : 4.0;
-    const double w_e = (ex->bf16 && &l != &ex->layers[0]) ? 2.0 * ex->parts : 4.0;
+    const double w_e = (ex->bf16 && &l != &ex->layers[CONV1_1]) ? 2.0 * ex->parts : 4.0;
     const double oh = l.deconv ? 2.0 * l.H : l.H, ow = l.deconv ? 2.0 * l.W : l.W;
     double b = ex->batch * ((double)l.H * l.W * l.real_cin * in_e + oh * ow * l.Cout * out_e) +
                9.0 * l.real_cin * l.Cout * w_e;
     // conv1_1 folded into conv1_2's launch: conv1_1's map is neither written nor read
-    if (ex->first2_variant >= 0 && &l == &ex->layers[0]) b -= ex->batch * oh * ow * l.Cout * out_e;
-    if (ex->first2_variant >= 0 && &l == &ex->layers[1]) b -= ex->batch * (double)l.H * l.W * l.real_cin * in_e;
-    if (l.name == "conv1_2" || l.name == "conv2_2" || l.name == "conv3_3")
+    if (ex->first2_variant >= 0 && &l == &ex->layers[CONV1_1]) b -= ex->batch * oh * ow * l.Cout * out_e;
+    if (ex->first2_variant >= 0 && &l == &ex->layers[CONV1_2]) b -= ex->batch * (double)l.H * l.W * l.real_cin * in_e;
+    if (l.pool >= 0)
         b += ex->batch * std::floor(oh / 2) * std::floor(ow / 2) * l.Cout * out_e;
     const double w_bytes = 9.0 * l.real_cin * l.Cout * w_e;
     return (b - w_bytes) * frac + w_bytes;
@@ -736,316 +626,82 @@ void plan_layer(Layer& l, int batch, int num_cus, bool allow_tail, std::vector<i
     l.tail.variant = best;
 }
 
-int run_pool(dodt_extractor* ex, int src, int dst) {
+int run_pool(const dodt_extractor* ex, const Pass& p, int src, int dst) {
     const Buffer& s = ex->buf[src];
     const Buffer& d = ex->buf[dst];
     const int planes = d.C / 8;
-    const long long total = (long long)ex->batch * planes * d.H * d.W * 2;
+    const long long total = (long long)p.frames * planes * d.H * d.W * 2;
     hipLaunchKernelGGL(maxpool2x2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       ex->ctx->stream, s.ptr, s.H, s.W, planes, (long long)s.frame_floats(),
-                       d.ptr, ex->batch);
+                       ex->ctx->stream, p.map[src], s.H, s.W, planes, (long long)s.frame_floats(),
+                       p.map[dst], p.frames);
     DODT_LAUNCH_CHECK();
     return DODT_OK;
 }
 
-// ---------------------------------------------------------------------------
-// input support: where a layer's outputs can depend on the input (dodt_extractor_set_input_support)
-// ---------------------------------------------------------------------------
-// An output whose receptive field holds only inputs that are zero in every frame (zero padding included) is a
-// function of the weights alone: a full forward writes it, and later forwards need not.
-struct Support {
-    int h = 0, w = 0;
-    std::vector<uint8_t> m;   // 1: may depend on the input
-    Support() = default;
-    Support(int h_, int w_) : h(h_), w(w_), m((size_t)h_ * w_, 0) {}
-    uint8_t& at(int y, int x) { return m[(size_t)y * w + x]; }
-    uint8_t at(int y, int x) const { return m[(size_t)y * w + x]; }
-};
-
-// the outputs of a 3x3 SAME conv (r = 1), or the margin of a transposed conv (r = 2)
-Support dilate(const Support& a, int r) {
-    Support t(a.h, a.w), o(a.h, a.w);
-    for (int y = 0; y < a.h; ++y)
-        for (int x = 0; x < a.w; ++x)
-            for (int d = -r; d <= r; ++d)
-                if (x + d >= 0 && x + d < a.w && a.at(y, x + d)) { t.at(y, x) = 1; break; }
-    for (int y = 0; y < a.h; ++y)
-        for (int x = 0; x < a.w; ++x)
-            for (int d = -r; d <= r; ++d)
-                if (y + d >= 0 && y + d < a.h && t.at(y + d, x)) { o.at(y, x) = 1; break; }
-    return o;
-}
-
-// VALID 2x2 max pool (odd sizes floored)
-Support pool2(const Support& a) {
-    Support o(a.h / 2, a.w / 2);
-    for (int y = 0; y < o.h; ++y)
-        for (int x = 0; x < o.w; ++x)
-            o.at(y, x) = a.at(2 * y, 2 * x) | a.at(2 * y, 2 * x + 1) | a.at(2 * y + 1, 2 * x) | a.at(2 * y + 1, 2 * x + 1);
-    return o;
-}
-
-// 3x3 stride-2 transposed conv: input i reaches outputs 2i .. 2i + 2 (or 2i - 1 .. 2i + 1 for the other padding
-// split); nearest 2x upsampling dilated by 2 covers both
-Support upconv2(const Support& a) {
-    Support u(2 * a.h, 2 * a.w);
-    for (int y = 0; y < u.h; ++y)
-        for (int x = 0; x < u.w; ++x) u.at(y, x) = a.at(y / 2, x / 2);
-    return dilate(u, 2);
-}
-
-// summed-area table: does a rectangle hold an input-dependent output?
-struct SupportSum {
-    int h = 0, w = 0;
-    std::vector<int> s;
-    explicit SupportSum(const Support& a) : h(a.h), w(a.w), s((size_t)(a.h + 1) * (a.w + 1), 0) {
-        for (int y = 0; y < h; ++y)
-            for (int x = 0; x < w; ++x)
-                s[(size_t)(y + 1) * (w + 1) + x + 1] = a.at(y, x) + s[(size_t)y * (w + 1) + x + 1] +
-                                                       s[(size_t)(y + 1) * (w + 1) + x] - s[(size_t)y * (w + 1) + x];
-    }
-    bool any(int y0, int y1, int x0, int x1) const {   // [y0, y1) x [x0, x1), clipped
-        y0 = std::max(y0, 0); x0 = std::max(x0, 0); y1 = std::min(y1, h); x1 = std::min(x1, w);
-        if (y0 >= y1 || x0 >= x1) return false;
-        return s[(size_t)y1 * (w + 1) + x1] - s[(size_t)y0 * (w + 1) + x1] - s[(size_t)y1 * (w + 1) + x0] +
-                   s[(size_t)y0 * (w + 1) + x0] > 0;
-    }
-};
-
-// Winograd F(4x4,3x3): an output's fp32 value depends on the whole 6 x 6 input tile of its 4 x 4 block (the
-// transforms are dense: taps outside its 3 x 3 field cancel exactly, not in rounding).  (F(2x2,3x3) has no such
-// reach: output 0 of a block never reads input 3, output 1 never input 0.)
-Support wino_blocks(const Support& a, int m) {
-    const SupportSum sum(a);
-    Support o(a.h, a.w);
-    for (int y0 = 0; y0 < a.h; y0 += m)
-        for (int x0 = 0; x0 < a.w; x0 += m)
-            if (sum.any(y0 - 1, y0 + m + 1, x0 - 1, x0 + m + 1))
-                for (int y = y0; y < std::min(y0 + m, a.h); ++y)
-                    for (int x = x0; x < std::min(x0 + m, a.w); ++x) o.at(y, x) = 1;
-    return o;
-}
-
-// ---------------------------------------------------------------------------
-// per-frame tables (frame_tables.h): three launches at the head of a forward
-// ---------------------------------------------------------------------------
-// the non-zero cells of the frames' input maps (NHWC, any channel) as bit masks: half a wave per word.  A cell that
-// holds only -0.0 counts as empty (the sign bit is masked off): every conv form starts its accumulators at +0.0 and
-// x w with x = -0.0 adds +-0.0, so its outputs are bit for bit those of +0.0, the value the skipped outputs were
-// computed from (tests/test_gpu_bev_skip_adversarial.py).  A denormal counts as non-zero.
-__global__ void __launch_bounds__(256)
-frame_support_kernel(const float* __restrict__ x, long long frame_stride, int H, int W, int C, uint32_t* __restrict__ bits) {
-    const int p = dodt::ft::pitch(W), words = H * p;
-    const int word = blockIdx.x * 8 + (threadIdx.x >> 5), frame = blockIdx.y;
-    const int y = word / p, cx = (word - y * p) * 32 + (threadIdx.x & 31);
-    bool nz = false;
-    if (word < words && cx < W) {
-        const uint2* c = reinterpret_cast<const uint2*>(x + (size_t)frame * frame_stride + ((size_t)y * W + cx) * C);
-        uint32_t acc = 0;
-        for (int k = 0; k < C / 2; ++k) {      // (C is even: dodt_extractor_create)
-            const uint2 v = c[k];
-            acc |= v.x | v.y;
-        }
-        nz = (acc & 0x7fffffffu) != 0;
-    }
-    const unsigned long long b = __ballot(nz);
-    if ((threadIdx.x & 31) == 0 && word < words)
-        bits[(size_t)frame * words + word] = (uint32_t)((threadIdx.x & 32) ? b >> 32 : b);
-}
-
-// one workgroup per frame walks the net's geometry on two masks in LDS and marks the items its frame reaches
-__global__ void __launch_bounds__(1024)
-frame_walk_kernel(const dodt::ft::Plan* __restrict__ pl, const uint32_t* __restrict__ bits) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t ft_lds[];
-    const int words = dodt::ft::level_words(pl->H, pl->W, 0);
-    uint32_t* a = ft_lds;
-    uint32_t* b = ft_lds + words;
-    const int frame = blockIdx.x;
-    for (int i = threadIdx.x; i < words; i += blockDim.x) a[i] = bits[(size_t)frame * words + i];
-    __syncthreads();
-    dodt::ft::walk(*pl, frame, a, b, (int)threadIdx.x, (int)blockDim.x, [] { __syncthreads(); });
-}
-
-// one workgroup per table: the items this forward runs, in the table's order (a prefix sum: the same table for the
-// same masks, whatever order the workgroups run in)
-__global__ void __launch_bounds__(256)
-frame_compact_kernel(const dodt::ft::Plan* __restrict__ pl, uint8_t* last_prev_main, uint8_t* last_prev_tail) {
-    __shared__ int scan[257];
-    const dodt::ft::Table t = pl->t[blockIdx.x];
-    if (!t.items) return;
-    const bool last = (int)blockIdx.x / 2 == dodt::ft::kLayers - 1;     // pyramid_fusion1: the output pair's set
-    uint8_t* prev = last ? ((blockIdx.x & 1) ? last_prev_tail : last_prev_main) : t.prev;
-    dodt::ft::compact(t, prev, scan, (int)threadIdx.x, (int)blockDim.x, [] { __syncthreads(); });
-}
+// one forward: d_x0 (or the X0 buffer where it is NULL) through the tables choose_tables picks
+int forward(dodt_extractor* ex, const float* d_in, const float* d_x0, float* d_feat_out, float* d_bottleneck_out,
+            bool timed);
 
 }  // namespace
 
-using dodt::ft::RestoreTable;
-using dodt::ft::RestorePlan;
-
-namespace {
-
-// Every table's restore list in one launch (ahead of conv1_1 on the extractor's stream): the outputs of an item that
-// the last forward into the same buffer reached and this one does not go back to the store's values.  Workgroups
-// stride over the lists end to end; one that finds nothing leaves at once.  last_on: pyramid_fusion1's list counts
-// (the output pair is one the layer remembers).
-__global__ void __launch_bounds__(256)
-frame_restore_kernel(const RestorePlan* __restrict__ pl, float* __restrict__ feat, float* __restrict__ bneck, int last_on) {
-    __shared__ int start[dodt::ft::kTables + 1];
-    if (threadIdx.x == 0) {
-        int sum = 0;
-        for (int k = 0; k < dodt::ft::kTables; ++k) {
-            start[k] = sum;
-            const bool on = pl->t[k].list && (k / 2 != dodt::ft::kLayers - 1 || last_on);
-            sum += on ? *pl->t[k].count : 0;
-        }
-        start[dodt::ft::kTables] = sum;
-    }
-    __syncthreads();
-    const int total = start[dodt::ft::kTables];
-    int k = 0;
-    for (int i = blockIdx.x; i < total; i += gridDim.x) {
-        while (i >= start[k + 1]) ++k;
-        dodt::ft::restore_item(*pl, pl->t[k], pl->t[k].list[i - start[k]], feat, bneck, (int)threadIdx.x, (int)blockDim.x);
-    }
-}
-
-void free_store(dodt_extractor* ex) {
-    for (int i = 0; i < NBUF; ++i) {
-        if (ex->store[i]) (void)hipFree(ex->store[i]);
-        ex->store[i] = nullptr;
-    }
-    if (ex->store_feat) (void)hipFree(ex->store_feat);
-    if (ex->store_bneck) (void)hipFree(ex->store_bneck);
-    if (ex->d_restore_plan) (void)hipFree(ex->d_restore_plan);
-    ex->store_feat = ex->store_bneck = nullptr;
-    ex->d_restore_plan = nullptr;
-    ex->store_valid = false;
-    ex->store_bytes = 0;
-}
-
-void free_frame_tables(dodt_extractor* ex) {
-    free_store(ex);
-    for (void* p : ex->frame_allocs) (void)hipFree(p);
-    ex->frame_allocs.clear();
-    for (Layer& l : ex->layers)
-        for (Launch* ln : {&l.main, &l.tail}) {
-            ln->d_run = nullptr;
-            ln->d_count = nullptr;
-        }
-    ex->frame_plan = dodt::ft::Plan();
-    ex->d_frame_plan = nullptr;
-    ex->d_frame_bits = nullptr;
-    ex->d_frame_counts = nullptr;
-    ex->out_slot.clear();
-    ex->frame_on = false;
-}
-
-// the builder's launches for this forward's input; slot: the output pair's item set of pyramid_fusion1
-int build_frame_tables(dodt_extractor* ex, int slot) {
-    const Buffer& x0 = ex->buf[X0];
-    const int words = dodt::ft::level_words(ex->H, ex->W, 0);
-    hipStream_t s = ex->ctx->stream;
-    hipLaunchKernelGGL(frame_support_kernel, dim3((unsigned)dodt::ceil_div(words, 8), (unsigned)ex->batch), dim3(256), 0, s,
-                       x0.ptr, (long long)x0.frame_floats(), ex->H, ex->W, x0.C, ex->d_frame_bits);
-    DODT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(frame_walk_kernel, dim3((unsigned)ex->batch), dim3(1024), (size_t)words * 8, s,
-                       ex->d_frame_plan, ex->d_frame_bits);
-    DODT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(frame_compact_kernel, dim3(dodt::ft::kTables), dim3(256), 0, s, ex->d_frame_plan,
-                       ex->out_prev[slot][0], ex->out_prev[slot][1]);
-    DODT_LAUNCH_CHECK();
-    return DODT_OK;
-}
-
-// the per-frame counts of the last forward (waits for the stream); false: per-frame tables are off
-bool read_frame_counts(const dodt_extractor* ex, int (&counts)[2 * dodt::ft::kTables]) {
-    if (!ex->frame_on) return false;
-    if (hipStreamSynchronize(ex->ctx->stream) != hipSuccess) return false;
-    return hipMemcpy(counts, ex->d_frame_counts, sizeof(counts), hipMemcpyDeviceToHost) == hipSuccess;
-}
-
-// the buffer a layer's epilogue pools into (conv1_2, conv2_2, conv3_3 where the tiling allows), or -1
-int fused_pool_buffer(const Layer& l) {
+int dodt::fused_pool_buffer(const Layer& l) {
     static const bool no_fuse = getenv("DODT_CONV_NO_POOL_FUSE") != nullptr;
-    if (no_fuse || !layer_can_pool(l)) return -1;
-    return l.name == "conv1_2" ? P1 : l.name == "conv2_2" ? P2 : l.name == "conv3_3" ? P3 : -1;
+    return no_fuse || !layer_can_pool(l) ? -1 : l.pool;
 }
 
-// pyramid_fusion1 computes the 1x1 bottleneck in its epilogue (32-channel tiles)
-bool bneck_fused(const Layer& last) {
+bool dodt::bneck_fused(const Layer& last) {
     return variants()[last.main.variant].BN == 32 && (last.tail.n_items == 0 || variants()[last.tail.variant].BN == 32);
 }
 
-// The share of a layer's work that is counted: the steady state's (steady_frac), or with per-frame tables what the
-// last finished forward ran of a layer that took them (waits for the stream).
-struct WorkShare {
-    int counts[2 * dodt::ft::kTables];   // computed items per table, then restored items per table
-    bool have;
-    explicit WorkShare(const dodt_extractor* ex) : have(read_frame_counts(ex, counts)) {}
-    bool per_frame(const dodt_extractor* ex, size_t li) const {
-        return have && li < ex->skipping.size() && ex->skipping[li] == 2;
+int dodt::run_layers(const dodt_extractor* ex, const Pass& p, float* d_feat_out, float* d_bottleneck_out) {
+    hipStream_t s = ex->ctx->stream;
+    int rc;
+    const std::vector<Layer>& ls = ex->layers;
+    if (ex->bf16)   // there is no stand-alone pool kernel for bf16 maps
+        for (int id : {CONV1_2, CONV2_2, CONV3_3})
+            DODT_REQUIRE(fused_pool_buffer(ls[id]) >= 0, "bf16 extractor: layer %s cannot pool in its epilogue",
+                         ls[id].name.c_str());
+    for (int id = ex->first2_variant >= 0 ? CONV1_2 : CONV1_1; id <= CONV4_3; ++id) {
+        const Layer& l = ls[id];
+        // conv1_1 folded into conv1_2's launch; a conv that a 2x2 max pool follows pools in its epilogue when its
+        // tiling allows
+        const Layer* folded = id == CONV1_2 && ex->first2_variant >= 0 ? &ls[CONV1_1] : nullptr;
+        const int pool_dst = folded ? l.pool : fused_pool_buffer(l);
+        if ((rc = run_layer(ex, p, l, nullptr, 0, 0, nullptr, pool_dst, folded))) return rc;
+        if (l.pool >= 0 && pool_dst < 0 && (rc = run_pool(ex, p, l.dst, l.pool))) return rc;
     }
-    int items(const dodt_extractor* ex, size_t li, int j) const {
-        const Layer& l = ex->layers[li];
-        return (j ? l.tail : l.main).d_count ? counts[2 * li + j] : 0;
+    if (ex->kind == DODT_EXTRACTOR_VGG) {
+        // bev_vgg.py:102-112 / img_vgg.py:104-114: 4x bilinear upsampling of conv4_3, and the
+        // 256 -> 1 bottleneck of the RPN (rpn_model.py:251-267) on the upsampled map
+        const Buffer& c4 = ex->buf[C4C];
+        const long long n_pix = (long long)p.frames * ex->out_h * ex->out_w;
+        constexpr int kLpp = 64;   // 256 channels / 4
+        hipLaunchKernelGGL(upsample_bilinear_cb8_kernel<kLpp>,
+                           dim3((unsigned)((n_pix * kLpp + 255) / 256)), dim3(256), 0, s, p.map[C4C],
+                           c4.H, c4.W, (long long)c4.frame_floats(), ex->out_h, ex->out_w,
+                           p.frames, d_feat_out, ex->d_bneck_w, ex->bneck_scale, ex->bneck_shift,
+                           d_bottleneck_out);
+        DODT_LAUNCH_CHECK();
+        return DODT_OK;
     }
-    // the items of the launch whose outputs the forward copied back from the store (none where a full table ran)
-    int restored(const dodt_extractor* ex, size_t li, int j) const {
-        const Layer& l = ex->layers[li];
-        return per_frame(ex, li) && ex->restoring && (j ? l.tail : l.main).d_count ? counts[dodt::ft::kTables + 2 * li + j] : 0;
+    for (int id = UPCONV3; id < FUSION1; ++id)
+        if ((rc = run_layer(ex, p, ls[id], nullptr, 0, 0))) return rc;
+    // last layer writes straight into the caller's buffer, pad rows sliced off
+    // ... and, fused into its epilogue, the 1x1 bottleneck (dt_rpn_model.py:298-322)
+    const Layer& last = ls[FUSION1];
+    const bool fuse = d_bottleneck_out && bneck_fused(last);
+    if ((rc = run_layer(ex, p, last, d_feat_out, ex->pad_top, ex->in_h,
+                        fuse ? d_bottleneck_out : nullptr)))
+        return rc;
+    if (d_bottleneck_out && !fuse) {
+        const long long n_pix = (long long)p.frames * ex->in_h * ex->in_w;
+        hipLaunchKernelGGL(bottleneck32_kernel, dim3((unsigned)((n_pix * 8 + 255) / 256)),
+                           dim3(256), 0, s, d_feat_out, n_pix, ex->d_bneck_w, ex->bneck_scale,
+                           ex->bneck_shift, d_bottleneck_out);
+        DODT_LAUNCH_CHECK();
     }
-    // HBM bytes of those copies, read from the store and written: the item's outputs, their pooled copy where the
-    // pool is fused, the bottleneck cells of a pyramid_fusion1 tile where the bottleneck is
-    double restore_bytes(const dodt_extractor* ex, const Layer& l) const {
-        const size_t li = &l - ex->layers.data();
-        const bool pooled = fused_pool_buffer(l) >= 0;
-        const bool bneck = &l == &ex->layers.back() && ex->bneck_loaded && bneck_fused(l);
-        double b = 0.0;
-        int j = 0;
-        for (const Launch* ln : {&l.main, &l.tail}) {
-            const int jj = j++;
-            if (ln->h_items.empty()) continue;
-            const KernelVariant& v = variants()[ln->variant];
-            const double px = (l.deconv ? 4.0 : 1.0) * v.TH * v.TW;
-            b += 2.0 * 4.0 * (px * v.BN * (pooled ? 1.25 : 1.0) + (bneck ? px : 0.0)) * restored(ex, li, jj);
-        }
-        return b;
-    }
-    double of(const dodt_extractor* ex, const Layer& l) const {
-        const size_t li = &l - ex->layers.data();
-        if (!per_frame(ex, li)) return steady_frac(ex, l);
-        double kept = 0.0, all = 0.0;
-        int j = 0;
-        for (const Launch* ln : {&l.main, &l.tail}) {
-            const int jj = j++;
-            if (ln->h_items.empty()) continue;
-            const KernelVariant& v = variants()[ln->variant];
-            const double units = (double)v.TH * v.TW * v.BN;
-            kept += units * items(ex, li, jj);
-            all += units * ln->h_items.size();
-        }
-        return all > 0 ? kept / all : 1.0;
-    }
-};
-
-void free_skip_tables(dodt_extractor* ex) {
-    free_frame_tables(ex);     // (they filter the skip tables)
-    for (Layer& l : ex->layers) {
-        for (Launch* ln : {&l.main, &l.tail}) {
-            if (ln->d_skip) (void)hipFree(ln->d_skip);
-            ln->d_skip = nullptr;
-            ln->n_skip = -1;
-        }
-        l.skip_frac = 1.0;
-    }
-    ex->skip_on = false;
+    return DODT_OK;
 }
-
-int run_layers(dodt_extractor* ex, float* d_feat_out, float* d_bottleneck_out);
-int take_store(dodt_extractor* ex);
-
-}  // namespace
 
 extern "C" {
 
@@ -1123,32 +779,41 @@ int dodt_extractor_create(dodt_ctx* ctx, int kind, int in_h, int in_w, int in_c,
     DODT_HIP_CHECK(hipMemsetAsync(ex->buf[X0].ptr, 0,
                                   ex->buf[X0].frame_floats() * batch * sizeof(float), ctx->stream));
 
-    auto add = [&](const char* name, bool deconv, int h, int w, int cin, int cout, int src,
-                   int src_coff, int dst, int dst_coff) {
+    // (LayerId names the layers by their place in this order)
+    bool in_order = true;
+    auto add = [&](LayerId id, const char* name, bool deconv, int h, int w, int cin, int cout, int src,
+                   int src_coff, int dst, int dst_coff, int pool = -1) {
+        in_order = in_order && id == (int)ex->layers.size() && deconv == ft::transposed(id);
         Layer l;
+        l.pool = pool;
         l.name = name; l.deconv = deconv; l.H = h; l.W = w; l.Cin = cin; l.Cout = cout;
         l.src = src; l.src_coff = src_coff; l.dst = dst; l.dst_coff = dst_coff;
         l.variant = pick_variant(deconv, h, w, cin, cout, bf16, ex->parts, batch, ctx->num_cus);
         l.real_cin = cin;
         ex->layers.push_back(l);
     };
-    add("conv1_1", false, H, W, in_c, 32, X0, 0, C1A, 0);
-    add("conv1_2", false, H, W, 32, 32, C1A, 0, CAT1, 0);
-    add("conv2_1", false, H2, W2, 32, 64, P1, 0, C2A, 0);
-    add("conv2_2", false, H2, W2, 64, 64, C2A, 0, CAT2, 0);
-    add("conv3_1", false, H4, W4, 64, 128, P2, 0, C3A, 0);
-    add("conv3_2", false, H4, W4, 128, 128, C3A, 0, C3B, 0);
-    add("conv3_3", false, H4, W4, 128, 128, C3B, 0, CAT3, 0);
-    add("conv4_1", false, H8, W8, 128, 256, P3, 0, C4A, 0);
-    add("conv4_2", false, H8, W8, 256, 256, C4A, 0, C4B, 0);
-    add("conv4_3", false, H8, W8, 256, 256, C4B, 0, C4C, 0);
+    add(CONV1_1, "conv1_1", false, H, W, in_c, 32, X0, 0, C1A, 0);
+    add(CONV1_2, "conv1_2", false, H, W, 32, 32, C1A, 0, CAT1, 0, P1);
+    add(CONV2_1, "conv2_1", false, H2, W2, 32, 64, P1, 0, C2A, 0);
+    add(CONV2_2, "conv2_2", false, H2, W2, 64, 64, C2A, 0, CAT2, 0, P2);
+    add(CONV3_1, "conv3_1", false, H4, W4, 64, 128, P2, 0, C3A, 0);
+    add(CONV3_2, "conv3_2", false, H4, W4, 128, 128, C3A, 0, C3B, 0);
+    add(CONV3_3, "conv3_3", false, H4, W4, 128, 128, C3B, 0, CAT3, 0, P3);
+    add(CONV4_1, "conv4_1", false, H8, W8, 128, 256, P3, 0, C4A, 0);
+    add(CONV4_2, "conv4_2", false, H8, W8, 256, 256, C4A, 0, C4B, 0);
+    add(CONV4_3, "conv4_3", false, H8, W8, 256, 256, C4B, 0, C4C, 0);
     if (!plain) {
-        add("upconv3", true, H8, W8, 256, 128, C4C, 0, CAT3, 128);
-        add("pyramid_fusion3", false, H4, W4, 256, 64, CAT3, 0, F3, 0);
-        add("upconv2", true, H4, W4, 64, 64, F3, 0, CAT2, 64);
-        add("pyramid_fusion2", false, H2, W2, 128, 32, CAT2, 0, F2, 0);
-        add("upconv1", true, H2, W2, 32, 32, F2, 0, CAT1, 32);
-        add("pyramid_fusion1", false, H, W, 64, 32, CAT1, 0, F1, 0);
+        add(UPCONV3, "upconv3", true, H8, W8, 256, 128, C4C, 0, CAT3, 128);
+        add(FUSION3, "pyramid_fusion3", false, H4, W4, 256, 64, CAT3, 0, F3, 0);
+        add(UPCONV2, "upconv2", true, H4, W4, 64, 64, F3, 0, CAT2, 64);
+        add(FUSION2, "pyramid_fusion2", false, H2, W2, 128, 32, CAT2, 0, F2, 0);
+        add(UPCONV1, "upconv1", true, H2, W2, 32, 32, F2, 0, CAT1, 32);
+        add(FUSION1, "pyramid_fusion1", false, H, W, 64, 32, CAT1, 0, F1, 0);
+    }
+    if (!in_order) {
+        dodt::set_error("dodt_extractor_create: the layers are not in LayerId's order");
+        dodt_extractor_destroy(ex);
+        return DODT_ERR_INVALID;
     }
     for (const Layer& l : ex->layers) {
         if (l.variant < 0) {
@@ -1176,8 +841,8 @@ int dodt_extractor_create(dodt_ctx* ctx, int kind, int in_h, int in_w, int in_c,
         // bf16 conv path: conv1_1 folded into conv1_2's launch when conv1_2 runs on the streaming kernel (same tiles, same
         // weight blocking) and the input rows are whole 16-byte slots (DODT_CONV_BF16_FIRST2=0: two launches)
         static const bool first2 = !(getenv("DODT_CONV_BF16_FIRST2") && atoi(getenv("DODT_CONV_BF16_FIRST2")) == 0);
-        const Layer& c11 = ex->layers[0];
-        const Layer& c12 = ex->layers[1];
+        const Layer& c11 = ex->layers[CONV1_1];
+        const Layer& c12 = ex->layers[CONV1_2];
         const auto& vs = variants();
         if (first2 && bf16 && ex->parts == 1 && vs[c12.variant].stream_nch == 2 && c12.tail.n_items == 0 &&
             c11.Cout == 32 && c11.src_coff == 0 && ex->buf[X0].C == c11.Cin && (W * c11.Cin * 4) % 16 == 0 &&
@@ -1208,7 +873,7 @@ int dodt_extractor_create(dodt_ctx* ctx, int kind, int in_h, int in_w, int in_c,
 int dodt_extractor_destroy(dodt_extractor* ex) {
     if (!ex) return DODT_OK;
     if (ex->ctx) (void)hipStreamSynchronize(ex->ctx->stream);
-    if (ex->own_x0) ex->buf[X0].ptr = ex->own_x0;      // (never free a caller's input buffer)
+    if (ex->own_x0) ex->buf[X0].ptr = ex->own_x0;      // (dodt_extractor_set_input: never free a caller's input buffer)
     free_frame_tables(ex);
     for (int i = 0; i < NBUF; ++i)
         if (ex->buf[i].ptr) (void)hipFree(ex->buf[i].ptr);
@@ -1238,17 +903,16 @@ int dodt_extractor_set_layer(dodt_extractor* ex, const char* name, const float* 
                              const float* var) {
     DODT_REQUIRE(ex && name && w && beta && mean && var, "dodt_extractor_set_layer: NULL argument");
     hipStream_t s = ex->ctx->stream;
+    int rc;
     // new weights: the input-independent outputs the skip tables leave alone change (the next forward primes)
     ex->primed = false;
-    ex->primed_out.clear();
+    forget_pairs(ex);
     ex->store_valid = false;
     if (std::strcmp(name, "bottleneck") == 0) {
         const int fc = ex->out_c;   // 32 (pyramid) or 256 (plain VGG: rpn_model.py:251-267)
         DODT_REQUIRE(kh == 1 && kw == 1 && c_a == fc && c_b == 1,
                      "bottleneck must be (1,1,%d,1), got (%d,%d,%d,%d)", fc, kh, kw, c_a, c_b);
-        if (!ex->d_bneck_w) DODT_HIP_CHECK(hipMalloc(&ex->d_bneck_w, fc * sizeof(float)));
-        DODT_HIP_CHECK(hipMemcpyAsync(ex->d_bneck_w, w, fc * sizeof(float), hipMemcpyHostToDevice, s));
-        DODT_HIP_CHECK(hipStreamSynchronize(s));
+        if ((rc = upload(&ex->d_bneck_w, std::vector<float>(w, w + fc), s))) return rc;
         const float inv = 1.0f / std::sqrt(var[0] + 0.001f);
         ex->bneck_scale = inv;
         ex->bneck_shift = beta[0] - mean[0] * inv;
@@ -1264,193 +928,28 @@ int dodt_extractor_set_layer(dodt_extractor* ex, const char* name, const float* 
     DODT_REQUIRE(cout == l.Cout && cin <= l.Cin && (cin == l.Cin || li == 0),
                  "layer %s: expected %d->%d channels, got %d->%d", name, l.Cin, l.Cout, cin, cout);
     for (Launch* ln : {&l.main, &l.tail}) {
-    if (ln->variant < 0) continue;
-    if (ln == &l.tail && variants()[l.tail.variant].BN == variants()[l.main.variant].BN) {
-        ln->d_w = nullptr;   // same blocking: share the main launch's copy (set below)
-        continue;
+        if (ln->variant < 0) continue;
+        if (ln == &l.tail && variants()[l.tail.variant].BN == variants()[l.main.variant].BN) {
+            ln->d_w = nullptr;   // same blocking: run_launch takes the main launch's copy
+            continue;
+        }
+        const KernelVariant& v = variants()[ln->variant];
+        const WeightTile t{v.BN, v.CK, v.bf16, v.small_cin, v.parts};
+        const std::vector<float> blocked = v.deconv_dma               ? block_deconv_dma(t, l, w, cin, cout)
+                                           : v.wino && v.wino_m == 4 ? block_wino43(t, l, w, cin, cout)
+                                           : v.wino                  ? block_wino22(t, l, w, cin, cout)
+                                                                     : block_direct(t, l, w, cin, cout);
+        if ((rc = upload(&ln->d_w, blocked, s))) return rc;
     }
-    const KernelVariant& v = variants()[ln->variant];
-    const int nchunks = l.Cin / v.CK;
-    if (v.deconv_dma) {
-        // transposed conv, TF layout (kh, kw, Cout, Cin): blocked [n-tile][chunk][tap][g = c / 2][t]
-        // [channel block][c & 1]: a lane (t, g) reads 16 bytes = its channel pair for both blocks
-        // (bf16: the same bytes hold 16 channels per chunk, [g = c / 4] ... [c & 3] as bf16)
-        const int ncb = v.BN / 16;
-        const size_t chunk_floats = (size_t)(9 * 8 * v.BN + 255) / 256 * 256;     // whole 1 KB pieces
-        std::vector<float> u((size_t)(l.Cout / v.BN) * nchunks * chunk_floats, 0.0f);
-        uint16_t* u16 = reinterpret_cast<uint16_t*>(u.data());
-        for (int tap = 0; tap < 9; ++tap)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int co = 0; co < cout; ++co) {
-                    const float val = w[((size_t)tap * cout + co) * cin + ci];
-                    const int nt = co / v.BN, n = co % v.BN, cb = n / 16, t = n % 16;
-                    if (v.bf16) {
-                        const int ch = ci / 16, c = ci % 16;
-                        u16[(((size_t)nt * nchunks + ch) * chunk_floats) * 2 +
-                            ((((size_t)tap * 4 + c / 4) * 16 + t) * ncb + cb) * 4 + (c & 3)] = dodt::float_to_bf16(val);
-                    } else {
-                        const int ch = ci / 8, c = ci % 8;
-                        u[((size_t)nt * nchunks + ch) * chunk_floats +
-                          ((((size_t)tap * 4 + c / 2) * 16 + t) * ncb + cb) * 2 + (c & 1)] = val;
-                    }
-                }
-        if (!ln->d_w) DODT_HIP_CHECK(hipMalloc(&ln->d_w, u.size() * sizeof(float)));
-        DODT_HIP_CHECK(hipMemcpyAsync(ln->d_w, u.data(), u.size() * sizeof(float),
-                                      hipMemcpyHostToDevice, s));
-        DODT_HIP_CHECK(hipStreamSynchronize(s));
-        continue;
-    }
-    if (v.wino && v.wino_m == 4) {
-        // F(4x4,3x3) filter transform U = G g G^T (6x6 points; float64 on the host, rounded once),
-        // blocked [n-tile][chunk][xi / 2][g = c / 2][cb][t][xi & 1][c & 1]: a lane (t, g) of channel
-        // block cb reads 16 bytes = its channel pair for two points
-        // points 0, +-2/3, +-3/2, infinity (wino43_kernel.h): G[j][k] = p_j^k / prod_{l != j} (p_j - p_l)
-        static const std::array<std::array<double, 3>, 6> G = [] {
-            const double p[5] = {0.0, 2.0 / 3.0, -2.0 / 3.0, 1.5, -1.5};
-            std::array<std::array<double, 3>, 6> g{};
-            for (int j = 0; j < 5; ++j) {
-                double n = 1.0;
-                for (int l = 0; l < 5; ++l)
-                    if (l != j) n *= p[j] - p[l];
-                g[j] = {1.0 / n, p[j] / n, p[j] * p[j] / n};
-            }
-            g[5] = {0.0, 0.0, 1.0};
-            return g;
-        }();
-        std::vector<float> u((size_t)36 * l.Cin * l.Cout, 0.0f);
-        for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < cout; ++co) {
-                double gk[3][3], tmp[6][3];
-                for (int ky = 0; ky < 3; ++ky)
-                    for (int kx = 0; kx < 3; ++kx)
-                        gk[ky][kx] = w[((size_t)(ky * 3 + kx) * cin + ci) * cout + co];
-                for (int i = 0; i < 6; ++i)
-                    for (int kx = 0; kx < 3; ++kx)
-                        tmp[i][kx] = G[i][0] * gk[0][kx] + G[i][1] * gk[1][kx] + G[i][2] * gk[2][kx];
-                const int nt = co / v.BN, n = co % v.BN, ch = ci / 8, c = ci % 8;
-                const int cb = n / 16, t = n % 16;
-                for (int i = 0; i < 6; ++i)
-                    for (int j = 0; j < 6; ++j) {
-                        const double val = tmp[i][0] * G[j][0] + tmp[i][1] * G[j][1] + tmp[i][2] * G[j][2];
-                        const int xi = i * 6 + j;
-                        u[(((((((size_t)nt * nchunks + ch) * 18 + xi / 2) * 4 + c / 2) * 2 + cb) * 16 + t) * 2 +
-                           (xi & 1)) * 2 + (c & 1)] = (float)val;
-                    }
-            }
-        if (!ln->d_w) DODT_HIP_CHECK(hipMalloc(&ln->d_w, u.size() * sizeof(float)));
-        DODT_HIP_CHECK(hipMemcpyAsync(ln->d_w, u.data(), u.size() * sizeof(float),
-                                      hipMemcpyHostToDevice, s));
-        DODT_HIP_CHECK(hipStreamSynchronize(s));
-        continue;
-    }
-    if (v.wino) {
-        // Winograd filter transform U = G g G^T (float64 on the host, rounded once to fp32),
-        // G = [[1,0,0],[1/2,1/2,1/2],[1/2,-1/2,1/2],[0,0,1]]; blocked like the direct kernel's
-        // weights with the 16 points in place of the 9 taps: [n-tile][chunk][xi][h][n][4]
-        static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-        std::vector<float> u((size_t)16 * l.Cin * l.Cout, 0.0f);
-        for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < cout; ++co) {
-                double gk[3][3], tmp[4][3];
-                for (int ky = 0; ky < 3; ++ky)
-                    for (int kx = 0; kx < 3; ++kx)
-                        gk[ky][kx] = w[((size_t)(ky * 3 + kx) * cin + ci) * cout + co];
-                for (int i = 0; i < 4; ++i)
-                    for (int kx = 0; kx < 3; ++kx)
-                        tmp[i][kx] = G[i][0] * gk[0][kx] + G[i][1] * gk[1][kx] + G[i][2] * gk[2][kx];
-                // [n-tile][chunk][xi][g = c/2][cb pair][t][cb & 1][k = c%2]: a lane (t, g) of the
-                // kernel reads 16 bytes = its (2g, 2g+1) channel pair for two 16-channel blocks
-                const int nt = co / v.BN, n = co % v.BN, ch = ci / 8, c = ci % 8;
-                const int cb = n / 16, t = n % 16, cbp = v.BN / 32;
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 4; ++j) {
-                        const double val = tmp[i][0] * G[j][0] + tmp[i][1] * G[j][1] + tmp[i][2] * G[j][2];
-                        u[((((((size_t)nt * nchunks + ch) * 16 + (i * 4 + j)) * 4 + c / 2) * cbp + cb / 2) * 16 + t) * 4 +
-                          (cb % 2) * 2 + c % 2] = (float)val;
-                    }
-            }
-        if (!ln->d_w) DODT_HIP_CHECK(hipMalloc(&ln->d_w, u.size() * sizeof(float)));
-        DODT_HIP_CHECK(hipMemcpyAsync(ln->d_w, u.data(), u.size() * sizeof(float),
-                                      hipMemcpyHostToDevice, s));
-        DODT_HIP_CHECK(hipStreamSynchronize(s));
-        continue;
-    }
-    // fp32 kernels: floats; bf16 MFMA kernels: bf16 pairs packed in the same array (half of it)
-    std::vector<float> blocked((size_t)9 * l.Cin * l.Cout, 0.0f);
-    uint16_t* blocked16 = reinterpret_cast<uint16_t*>(blocked.data());
-    const bool w16 = v.bf16 && !v.small_cin;
-    for (int tap = 0; tap < 9; ++tap)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int co = 0; co < cout; ++co) {
-                const float val = l.deconv ? w[((size_t)tap * cout + co) * cin + ci]
-                                           : w[((size_t)tap * cin + ci) * cout + co];
-                int n = co % v.BN;
-                if (v.bf16) {
-                    // MFMA row that delivers channel co (conv_kernels.h group_channel<PERM>):
-                    // channel 16a + 8lh + 4b + k  <-  row 8(2a + b) + 4lh + k
-                    const int c32 = co % 32, a2 = c32 >> 4, lh = (c32 >> 3) & 1, b2 = (c32 >> 2) & 1;
-                    n = (n / 32) * 32 + 8 * (2 * a2 + b2) + 4 * lh + (c32 & 3);
-                }
-                const int nt = co / v.BN, ch = ci / v.CK, c = ci % v.CK;
-                if (v.small_cin) {   // [tap][c][n]
-                    blocked[((size_t)tap * v.CK + c) * v.BN + n] = val;
-                } else if (!w16) {   // [n_tile][chunk][tap][h = c/4][n][s = c%4]
-                    blocked[(((((size_t)nt * nchunks + ch) * 9 + tap) * 2 + c / 4) * v.BN + n) * 4 +
-                            c % 4] = val;
-                } else {   // [n_tile][chunk16][part][tap][h = c/8][n][j = c%8] bf16
-                    const uint16_t hi = dodt::float_to_bf16(val);
-                    const size_t base = ((size_t)nt * nchunks + ch) * v.parts;
-                    const size_t in = ((size_t)(tap * 2 + c / 8) * v.BN + n) * 8 + c % 8;
-                    blocked16[(base + 0) * 9 * 2 * v.BN * 8 + in] = hi;
-                    if (v.parts == 2)    // lo = bf16(w - hi): w = hi + lo to 16 mantissa bits
-                        blocked16[(base + 1) * 9 * 2 * v.BN * 8 + in] =
-                            dodt::float_to_bf16(val - dodt::bf16_to_float(hi));
-                }
-            }
-    if (!ln->d_w) DODT_HIP_CHECK(hipMalloc(&ln->d_w, blocked.size() * sizeof(float)));
-    DODT_HIP_CHECK(hipMemcpyAsync(ln->d_w, blocked.data(), blocked.size() * sizeof(float),
-                                  hipMemcpyHostToDevice, s));
-    DODT_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    if (li == 0 && ex->bf16 && ex->parts == 1 && l.Cout == 32 && (l.Cin == 6 || l.Cin == 4)) {
-        // conv1_1 for conv3x3_bf16_first2_kernel: A fragments [K = 16 step][hi, lo][lane half][32 MFMA rows][8 bf16];
-        // a lane half's eight K slots are one tap's six channels + two zeros (Cin 6: taps 2 s + lh) or two taps' four
-        // channels (Cin 4: taps 4 s + 2 lh, + 1); w = hi + lo to 16 mantissa bits
-        const int steps = l.Cin == 6 ? 5 : 3;
-        std::vector<uint16_t> frag((size_t)steps * 2 * 2 * 32 * 8, 0);
-        for (int st = 0; st < steps; ++st)
-            for (int lh = 0; lh < 2; ++lh)
-                for (int row = 0; row < 32; ++row) {
-                    // channel of MFMA row 8 (2 a + b) + 4 lh' + k: 16 a + 8 lh' + 4 b + k (group_channel<true>)
-                    const int g = row >> 3, lho = (row >> 2) & 1, co = 16 * (g >> 1) + 8 * lho + 4 * (g & 1) + (row & 3);
-                    for (int j = 0; j < 8; ++j) {
-                        const int tap = l.Cin == 6 ? 2 * st + lh : 4 * st + 2 * lh + (j >> 2);
-                        const int ci = l.Cin == 6 ? j : (j & 3);
-                        if (tap >= 9 || ci >= cin) continue;
-                        const float val = w[((size_t)tap * cin + ci) * cout + co];
-                        const uint16_t hi = dodt::float_to_bf16(val);
-                        const size_t at = ((((size_t)st * 2 + 0) * 2 + lh) * 32 + row) * 8 + j;
-                        frag[at] = hi;
-                        frag[at + 2 * 32 * 8] = dodt::float_to_bf16(val - dodt::bf16_to_float(hi));
-                    }
-                }
-        if (!l.d_first_w) DODT_HIP_CHECK(hipMalloc(&l.d_first_w, frag.size() * sizeof(uint16_t)));
-        DODT_HIP_CHECK(hipMemcpyAsync(l.d_first_w, frag.data(), frag.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-        DODT_HIP_CHECK(hipStreamSynchronize(s));
-    }
+    if (li == 0 && ex->bf16 && ex->parts == 1 && l.Cout == 32 && (l.Cin == 6 || l.Cin == 4))
+        if ((rc = upload(reinterpret_cast<uint16_t**>(&l.d_first_w), pack_first2(l, w, cin, cout), s))) return rc;
     std::vector<float> scale(l.Cout), shift(l.Cout);
     for (int co = 0; co < l.Cout; ++co) {
         const float inv = 1.0f / std::sqrt(var[co] + 0.001f);
         scale[co] = inv;
         shift[co] = beta[co] - mean[co] * inv;
     }
-    if (!l.d_scale) DODT_HIP_CHECK(hipMalloc(&l.d_scale, l.Cout * sizeof(float)));
-    if (!l.d_shift) DODT_HIP_CHECK(hipMalloc(&l.d_shift, l.Cout * sizeof(float)));
-    DODT_HIP_CHECK(hipMemcpyAsync(l.d_scale, scale.data(), l.Cout * sizeof(float),
-                                  hipMemcpyHostToDevice, s));
-    DODT_HIP_CHECK(hipMemcpyAsync(l.d_shift, shift.data(), l.Cout * sizeof(float),
-                                  hipMemcpyHostToDevice, s));
-    DODT_HIP_CHECK(hipStreamSynchronize(s));
+    if ((rc = upload(&l.d_scale, scale, s)) || (rc = upload(&l.d_shift, shift, s))) return rc;
     l.loaded = true;
     l.real_cin = cin;
     return DODT_OK;
@@ -1466,6 +965,29 @@ int dodt_extractor_input(dodt_extractor* ex, float** d_ptr, long long* frame_str
 
 int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_out,
                            float* d_bottleneck_out) {
+    return forward(ex, d_in, nullptr, d_feat_out, d_bottleneck_out, false);
+}
+
+int dodt_extractor_forward_padded(dodt_extractor* ex, const float* d_x0, float* d_feat_out,
+                                  float* d_bottleneck_out) {
+    DODT_REQUIRE(ex && d_x0 && d_feat_out, "dodt_extractor_forward_padded: NULL argument");
+    // the first layer reads the caller's buffer in place of the extractor's own input buffer
+    return forward(ex, nullptr, d_x0, d_feat_out, d_bottleneck_out, false);
+}
+
+int dodt_extractor_set_input(dodt_extractor* ex, const float* d_x0) {
+    DODT_REQUIRE(ex, "dodt_extractor_set_input: extractor is NULL");
+    if (!ex->own_x0) ex->own_x0 = ex->buf[X0].ptr;
+    ex->buf[X0].ptr = d_x0 ? const_cast<float*>(d_x0) : ex->own_x0;
+    return DODT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int forward(dodt_extractor* ex, const float* d_in, const float* d_x0, float* d_feat_out, float* d_bottleneck_out,
+            bool timed) {
     DODT_REQUIRE(ex && d_feat_out, "dodt_extractor_forward: NULL argument");
     for (const Layer& l : ex->layers)
         DODT_REQUIRE(l.loaded, "dodt_extractor_forward: weights of layer %s not set",
@@ -1473,8 +995,13 @@ int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_
     DODT_REQUIRE(!d_bottleneck_out || ex->bneck_loaded,
                  "dodt_extractor_forward: bottleneck weights not set");
     hipStream_t s = ex->ctx->stream;
+    Pass p;
+    for (int i = 0; i < NBUF; ++i) p.map[i] = ex->buf[i].ptr;
+    if (d_x0) p.map[X0] = const_cast<float*>(d_x0);
+    p.frames = ex->batch;
+    p.timed = timed;
     const Buffer& x0 = ex->buf[X0];
-    float* own_in = x0.ptr + (size_t)ex->pad_top * x0.W * x0.C;
+    float* own_in = p.map[X0] + (size_t)ex->pad_top * x0.W * x0.C;
     if (d_in && d_in != own_in) {
         const long long n4 = (long long)ex->in_h * ex->in_w * ex->in_c / 4;
         DODT_REQUIRE(((long long)ex->in_h * ex->in_w * ex->in_c) % 4 == 0, "input not float4-sized");
@@ -1490,511 +1017,24 @@ int dodt_extractor_forward(dodt_extractor* ex, const float* d_in, float* d_feat_
     // skip tables once a full forward has primed the buffers; pyramid_fusion1 writes the caller's buffers, so it
     // primes every output pair of its own
     const bool skip = ex->skip_on && ex->primed;
-    bool last_skip = false;
-    size_t pair = 0;
-    while (pair < ex->primed_out.size() &&
-           !(ex->primed_out[pair].first == d_feat_out && ex->primed_out[pair].second == d_bottleneck_out))
-        ++pair;
-    const bool known_pair = pair < ex->primed_out.size();
-    last_skip = skip && known_pair;
-    ex->skipping.assign(ex->layers.size(), skip ? (ex->frame_on ? 2 : 1) : 0);
-    if (ex->kind == DODT_EXTRACTOR_VGG_PYR)
-        ex->skipping[find_layer(ex, "pyramid_fusion1")] = last_skip ? (ex->frame_on ? 2 : 1) : 0;
+    const int known = find_pair(ex, d_feat_out, d_bottleneck_out);
+    const bool last_skip = skip && known >= 0;
+    choose_tables(ex, skip, last_skip, p);
+    // (per-frame tables: a new pair takes the item set of the pair it evicts, or a free one)
+    const int slot = known >= 0 ? ex->pairs[known].slot : slot_for_new_pair(ex);
     int rc;
-    ex->restoring = false;
-    if (ex->frame_on) {
-        // Per-frame tables: every launch runs the items this input reaches; the ones the last forward into the same
-        // buffer reached and this one does not go back to their input-independent values (frame_restore_kernel), and
-        // the builder keeps this input's set for the next forward.  A forward on full tables (priming; pyramid_fusion1
-        // into a pair it has not written) records its set the same way.  A new pair takes the set of the pair it
-        // evicts, or a free one.
-        if (ex->primed_out.empty()) ex->out_slot.clear();
-        int slot = 0;
-        if (known_pair) {
-            slot = ex->out_slot[pair];
-        } else if (ex->primed_out.size() < 8) {
-            bool used[8] = {};
-            for (int k : ex->out_slot) used[k] = true;
-            while (used[slot]) ++slot;
-        } else {
-            slot = ex->out_slot[0];
-        }
-        // the stale items go back to their values by copy, not by arithmetic: one launch for all tables, behind the
-        // builder and ahead of conv1_1 (a forward that primes has nothing to restore)
-        ex->restoring = skip;
-        if (skip && !ex->store_valid) {
-            if ((rc = take_store(ex))) return rc;
-            DODT_HIP_CHECK(hipMemsetAsync(ex->d_counters, 0, 4096 * sizeof(int), s));
-        }
-        if ((rc = build_frame_tables(ex, slot))) return rc;
-        if (skip) {
-            hipLaunchKernelGGL(frame_restore_kernel, dim3((unsigned)(4 * ex->ctx->num_cus)), dim3(256), 0, s,
-                               ex->d_restore_plan, d_feat_out, d_bottleneck_out, last_skip ? 1 : 0);
-            DODT_LAUNCH_CHECK();
-        }
-        if (!known_pair) {
-            if (ex->primed_out.size() >= 8) ex->out_slot.erase(ex->out_slot.begin());
-            ex->out_slot.push_back(slot);
-        }
-    }
-    if ((rc = run_layers(ex, d_feat_out, d_bottleneck_out))) return rc;
+    if (ex->frame_on && (rc = begin_frame_forward(ex, p, slot, last_skip, d_feat_out, d_bottleneck_out))) return rc;
+    if ((rc = run_layers(ex, p, d_feat_out, d_bottleneck_out))) return rc;
     if (ex->skip_on) {
         ex->primed = true;
-        if (!known_pair) {
-            ex->primed_out.emplace_back(d_feat_out, d_bottleneck_out);
-            if (ex->primed_out.size() > 8) ex->primed_out.erase(ex->primed_out.begin());   // (re-primed when back)
-        }
+        if (known < 0) add_pair(ex, d_feat_out, d_bottleneck_out, slot);
     }
-    return DODT_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// the layers of one forward on the extractor's stream, with the tables ex->skipping selects
-int run_layers(dodt_extractor* ex, float* d_feat_out, float* d_bottleneck_out) {
-    hipStream_t s = ex->ctx->stream;
-    int rc;
-    auto L = [&](const char* n) -> const Layer& { return ex->layers[find_layer(ex, n)]; };
-#define RUN(name)                                           \
-    if ((rc = run_layer(ex, L(name), nullptr, 0, 0))) return rc;
-    // a conv that a 2x2 max pool follows pools in its epilogue when its tiling allows
-    static const bool no_fuse = getenv("DODT_CONV_NO_POOL_FUSE") != nullptr;
-#define RUN_POOLED(name, src, dst)                                                   \
-    if (!no_fuse && layer_can_pool(L(name))) {                                       \
-        if ((rc = run_layer(ex, L(name), nullptr, 0, 0, nullptr, dst))) return rc;   \
-    } else {                                                                         \
-        RUN(name);                                                                   \
-        if ((rc = run_pool(ex, src, dst))) return rc;                                \
-    }
-    if (ex->bf16)   // there is no stand-alone pool kernel for bf16 maps
-        for (const char* n : {"conv1_2", "conv2_2", "conv3_3"})
-            DODT_REQUIRE(!no_fuse && layer_can_pool(L(n)),
-                         "bf16 extractor: layer %s cannot pool in its epilogue", n);
-    if (ex->first2_variant >= 0) {
-        if ((rc = run_layer(ex, L("conv1_2"), nullptr, 0, 0, nullptr, P1, &L("conv1_1")))) return rc;
-    } else {
-        RUN("conv1_1"); RUN_POOLED("conv1_2", CAT1, P1);
-    }
-    RUN("conv2_1"); RUN_POOLED("conv2_2", CAT2, P2);
-    RUN("conv3_1"); RUN("conv3_2"); RUN_POOLED("conv3_3", CAT3, P3);
-#undef RUN_POOLED
-    RUN("conv4_1"); RUN("conv4_2"); RUN("conv4_3");
-    if (ex->kind == DODT_EXTRACTOR_VGG) {
-        // bev_vgg.py:102-112 / img_vgg.py:104-114: 4x bilinear upsampling of conv4_3, and the
-        // 256 -> 1 bottleneck of the RPN (rpn_model.py:251-267) on the upsampled map
-        const Buffer& c4 = ex->buf[C4C];
-        const long long n_pix = (long long)ex->batch * ex->out_h * ex->out_w;
-        constexpr int kLpp = 64;   // 256 channels / 4
-        hipLaunchKernelGGL(upsample_bilinear_cb8_kernel<kLpp>,
-                           dim3((unsigned)((n_pix * kLpp + 255) / 256)), dim3(256), 0, s, c4.ptr,
-                           c4.H, c4.W, (long long)c4.frame_floats(), ex->out_h, ex->out_w,
-                           ex->batch, d_feat_out, ex->d_bneck_w, ex->bneck_scale, ex->bneck_shift,
-                           d_bottleneck_out);
-        DODT_LAUNCH_CHECK();
-        return DODT_OK;
-    }
-    RUN("upconv3"); RUN("pyramid_fusion3");
-    RUN("upconv2"); RUN("pyramid_fusion2");
-    RUN("upconv1");
-#undef RUN
-    // last layer writes straight into the caller's buffer, pad rows sliced off
-    // ... and, fused into its epilogue, the 1x1 bottleneck (dt_rpn_model.py:298-322)
-    const Layer& last = L("pyramid_fusion1");
-    const bool fuse = d_bottleneck_out && variants()[last.main.variant].BN == 32 &&
-                      (last.tail.n_items == 0 || variants()[last.tail.variant].BN == 32);
-    if ((rc = run_layer(ex, last, d_feat_out, ex->pad_top, ex->in_h,
-                        fuse ? d_bottleneck_out : nullptr)))
-        return rc;
-    if (d_bottleneck_out && !fuse) {
-        const long long n_pix = (long long)ex->batch * ex->in_h * ex->in_w;
-        hipLaunchKernelGGL(bottleneck32_kernel, dim3((unsigned)((n_pix * 8 + 255) / 256)),
-                           dim3(256), 0, s, d_feat_out, n_pix, ex->d_bneck_w, ex->bneck_scale,
-                           ex->bneck_shift, d_bottleneck_out);
-        DODT_LAUNCH_CHECK();
-    }
-    return DODT_OK;
-}
-
-// The constants store: frame 0 of a forward on a zero input, through the same kernels and the full tables, written into
-// the store's maps in place of the layer buffers.  Neither the caller's input nor any live buffer is touched.  Waits
-// for the stream (once per weight load).
-int take_store(dodt_extractor* ex) {
-    hipStream_t s = ex->ctx->stream;
-    const bool fresh = ex->d_restore_plan == nullptr;
-    if (fresh) {
-        size_t total = 0;
-        hipError_t ea = hipSuccess;
-        for (int i = 0; i < NBUF && ea == hipSuccess; ++i) {
-            if (i == X0 || i == F1 || !ex->buf[i].ptr) continue;
-            const size_t bytes = ex->buf[i].frame_floats() * sizeof(float);
-            ea = hipMalloc(&ex->store[i], bytes);
-            total += bytes;
-        }
-        const size_t px = (size_t)ex->out_h * ex->out_w;
-        if (ea == hipSuccess) ea = hipMalloc(&ex->store_feat, px * ex->out_c * sizeof(float));
-        if (ea == hipSuccess) ea = hipMalloc(&ex->store_bneck, px * sizeof(float));
-        if (ea == hipSuccess) ea = hipMalloc(&ex->d_restore_plan, sizeof(RestorePlan));
-        if (ea != hipSuccess) free_store(ex);     // (nothing half-allocated stays behind)
-        DODT_HIP_CHECK(ea);
-        ex->store_bytes = total + px * (ex->out_c + 1) * sizeof(float);
-    }
-    // a zero input frame, and every launch's items of frame 0
-    float* zeros = nullptr;
-    const size_t in_bytes = ex->buf[X0].frame_floats() * sizeof(float);
-    DODT_HIP_CHECK(hipMalloc(&zeros, in_bytes));
-    DODT_HIP_CHECK(hipMemsetAsync(zeros, 0, in_bytes, s));
-    struct Saved { Launch* ln; int4* d_items; int n_items; };
-    std::vector<Saved> saved;
-    std::vector<void*> temps = {zeros};
-    hipError_t e = hipSuccess;
-    for (Layer& l : ex->layers)
-        for (Launch* ln : {&l.main, &l.tail}) {
-            if (ln->h_items.empty()) continue;
-            std::vector<int4> first;
-            for (const int4& it : ln->h_items)
-                if (it.x == 0) first.push_back(it);
-            int4* d = nullptr;
-            if (!first.empty() && e == hipSuccess) e = hipMalloc(&d, first.size() * sizeof(int4));
-            if (d) temps.push_back(d);
-            if (d && e == hipSuccess) e = hipMemcpy(d, first.data(), first.size() * sizeof(int4), hipMemcpyHostToDevice);
-            saved.push_back({ln, ln->d_items, ln->n_items});
-            ln->d_items = d;
-            ln->n_items = (int)first.size();
-        }
-    float* live[NBUF];
-    for (int i = 0; i < NBUF; ++i) {
-        live[i] = ex->buf[i].ptr;
-        if (ex->store[i]) ex->buf[i].ptr = ex->store[i];
-    }
-    ex->buf[X0].ptr = zeros;
-    const std::vector<char> skipping = ex->skipping;
-    const int batch = ex->batch;
-    const bool timed = ex->timed;
-    ex->skipping.assign(ex->layers.size(), 0);
-    ex->batch = 1;
-    ex->timed = false;
-    int rc = DODT_OK;
-    if (e == hipSuccess) e = hipMemsetAsync(ex->d_counters, 0, 4096 * sizeof(int), s);
-    if (e == hipSuccess) rc = run_layers(ex, ex->store_feat, ex->bneck_loaded ? ex->store_bneck : nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    ex->skipping = skipping;
-    ex->batch = batch;
-    ex->timed = timed;
-    for (int i = 0; i < NBUF; ++i) ex->buf[i].ptr = live[i];
-    for (const Saved& sv : saved) {
-        sv.ln->d_items = sv.d_items;
-        sv.ln->n_items = sv.n_items;
-    }
-    for (void* p : temps) (void)hipFree(p);
-    if (rc) return rc;
-    DODT_HIP_CHECK(e);
-    // where each table's items live (the layer buffers never move; the caller's pair comes with the launch)
-    RestorePlan pl;
-    for (size_t li = 0; li < ex->layers.size(); ++li) {
-        const Layer& l = ex->layers[li];
-        const int pool_dst = fused_pool_buffer(l);
-        int j = 0;
-        for (const Launch* ln : {&l.main, &l.tail}) {
-            const dodt::ft::Table& ft = ex->frame_plan.t[2 * li + j];
-            RestoreTable& t = pl.t[2 * li + j++];
-            if (!ft.items) continue;
-            const Buffer& dst = ex->buf[l.dst];
-            t.list = ft.restore;
-            t.count = ft.rcount;
-            t.dst = dst.ptr;                 // (nullptr: pyramid_fusion1)
-            t.src = ex->store[l.dst];
-            t.frame_stride = (long long)dst.frame_floats();
-            t.H = dst.H; t.W = dst.W;
-            t.ch0 = l.dst_coff;
-            t.bn = variants()[ln->variant].BN;
-            t.f = ft.f; t.th = ft.th; t.tw = ft.tw;
-            if (pool_dst >= 0) {
-                t.pool_dst = ex->buf[pool_dst].ptr;
-                t.pool_src = ex->store[pool_dst];
-                t.pool_frame_stride = (long long)ex->buf[pool_dst].frame_floats();
-            }
-        }
-    }
-    pl.feat = ex->store_feat;
-    pl.bneck = ex->bneck_loaded && bneck_fused(ex->layers.back()) ? ex->store_bneck : nullptr;   // (not fused: a kernel of its own rewrites the map)
-    pl.pad_top = ex->pad_top; pl.out_h = ex->out_h; pl.out_c = ex->out_c;
-    DODT_HIP_CHECK(hipMemcpy(ex->d_restore_plan, &pl, sizeof(pl), hipMemcpyHostToDevice));
-    ex->store_valid = true;
     return DODT_OK;
 }
 
 }  // namespace
 
 extern "C" {
-
-int dodt_extractor_forward_padded(dodt_extractor* ex, const float* d_x0, float* d_feat_out,
-                                  float* d_bottleneck_out) {
-    DODT_REQUIRE(ex && d_x0 && d_feat_out, "dodt_extractor_forward_padded: NULL argument");
-    // the first layer reads the caller's buffer in place of the extractor's own input buffer
-    Buffer& x0 = ex->buf[X0];
-    float* cur = x0.ptr;
-    x0.ptr = const_cast<float*>(d_x0);
-    const int rc = dodt_extractor_forward(ex, nullptr, d_feat_out, d_bottleneck_out);
-    x0.ptr = cur;
-    return rc;
-}
-
-int dodt_extractor_set_input(dodt_extractor* ex, const float* d_x0) {
-    DODT_REQUIRE(ex, "dodt_extractor_set_input: extractor is NULL");
-    if (!ex->own_x0) ex->own_x0 = ex->buf[X0].ptr;
-    ex->buf[X0].ptr = d_x0 ? const_cast<float*>(d_x0) : ex->own_x0;
-    return DODT_OK;
-}
-
-int dodt_extractor_set_input_support(dodt_extractor* ex, const uint8_t* mask, int rows, int cols,
-                                     long long* skipped_items) {
-    DODT_REQUIRE(ex, "dodt_extractor_set_input_support: extractor is NULL");
-    DODT_REQUIRE(!mask || (rows == ex->H && cols == ex->W),
-                 "dodt_extractor_set_input_support: mask is %dx%d, the padded input %dx%d", rows, cols, ex->H, ex->W);
-    if (skipped_items) *skipped_items = 0;
-    DODT_HIP_CHECK(hipStreamSynchronize(ex->ctx->stream));   // (no launch still reads the old tables)
-    free_skip_tables(ex);
-    ex->primed = false;
-    ex->primed_out.clear();
-    // fp32 pyramid only (the bf16 / split paths and the plain VGG keep full tables)
-    if (!mask || ex->kind != DODT_EXTRACTOR_VGG_PYR || ex->bf16 || ex->first2_variant >= 0) return DODT_OK;
-    // each layer's input-dependent outputs, in forward order; a buffer's mask is the OR of its writers so far
-    Support bufs[NBUF];
-    bufs[X0] = Support(ex->H, ex->W);
-    for (int y = 0; y < ex->H; ++y)
-        for (int x = 0; x < ex->W; ++x) bufs[X0].at(y, x) = mask[(size_t)y * ex->W + x] != 0;
-    long long skipped = 0;
-    for (Layer& l : ex->layers) {
-        const KernelVariant& lv = variants()[l.main.variant];
-        const Support out = l.deconv ? upconv2(bufs[l.src])
-                            : lv.wino && lv.wino_m == 4 ? wino_blocks(bufs[l.src], 4) : dilate(bufs[l.src], 1);
-        Support& d = bufs[l.dst];
-        if (d.m.empty()) d = out;
-        else
-            for (size_t k = 0; k < d.m.size(); ++k) d.m[k] |= out.m[k];
-        // the fused (or stand-alone) 2x2 pools behind conv1_2 / conv2_2 / conv3_3
-        if (l.name == "conv1_2") bufs[P1] = pool2(out);
-        if (l.name == "conv2_2") bufs[P2] = pool2(out);
-        if (l.name == "conv3_3") bufs[P3] = pool2(out);
-        // an item is kept if any output it writes may depend on the input: its conv tile (and with it the pooled
-        // outputs of the tile, the NHWC copy and the bottleneck), a transposed conv's 2TH x 2TW outputs
-        const SupportSum sum(out);
-        double kept_units = 0.0, all_units = 0.0;
-        for (Launch* ln : {&l.main, &l.tail}) {
-            if (ln->h_items.empty()) continue;
-            const KernelVariant& v = variants()[ln->variant];
-            const int f = l.deconv ? 2 : 1;
-            std::vector<int4> keep;
-            for (const int4& it : ln->h_items)
-                if (sum.any(f * it.z, f * (it.z + v.TH), f * it.w, f * (it.w + v.TW))) keep.push_back(it);
-            const double units = (double)v.TH * v.TW * v.BN;
-            kept_units += units * keep.size();
-            all_units += units * ln->h_items.size();
-            skipped += (long long)(ln->h_items.size() - keep.size());
-            ln->n_skip = (int)keep.size();
-            if (keep.empty()) continue;
-            DODT_HIP_CHECK(hipMalloc(&ln->d_skip, keep.size() * sizeof(int4)));
-            DODT_HIP_CHECK(hipMemcpy(ln->d_skip, keep.data(), keep.size() * sizeof(int4), hipMemcpyHostToDevice));
-        }
-        l.skip_frac = all_units > 0 ? kept_units / all_units : 1.0;
-    }
-    ex->skip_on = true;
-    if (skipped_items) *skipped_items = skipped;
-    if (getenv("DODT_DEBUG_PLAN"))
-        for (const Layer& l : ex->layers)
-            fprintf(stderr, "[dodt] %-16s skip tables: %d of %d items\n", l.name.c_str(),
-                    std::max(l.main.n_skip, 0) + std::max(l.tail.n_skip, 0), l.main.n_items + l.tail.n_items);
-    return DODT_OK;
-}
-
-int dodt_extractor_set_frame_tables(dodt_extractor* ex, int on, int* enabled) {
-    DODT_REQUIRE(ex, "dodt_extractor_set_frame_tables: extractor is NULL");
-    namespace ft = dodt::ft;
-    if (enabled) *enabled = 0;
-    DODT_HIP_CHECK(hipStreamSynchronize(ex->ctx->stream));   // (no launch still reads the old tables)
-    free_frame_tables(ex);
-    if (!on || !ex->skip_on) return DODT_OK;
-    // the layers in the builder's order, none of them block-wise (F(4x4) Winograd); both masks of a frame in LDS
-    if ((int)ex->layers.size() != ft::kLayers) return DODT_OK;
-    for (const Layer& l : ex->layers)
-        for (const Launch* ln : {&l.main, &l.tail})
-            if (ln->variant >= 0 && variants()[ln->variant].wino && variants()[ln->variant].wino_m == 4) return DODT_OK;
-    const size_t words = (size_t)ft::level_words(ex->H, ex->W, 0);
-    if (words * 8 > 160 * 1024 - 1024) return DODT_OK;
-    DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&frame_walk_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(words * 8)));
-    auto alloc = [&](size_t bytes, void** p) {
-        hipError_t e = hipMalloc(p, bytes);
-        if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
-        if (e == hipSuccess) ex->frame_allocs.push_back(*p);
-        return e;
-    };
-    ft::Plan& pl = ex->frame_plan;
-    pl.H = ex->H; pl.W = ex->W; pl.frames = ex->batch;
-    DODT_HIP_CHECK(alloc((size_t)ex->batch * ft::stash_words(ex->H, ex->W) * 4, (void**)&pl.stash));
-    DODT_HIP_CHECK(alloc((size_t)ex->batch * words * 4, (void**)&ex->d_frame_bits));
-    DODT_HIP_CHECK(alloc(2 * ft::kTables * sizeof(int), (void**)&ex->d_frame_counts));
-    for (size_t li = 0; li < ex->layers.size(); ++li) {
-        Layer& l = ex->layers[li];
-        int j = 0;
-        for (Launch* ln : {&l.main, &l.tail}) {
-            ft::Table& t = pl.t[2 * li + j];
-            const int jj = j++;
-            if (ln->n_skip <= 0) continue;
-            const KernelVariant& v = variants()[ln->variant];
-            t.items = ln->d_skip;
-            t.n = ln->n_skip;
-            t.f = l.deconv ? 2 : 1;
-            t.th = t.f * v.TH;
-            t.tw = t.f * v.TW;
-            DODT_HIP_CHECK(alloc(t.n, (void**)&t.now));
-            if (li + 1 == ex->layers.size()) {     // pyramid_fusion1: a set per remembered output pair
-                for (int k = 0; k < 8; ++k) DODT_HIP_CHECK(alloc(t.n, (void**)&ex->out_prev[k][jj]));
-            } else {
-                DODT_HIP_CHECK(alloc(t.n, (void**)&t.prev));
-            }
-            DODT_HIP_CHECK(alloc(t.n * sizeof(int4), (void**)&t.run));
-            t.count = ex->d_frame_counts + 2 * li + jj;
-            DODT_HIP_CHECK(alloc(t.n * sizeof(int4), (void**)&t.restore));
-            t.rcount = ex->d_frame_counts + ft::kTables + 2 * li + jj;
-            ln->d_run = t.run;
-            ln->d_count = t.count;
-        }
-    }
-    DODT_HIP_CHECK(alloc(sizeof(ft::Plan), (void**)&ex->d_frame_plan));
-    DODT_HIP_CHECK(hipMemcpy(ex->d_frame_plan, &pl, sizeof(ft::Plan), hipMemcpyHostToDevice));
-    // the next forward runs full tables and records its input's items
-    ex->primed = false;
-    ex->primed_out.clear();
-    ex->frame_on = true;
-    if (enabled) *enabled = 1;
-    return DODT_OK;
-}
-
-int dodt_extractor_frame_items(dodt_extractor* ex, int* items, int n) {
-    DODT_REQUIRE(ex && items && n >= (int)ex->layers.size(),
-                 "dodt_extractor_frame_items: items must hold dodt_extractor_layer_count() entries");
-    const WorkShare share(ex);
-    for (size_t i = 0; i < ex->layers.size(); ++i)
-        items[i] = share.per_frame(ex, i) ? share.items(ex, i, 0) + share.items(ex, i, 1) + share.restored(ex, i, 0) +
-                                                share.restored(ex, i, 1)
-                                          : -1;
-    return DODT_OK;
-}
-
-int dodt_extractor_frame_split(dodt_extractor* ex, int* computed, int* restored, int n) {
-    DODT_REQUIRE(ex && computed && restored && n >= (int)ex->layers.size(),
-                 "dodt_extractor_frame_split: computed and restored must hold dodt_extractor_layer_count() entries");
-    const WorkShare share(ex);
-    for (size_t i = 0; i < ex->layers.size(); ++i) {
-        const bool pf = share.per_frame(ex, i);
-        computed[i] = pf ? share.items(ex, i, 0) + share.items(ex, i, 1) : -1;
-        restored[i] = pf ? share.restored(ex, i, 0) + share.restored(ex, i, 1) : -1;
-    }
-    return DODT_OK;
-}
-
-long long dodt_extractor_store_bytes(const dodt_extractor* ex) { return ex ? (long long)ex->store_bytes : 0; }
-
-}  // extern "C"
-
-namespace {
-
-// the host rule for one layer: restore != nullptr: the two lists; nullptr: run receives their union, in table order
-int frame_lists_host(const char* who, const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
-                     const int* items, int n_items, const uint8_t* prev, int* run, int* n_run, int* restore, int* n_restore) {
-    namespace ft = dodt::ft;
-    DODT_REQUIRE(masks && items && run && n_run && frames >= 1 && n_items >= 0, "%s: NULL argument", who);
-    DODT_REQUIRE(rows > 0 && cols > 0 && rows % 8 == 0 && cols % 8 == 0, "%s: masks of %dx%d, not divisible by 8", who, rows,
-                 cols);
-    DODT_REQUIRE(layer >= 0 && layer < ft::kLayers && th > 0 && tw > 0, "%s: bad layer or tile", who);
-    for (int i = 0; i < n_items; ++i)
-        DODT_REQUIRE(items[4 * i] >= 0 && items[4 * i] < frames, "%s: item %d names frame %d", who, i, items[4 * i]);
-    const bool deconv = layer == 10 || layer == 12 || layer == 14;
-    std::vector<uint8_t> now((size_t)n_items, 0), pv((size_t)n_items, 0);
-    if (prev) pv.assign(prev, prev + n_items);
-    int count = 0, rcount = 0;
-    ft::Plan pl;
-    pl.H = rows; pl.W = cols; pl.frames = frames;
-    std::vector<uint32_t> stash((size_t)ft::stash_words(rows, cols) * frames);
-    pl.stash = stash.data();
-    ft::Table& t = pl.t[2 * layer];
-    t.items = reinterpret_cast<const int4*>(items);
-    t.n = n_items;
-    t.f = deconv ? 2 : 1;
-    t.th = t.f * th;
-    t.tw = t.f * tw;
-    t.now = now.data();
-    t.prev = pv.data();
-    t.run = reinterpret_cast<int4*>(run);
-    t.count = &count;
-    t.restore = reinterpret_cast<int4*>(restore);
-    t.rcount = &rcount;
-    const int words = ft::level_words(rows, cols, 0), p = ft::pitch(cols);
-    std::vector<uint32_t> a(words), b(words);
-    for (int f = 0; f < frames; ++f) {
-        std::fill(a.begin(), a.end(), 0u);
-        for (int y = 0; y < rows; ++y)
-            for (int x = 0; x < cols; ++x)
-                if (masks[((size_t)f * rows + y) * cols + x]) a[y * p + (x >> 5)] |= 1u << (x & 31);
-        ft::walk(pl, f, a.data(), b.data(), 0, 1, [] {});
-    }
-    if (!restore) {     // what a forward touches, computed or restored
-        for (int i = 0; i < n_items; ++i)
-            if (now[i] | pv[i]) memcpy(run + 4 * count++, items + 4 * i, 16);
-        *n_run = count;
-        return DODT_OK;
-    }
-    int scan[2];
-    if (n_items > 0) ft::compact(t, pv.data(), scan, 0, 1, [] {});
-    *n_run = count;
-    *n_restore = rcount;
-    return DODT_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int dodt_frame_tables_host(const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
-                           const int* items, int n_items, const uint8_t* prev, int* run, int* n_run) {
-    return frame_lists_host("dodt_frame_tables_host", masks, frames, rows, cols, layer, th, tw, items, n_items, prev, run,
-                            n_run, nullptr, nullptr);
-}
-
-int dodt_frame_restore_host(const int* item, int f, int th, int tw, int bn, int ch0, int rows, int cols, int channels,
-                            int pad_top, float* dst, const float* src, float* dst2, const float* src2) {
-    DODT_REQUIRE(item && dst && src && (!dst2 == !src2), "dodt_frame_restore_host: NULL argument");
-    DODT_REQUIRE(f >= 1 && th > 0 && tw > 0 && tw % 4 == 0 && bn > 0 && bn % 8 == 0 && ch0 % 8 == 0 && rows > 0 && cols > 0 &&
-                     cols % 4 == 0 && ch0 + (item[1] + 1) * bn <= channels && item[0] >= 0 && item[2] >= 0 && item[3] >= 0,
-                 "dodt_frame_restore_host: bad geometry");
-    namespace ft = dodt::ft;
-    ft::RestorePlan pl;
-    ft::RestoreTable& t = pl.t[0];
-    t.H = rows; t.W = cols; t.ch0 = ch0; t.bn = bn; t.f = f; t.th = f * th; t.tw = f * tw;
-    if (pad_top < 0) {
-        t.dst = dst; t.src = src;
-        t.frame_stride = (long long)rows * cols * channels;
-        t.pool_dst = dst2; t.pool_src = src2;
-        t.pool_frame_stride = (long long)(rows / 2) * (cols / 2) * channels;
-    } else {
-        DODT_REQUIRE(pad_top < rows, "dodt_frame_restore_host: bad geometry");
-        pl.feat = src; pl.bneck = src2;
-        pl.pad_top = pad_top; pl.out_h = rows - pad_top; pl.out_c = channels;
-    }
-    ft::restore_item(pl, t, make_int4(item[0], item[1], item[2], item[3]), dst, dst2, 0, 1);
-    return DODT_OK;
-}
-
-int dodt_frame_lists_host(const uint8_t* masks, int frames, int rows, int cols, int layer, int th, int tw,
-                          const int* items, int n_items, const uint8_t* prev, int* run, int* n_run, int* restore,
-                          int* n_restore) {
-    DODT_REQUIRE(restore && n_restore, "dodt_frame_lists_host: NULL argument");
-    return frame_lists_host("dodt_frame_lists_host", masks, frames, rows, cols, layer, th, tw, items, n_items, prev, run,
-                            n_run, restore, n_restore);
-}
 
 int dodt_extractor_output_shape(const dodt_extractor* ex, int* h, int* w, int* c) {
     DODT_REQUIRE(ex, "dodt_extractor_output_shape: NULL argument");
@@ -2037,8 +1077,8 @@ int dodt_extractor_read_activation(dodt_extractor* ex, const char* name, float* 
     const Layer& l = ex->layers[li];
     DODT_REQUIRE(!(li == 0 && ex->first2_variant >= 0),
                  "layer %s runs folded into conv1_2's launch: its map is not stored (DODT_CONV_BF16_FIRST2=0 keeps it)", name);
-    Buffer b = ex->buf[buffer_for_layer_output(l)];
-    if (stored) b.ptr = ex->store[buffer_for_layer_output(l)];
+    Buffer b = ex->buf[l.dst];
+    if (stored) b.ptr = ex->store[l.dst];
     const size_t frame_step = stored ? 0 : b.frame_floats();
     DODT_REQUIRE(b.ptr != nullptr,
                  "layer %s is written straight into the caller's output buffer", name);
@@ -2110,9 +1150,7 @@ int dodt_extractor_forward_timed(dodt_extractor* ex, const float* d_in, float* d
         if (!l.ev0) DODT_HIP_CHECK(hipEventCreate(&l.ev0));
         if (!l.ev1) DODT_HIP_CHECK(hipEventCreate(&l.ev1));
     }
-    ex->timed = true;
-    const int rc = dodt_extractor_forward(ex, d_in, d_feat_out, d_bottleneck_out);
-    ex->timed = false;
+    const int rc = forward(ex, d_in, nullptr, d_feat_out, d_bottleneck_out, true);
     if (rc) return rc;
     DODT_HIP_CHECK(hipStreamSynchronize(ex->ctx->stream));
     const WorkShare share(ex);
@@ -2123,12 +1161,11 @@ int dodt_extractor_forward_timed(dodt_extractor* ex, const float* d_in, float* d
         snprintf(o.name, sizeof(o.name), "%s", l.name.c_str());
         const bool folded = ex->first2_variant >= 0 && i < 2;      // conv1_1 and conv1_2 are one launch, timed as conv1_2
         snprintf(o.kernel, sizeof(o.kernel), "%s", kernel_name(variants()[folded ? ex->first2_variant : l.main.variant]));
-        // (what this forward ran: the skip tables of a layer that skipped)
-        const bool sk = i < ex->skipping.size() && ex->skipping[i];
-        const bool pf = share.per_frame(ex, i);     // (per-frame tables: the counts the builder wrote)
-        const double frac = pf ? share.of(ex, l) : sk ? l.skip_frac : 1.0;
-        const int n_main = pf ? share.items(ex, i, 0) : sk && l.main.n_skip >= 0 ? l.main.n_skip : l.main.n_items;
-        const int n_tail = pf ? share.items(ex, i, 1) : sk && l.tail.n_skip >= 0 ? l.tail.n_skip : l.tail.n_items;
+        // (what this forward ran: choose_tables' record; per-frame tables: the counts the builder wrote)
+        const bool pf = share.per_frame(ex, i);
+        const double frac = pf ? share.of(ex, l) : ex->ran[i].kind != Tables::Full ? l.skip_frac : 1.0;
+        const int n_main = pf ? share.items(i, 0) : ex->ran[i].n[0];
+        const int n_tail = pf ? share.items(i, 1) : ex->ran[i].n[1];
         o.launches = folded && i == 0 ? 0 : (n_main > 0) + (n_tail > 0);
         o.items = n_main + n_tail;
         o.flops_direct = layer_direct_flops(ex, l, frac);

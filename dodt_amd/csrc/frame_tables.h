@@ -8,7 +8,8 @@
 //
 // The rule is written once, for the host and the device: a "team" of nthr threads (tid 0 of 1 on the host) walks the
 // words of a phase with that stride and meets at sync() between phases.  On the device one workgroup per frame holds
-// the two working masks in LDS; the host entry dodt_frame_tables_host runs the same functions on vectors.
+// the two working masks in LDS (conv_skip.hip frame_walk_kernel); the host entry dodt_frame_tables_host runs the same
+// functions on vectors.
 #pragma once
 #include <cstdint>
 
@@ -19,8 +20,11 @@ namespace ft {
 
 #define DODT_FT_HD __host__ __device__ inline
 
-constexpr int kLayers = 16;   // the pyramid net's layers in launch order (conv.hip dodt_extractor_create)
+constexpr int kLayers = 16;   // the pyramid net's layers in launch order (extractor.h LayerId, which asserts the count)
 constexpr int kTables = 2 * kLayers;   // a layer's main and tail launch
+// the decoder behind the ten convs alternates transposed conv and fusion conv (walk() below; extractor.h asserts that
+// these are the net's upconv layers)
+constexpr bool transposed(int layer) { return layer >= 10 && layer % 2 == 0; }
 
 // one launch's tables
 struct Table {

@@ -1,5 +1,5 @@
 """Soundness of the fp32 BEV net's skip rule ("a 3x3 conv reaches 1, a pool ORs 2x2 windows, a transposed conv is the
-nearest 2x upsampling dilated by 2"), which frame_tables.h, the Support functions of conv.hip and layer_masks of
+nearest 2x upsampling dilated by 2"), which frame_tables.h, the Support functions of conv_skip.hip and layer_masks of
 tests/test_bev_support_mask.py all restate.
 
 1. The rule against the network's arithmetic: the oracle net with live-fringe weights (|w|, beta = 0: nothing cancels,

@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 
 from dodt_amd import config, device, ops, synth
+from dodt_amd.core.feature_extractors.vgg_pyramid import BevVggPyr
 from dodt_amd.pipeline import FramePairPipeline
+from tests import test_bev_skip_soundness as sound
 from tests import test_gpu_bev_frame_skip as fs
 from tests import test_gpu_bev_skip as base
 
@@ -101,6 +103,101 @@ def test_store_equals_a_full_table_net_fed_zeros():
     base._assert_same(got, want, 'constants store after a weight reload')
     on.set_input_support(None)                               # frees it
     assert on.store_bytes() == 0
+
+
+# the smallest net that still has every pyramid level and more than one tile per layer: 60 x 96 (padded 64 x 96, level
+# 3 is 8 x 12), three frames -- the store's pass runs one frame beside them
+SB, SH, SW, DEPTH = 3, 60, 96, C['bev_depth']
+
+
+def _small_read(ctx, ex, feat, bneck):
+    ctx.sync()
+    out = {n: ex.activation(n) for n in base.LAYERS}
+    out['feat'] = feat.download().copy()
+    out['bneck'] = bneck.download().copy()
+    return out
+
+
+def _small_store(ex):
+    got = {n: ex.activation('store:' + n) for n in base.LAYERS}
+    got['feat'] = ex.activation('store:pyramid_fusion1')
+    got['bneck'] = ex.activation('store:bottleneck')
+    return got
+
+
+def test_store_taken_inside_a_timed_forward_on_a_callers_input():
+    """The constants store is a one-frame walk on zeros beside a three-frame extractor, taken here inside a timed
+    forward while the input is a caller's buffer (set_input): the forward around it, the caller's input and the
+    forwards after it through all three ways the input is chosen must be untouched by it."""
+    ctx = device.default_context()
+    nets = []
+    for _ in range(2):
+        ex = BevVggPyr(ctx=ctx, shared_gpu=True)
+        ex.load_params(sound.live_fringe_params(DEPTH))
+        ex._ensure(SB, SH, SW, DEPTH)
+        nets.append(ex)
+    on, off = nets
+    mask = np.ones((PAD + SH, SW), np.uint8)     # every cell of the real rows
+    mask[:PAD] = 0
+    on.set_input_support(mask, frame_tables=True)
+    if not on.frame_tables_on:
+        assert ctx.lib.dodt_conv_mode() == 4
+        return
+    rng = np.random.default_rng(11)
+    dense = np.zeros((SB, PAD + SH, SW, DEPTH), np.float32)
+    dense[:, PAD:] = rng.uniform(0.1, 1.0, size=(SB, SH, SW, DEPTH))
+    sparse = np.zeros_like(dense)      # a few isolated cells, other ones in every frame
+    for f, y, x, c in ((0, PAD, 0, 0), (0, PAD + SH - 1, SW - 1, 5), (1, PAD + 30, 47, 2), (2, PAD + 17, 64, 5)):
+        sparse[f, y, x, c] = 0.75
+    other = np.zeros_like(dense)
+    for f, y, x, c in ((0, PAD + 40, 20, 1), (1, PAD + 5, 90, 3), (2, PAD + 59, 33, 0), (2, PAD + 8, 8, 4)):
+        other[f, y, x, c] = 0.5
+    zeros = ctx.zeros(dense.shape, np.float32)
+    new_pair = lambda: (ctx.empty((SB, SH, SW, 32), np.float32), ctx.empty((SB, SH, SW, 1), np.float32))
+    pair_a, pair_b, ref = new_pair(), new_pair(), new_pair()
+
+    def want(host):
+        d = ctx.array(host)
+        off.forward_device_padded(d, *ref)
+        return _small_read(ctx, off, *ref)
+
+    # 1. prime through set_input on a caller's buffer
+    x = ctx.array(dense)
+    on.set_input(x)
+    on.forward_timed(None, *pair_a)
+    base._assert_same(_small_read(ctx, on, *pair_a), want(dense), 'priming forward')
+    assert on.store_bytes() == 0
+    # 2. the first restoring forward is a timed one, on the same buffer: it takes the store
+    x.upload(sparse)
+    info = on.forward_timed(None, *pair_a)
+    base._assert_same(_small_read(ctx, on, *pair_a), want(sparse), 'first restoring forward (timed, set_input)')
+    assert np.array_equal(x.download().view(np.uint32), sparse.view(np.uint32))
+    assert on.store_bytes() > 0
+    assert all(np.isfinite(l['ms']) and l['ms'] >= 0 for l in info), [l['ms'] for l in info]
+    computed, restored = on.frame_split()
+    assert min(computed) >= 0 and min(restored) >= 0 and sum(restored) > 0, (computed, restored)
+    assert [l['items'] for l in info] == computed
+    zero_maps = want(np.zeros_like(dense))
+    base._assert_same(_small_store(on), zero_maps, 'constants store')
+    # 3. the extractor's own input buffer (the host-side copy), then a padded caller's buffer
+    on.set_input(None)
+    d_other, d_dense, d_sparse = ctx.array(np.ascontiguousarray(other[:, PAD:])), ctx.array(dense), ctx.array(sparse)
+    on.forward_device(d_other, *pair_b)
+    base._assert_same(_small_read(ctx, on, *pair_b), want(other), 'forward_device into a second pair')
+    on.forward_device_padded(d_dense, *pair_a)
+    base._assert_same(_small_read(ctx, on, *pair_a), want(dense), 'forward_device_padded into the first pair')
+    # 4. new weights (a store that is not zero): one priming and one restoring forward
+    reload = synth.pyramid_params(DEPTH, seed=77)
+    on.load_params(reload)
+    off.load_params(reload)
+    on.forward_device_padded(d_dense, *pair_a)
+    base._assert_same(_small_read(ctx, on, *pair_a), want(dense), 'priming forward after a weight reload')
+    on.forward_device_padded(d_sparse, *pair_a)
+    base._assert_same(_small_read(ctx, on, *pair_a), want(sparse), 'restoring forward after a weight reload')
+    off.forward_device_padded(zeros, *ref)
+    zero_maps = _small_read(ctx, off, *ref)
+    assert any(v.any() for v in zero_maps.values())
+    base._assert_same(_small_store(on), zero_maps, 'constants store after a weight reload')
 
 
 def _run_sequence(check_counts):

@@ -1,5 +1,5 @@
 """The Winograd transforms the fp32 conv kernels hard-code (dodt_amd/csrc/wino_kernels.h: F(2x2,3x3), points
-0, +-1, inf; wino43_kernel.h: F(4x4,3x3), points 0, +-2/3, +-3/2, inf; filter transforms in conv.hip),
+0, +-1, inf; wino43_kernel.h: F(4x4,3x3), points 0, +-2/3, +-3/2, inf; filter transforms in conv_weights.hip),
 restated in numpy float64 exactly as the kernels compute them and checked against the direct correlation.
 CPU only: pins the algebra, the kernels are held to the oracle on the GPU (tests/test_gpu_conv.py)."""
 import numpy as np
@@ -24,7 +24,7 @@ def at43(m):
 
 
 def g43():
-    """conv.hip: G[j][k] = p_j^k / prod_{l != j} (p_j - p_l), last row (0, 0, 1)."""
+    """conv_weights.hip (block_wino43): G[j][k] = p_j^k / prod_{l != j} (p_j - p_l), last row (0, 0, 1)."""
     p = [0.0, A, -A, B, -B]
     g = np.zeros((6, 3))
     for j in range(5):
