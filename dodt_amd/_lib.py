@@ -133,6 +133,10 @@ SIGNATURES = {
     'dodt_crop_and_resize_strided': (_i, [_vp, _pf, _i, _i, _i, _pf, _i, _pi32, _i, _i, _pf,
                                           C.c_longlong]),
     'dodt_correlation': (_i, [_vp, _pf, _pf, _i, _i, _i, _i, _i, _i, _pf]),
+    'dodt_crop_and_resize_indexed': (_i, [_vp, _pf, _i, _i, _i, _pf, _i, _pi32, _i, _pi32, _i, _i, _pf,
+                                          C.c_longlong]),
+    'dodt_correlation_tile_list': (_i, [_vp, _i, _i, _pf, _i, _pi32, _i, _pi32, _i, _i, _pi32, _i, _pi32]),
+    'dodt_correlation_tiles': (_i, [_vp, _pf, _pf, _i, _i, _i, _i, _i, _i, _pi32, _i, _pi32, _pf]),
     'dodt_mean_fusion': (_i, [_vp, _pf, _pf, _i, _pi32, _i, _pf]),
     'dodt_fc_create': (_i, [_vp, _i, _i, _hf, _hf, _i, C.POINTER(_vp)]),
     'dodt_fc_create_ex': (_i, [_vp, _i, _i, _hf, _hf, _i, C.POINTER(_vp)]),
@@ -154,6 +158,7 @@ SIGNATURES = {
     'dodt_gather_rows': (_i, [_vp, _pf, _i, _pi32, _i, _pi32, _pf]),
     'dodt_max_fg_logit': (_i, [_vp, _pf, _i, _i, _pi32, _pf]),
     'dodt_pack_detections': (_i, [_vp, _pf, _pf, _pf, _pf, _pi32, _pi32, _i, _f, _pf, _pi32]),
+    'dodt_pack_detections_compact': (_i, [_vp, _pf, _pf, _pf, _pf, _pi32, _pi32, _i, _f, _pf, _pi32]),
     'dodt_angle_vector_to_orientation': (_i, [_vp, _pf, _i, _pi32, _pf]),
     'dodt_box_4c_decode': (_i, [_vp, _pf, _pf, _i, _pi32, C.POINTER(_f),
                                 C.POINTER(_f), _pf, _pf, _pf]),

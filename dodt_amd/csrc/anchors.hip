@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(256)
 pack_detections_kernel(const float* __restrict__ boxes_3d, const float* __restrict__ scores,
                        const float* __restrict__ orientations, const float* __restrict__ corr,
                        const int* __restrict__ sel, const int* __restrict__ d_count, int max_det,
-                       float frame_mark, float* __restrict__ rec, int* __restrict__ count_out) {
+                       float frame_mark, float* __restrict__ rec, int* __restrict__ count_out, int corr_compact) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int cnt = min(*d_count, max_det);
     if (t == 0) *count_out = cnt;
@@ -348,9 +348,11 @@ pack_detections_kernel(const float* __restrict__ boxes_3d, const float* __restri
             if (orientations) orientation_correct(b, orientations[src]);
             if (col >= 9) {
                 // dt_evaluator.py:1217-1224: the box shifted by (dx, dz, dry) into the next frame
-                b[0] += corr[(size_t)src * 3 + 0];
-                b[2] += corr[(size_t)src * 3 + 1];
-                b[6] += corr[(size_t)src * 3 + 2];
+                // (compact: one row of offsets per detection instead of one per proposal)
+                const size_t cr = corr_compact ? row : src;
+                b[0] += corr[cr * 3 + 0];
+                b[2] += corr[cr * 3 + 1];
+                b[6] += corr[cr * 3 + 2];
             }
             const int c = col < 7 ? col : col - 9;
 #pragma unroll
@@ -656,18 +658,36 @@ int dodt_max_fg_logit(dodt_ctx* ctx, const float* d_logits, int n_cls, int n, co
     return DODT_OK;
 }
 
-int dodt_pack_detections(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores,
-                         const float* d_orientations, const float* d_corr_offsets,
-                         const int32_t* d_sel, const int32_t* d_count, int max_det,
-                         float frame_mark, float* d_rec_out, int32_t* d_count_out) {
+namespace {
+int launch_pack_detections(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores,
+                           const float* d_orientations, const float* d_corr_offsets, int corr_compact,
+                           const int32_t* d_sel, const int32_t* d_count, int max_det,
+                           float frame_mark, float* d_rec_out, int32_t* d_count_out) {
     DODT_REQUIRE(ctx && d_boxes_3d && d_scores && d_sel && d_count && d_rec_out && d_count_out &&
                      max_det > 0,
                  "dodt_pack_detections: bad argument");
     hipLaunchKernelGGL(pack_detections_kernel, dim3(dodt::ceil_div(max_det * 17, 256)), dim3(256),
                        0, ctx->stream, d_boxes_3d, d_scores, d_orientations, d_corr_offsets, d_sel,
-                       d_count, max_det, frame_mark, d_rec_out, d_count_out);
+                       d_count, max_det, frame_mark, d_rec_out, d_count_out, corr_compact);
     DODT_LAUNCH_CHECK();
     return DODT_OK;
+}
+}  // namespace
+
+int dodt_pack_detections(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores,
+                         const float* d_orientations, const float* d_corr_offsets,
+                         const int32_t* d_sel, const int32_t* d_count, int max_det,
+                         float frame_mark, float* d_rec_out, int32_t* d_count_out) {
+    return launch_pack_detections(ctx, d_boxes_3d, d_scores, d_orientations, d_corr_offsets, 0, d_sel, d_count,
+                                  max_det, frame_mark, d_rec_out, d_count_out);
+}
+
+int dodt_pack_detections_compact(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores,
+                                 const float* d_orientations, const float* d_det_offsets,
+                                 const int32_t* d_sel, const int32_t* d_count, int max_det,
+                                 float frame_mark, float* d_rec_out, int32_t* d_count_out) {
+    return launch_pack_detections(ctx, d_boxes_3d, d_scores, d_orientations, d_det_offsets, 1, d_sel, d_count,
+                                  max_det, frame_mark, d_rec_out, d_count_out);
 }
 
 int dodt_angle_vector_to_orientation(dodt_ctx* ctx, const float* d_angle_vectors, int n,

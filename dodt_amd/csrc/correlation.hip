@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "common.h"
+#include "crop_coords.h"
 #include "lds_dma.h"
 
 namespace {
@@ -229,9 +230,11 @@ constexpr int kSpLds = kSpP * kSpP * kC * 4;
 template <int HALVES>
 __global__ void __launch_bounds__(256 * HALVES, 2 * HALVES)
 correlation_sp_kernel(const float* __restrict__ A, const float* __restrict__ B, int H, int W, int d, int pad,
-                      int OH, int OW, const int* __restrict__ tile_list, int n_tiles, float* __restrict__ out,
-                      int* __restrict__ stamps) {
+                      int OH, int OW, const int* __restrict__ tile_list, int n_tiles,
+                      const int* __restrict__ d_n_tiles, float* __restrict__ out, int* __restrict__ stamps) {
     constexpr int GW = 5, K = GW * GW, S2 = 2, QH = kC / 4 / HALVES;     // QH: 16-byte quads a lane takes of a pixel
+    // (a list made on the device, dodt_correlation_tiles: its length is there too; n_tiles is then its capacity)
+    if (d_n_tiles) n_tiles = min(n_tiles, max(*d_n_tiles, 0));
     constexpr int NW = 4 * HALVES;                                      // waves
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
@@ -441,6 +444,140 @@ int sp_tile_list(dodt_ctx* ctx, int tiles_y, int tiles_x, const int** out) {
     return DODT_OK;
 }
 
+// the one-pass kernel over `n` listed tiles (d_n_tiles: NULL, or the device's count of them, <= n)
+int launch_sp(dodt_ctx* ctx, const float* d_a, const float* d_b, int H, int W, int max_displacement, int pad,
+              int OH, int OW, const int* d_list, int n, const int* d_n_tiles, float* d_out) {
+    static const int halves = getenv("DODT_CORR_HALVES") && atoi(getenv("DODT_CORR_HALVES")) == 2 ? 2 : 1;
+    static bool prepared = false;
+    if (!prepared) {
+        DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&correlation_sp_kernel<1>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, kSpLds));
+        DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&correlation_sp_kernel<2>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, kSpLds));
+        prepared = true;
+    }
+    // two resident workgroups per CU, a multiple of 8 (an equal share per XCD), no more than there are tiles
+    static const int grid_env = getenv("DODT_CORR_GRID") ? atoi(getenv("DODT_CORR_GRID")) : 0;   // (tools/: A/B)
+    int grid = grid_env > 0 ? grid_env / 8 * 8 : 2 * ctx->num_cus / 8 * 8;
+    if (grid > 8 * dodt::ceil_div(n, 8)) grid = 8 * dodt::ceil_div(n, 8);
+    static const bool want_stamps = getenv("DODT_CORR_STAMPS") != nullptr;
+    static int* d_stamps = nullptr;
+    if (want_stamps && !d_stamps) {
+        DODT_HIP_CHECK(hipMalloc(&d_stamps, 64 * sizeof(int)));
+        DODT_HIP_CHECK(hipMemset(d_stamps, 0, 64 * sizeof(int)));
+    }
+    if (halves == 2)
+        hipLaunchKernelGGL(correlation_sp_kernel<2>, dim3(grid), dim3(512), kSpLds, ctx->stream,
+                           d_a, d_b, H, W, max_displacement, pad, OH, OW, d_list, n, d_n_tiles, d_out, d_stamps);
+    else
+        hipLaunchKernelGGL(correlation_sp_kernel<1>, dim3(grid), dim3(256), kSpLds, ctx->stream,
+                           d_a, d_b, H, W, max_displacement, pad, OH, OW, d_list, n, d_n_tiles, d_out, d_stamps);
+    DODT_LAUNCH_CHECK();
+    if (want_stamps) {
+        int h[64];
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);
+        fprintf(stderr, "[dodt] correlation, workgroup 9, us per phase: wait copies | barrier | arithmetic | barrier | "
+                        "early copies + outputs to LDS | stores | barrier + late copies\n");
+        for (int t = 0; t < 4; ++t) {
+            fprintf(stderr, "[dodt]   tile %d:", t);
+            for (int k = 0; k < 7; ++k) fprintf(stderr, " %6.2f", (h[t * 8 + k + 1] - h[t * 8 + k]) / 100.0);
+            fprintf(stderr, "   next tile's top +%.2f\n", (h[(t + 1) * 8] - h[t * 8]) / 100.0);
+        }
+    }
+    return DODT_OK;
+}
+
+// ---- the tiles a set of crops reads (the T branch at the kept detections only) -----------------------------------------
+// One workgroup.  For every listed box: the pixel rectangle its crop's samples can read -- floor of the smallest
+// sample coordinate to floor of the largest plus one (the bilinear taps), clipped to the map, then one pixel wider on
+// every side: a superset on purpose, so that no rounding of a coordinate can make crop_kernel read a tile that was
+// not computed.  The coordinates are crop_kernel's own (crop_coords.h).  The rectangle's tiles are flagged in LDS at
+// their position on the super-block curve (plain stores of the same value), and the flags are compacted in that order
+// into the list correlation_sp_kernel walks: the XCD / super-block order of the full map, restricted to the list.
+constexpr int kListThreads = 256;
+constexpr int kListMaxTiles = 8192;       // flags in LDS (the 700 x 800 map has 2200 tiles)
+
+__global__ void __launch_bounds__(kListThreads)
+corr_tile_list_kernel(int OH, int OW, const float* __restrict__ boxes, int n_boxes, const int* __restrict__ box_idx,
+                      int n, const int* __restrict__ d_n, int ch, int cw, const int* __restrict__ curve,
+                      int* __restrict__ list, int* __restrict__ d_count) {
+    __shared__ int flag[kListMaxTiles];
+    __shared__ int part[kListThreads];
+    __shared__ int4 rect[kListThreads];
+    const int tid = threadIdx.x;
+    const int tiles_y = (OH + kSpT - 1) / kSpT, tiles_x = (OW + kSpT - 1) / kSpT, total = tiles_y * tiles_x;
+    for (int t = tid; t < total; t += kListThreads) flag[t] = 0;
+    __syncthreads();
+    const int lim = d_n ? min(max(*d_n, 0), n) : n;
+    // the sample range of one axis as a clipped, widened pixel range [lo, hi]; false: no sample has a coordinate
+    auto range = [](float a, float b, int size, int crop, int& lo, int& hi) {
+        float mn = 3.0e38f, mx = -3.0e38f;
+        for (int i = 0; i < crop; ++i) {
+            const float v = dodt::crop_coord(a, b, size, crop, i);
+            if (v == v) { mn = fminf(mn, v); mx = fmaxf(mx, v); }
+        }
+        if (mn > mx) return false;
+        // (clamped before the conversion: a far-away box has coordinates no int holds)
+        const float cap = (float)size + 1.0f;
+        lo = (int)floorf(fminf(fmaxf(mn, -2.0f), cap)) - 1;
+        hi = (int)floorf(fminf(fmaxf(mx, -4.0f), cap)) + 2;
+        lo = max(lo, 0);
+        hi = min(hi, size - 1);
+        return lo <= hi;
+    };
+    // The boxes' rectangles first, one box per lane (its index, its box and its 14 coordinates: one memory latency for
+    // all of them), as tile ranges in LDS; then one wave per box flags that box's tiles, a tile per lane.
+    for (int base = 0; base < lim; base += kListThreads) {
+        const int j = base + tid;
+        int4 r = make_int4(0, -1, 0, -1);                   // (ty0, ty1, tx0, tx1): empty
+        if (j < lim) {
+            const int src = box_idx ? box_idx[j] : j;
+            if (src >= 0 && src < n_boxes) {                // (crop_kernel writes zeros for any other row)
+                const float4 bx = reinterpret_cast<const float4*>(boxes)[src];
+                int y_lo, y_hi, x_lo, x_hi;
+                if (range(bx.x, bx.z, OH, ch, y_lo, y_hi) && range(bx.y, bx.w, OW, cw, x_lo, x_hi))
+                    r = make_int4(y_lo / kSpT, y_hi / kSpT, x_lo / kSpT, x_hi / kSpT);
+            }
+        }
+        rect[tid] = r;
+        __syncthreads();
+        const int here = min(lim - base, kListThreads);
+        for (int k = tid / 64; k < here; k += kListThreads / 64) {
+            const int4 q = rect[k];
+            const int rw = q.w - q.z + 1, cnt = (q.y - q.x + 1) * rw;      // (empty: cnt <= 0)
+            for (int t = tid % 64; t < cnt; t += 64) {
+                const int ty = q.x + t / rw, tx = q.z + t % rw;
+                // position on the curve (sp_tile_list): 8 x 8-tile blocks in raster order, raster order inside a block
+                const int by = ty / 8 * 8, bxs = tx / 8 * 8;
+                const int bh = min(8, tiles_y - by), bw = min(8, tiles_x - bxs);
+                flag[by * tiles_x + bxs * bh + (ty - by) * bw + (tx - bxs)] = 1;
+            }
+        }
+        __syncthreads();                                    // (rect is rewritten by the next 256 boxes)
+    }
+    // compaction in curve order: a contiguous run of positions per lane, the runs' counts summed by one lane
+    const int run = (total + kListThreads - 1) / kListThreads;
+    const int p0 = min(tid * run, total), p1 = min(p0 + run, total);
+    int mine = 0;
+    for (int p = p0; p < p1; ++p) mine += flag[p];
+    part[tid] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0;
+        for (int t = 0; t < kListThreads; ++t) {
+            const int c = part[t];
+            part[t] = acc;
+            acc += c;
+        }
+        *d_count = acc;
+    }
+    __syncthreads();
+    int o = part[tid];
+    for (int p = p0; p < p1; ++p)
+        if (flag[p]) list[o++] = curve[p];
+}
+
 // ---- any other displacement grid (<= 32 displacements): one pixel per lane, a 16 x 16 tile, the
 //      neighbourhood padded to 20 floats per pixel; the form the fast kernel above grew out of -----------
 constexpr int kT = 16;        // tile edge
@@ -556,45 +693,8 @@ extern "C" int dodt_correlation(dodt_ctx* ctx, const float* d_a, const float* d_
         const int ty = dodt::ceil_div(OH, kSpT), tx = dodt::ceil_div(OW, kSpT);
         const int* d_list = nullptr;
         if (int rc = sp_tile_list(ctx, ty, tx, &d_list)) return rc;
-        static const int halves = getenv("DODT_CORR_HALVES") && atoi(getenv("DODT_CORR_HALVES")) == 2 ? 2 : 1;
-        static bool prepared = false;
-        if (!prepared) {
-            DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&correlation_sp_kernel<1>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kSpLds));
-            DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&correlation_sp_kernel<2>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kSpLds));
-            prepared = true;
-        }
-        const int n = ty * tx;
-        // two resident workgroups per CU, a multiple of 8 (an equal share per XCD), no more than there are tiles
-        static const int grid_env = getenv("DODT_CORR_GRID") ? atoi(getenv("DODT_CORR_GRID")) : 0;   // (tools/: A/B)
-        int grid = grid_env > 0 ? grid_env / 8 * 8 : 2 * ctx->num_cus / 8 * 8;
-        if (grid > 8 * dodt::ceil_div(n, 8)) grid = 8 * dodt::ceil_div(n, 8);
-        static const bool want_stamps = getenv("DODT_CORR_STAMPS") != nullptr;
-        static int* d_stamps = nullptr;
-        if (want_stamps && !d_stamps) {
-            DODT_HIP_CHECK(hipMalloc(&d_stamps, 64 * sizeof(int)));
-            DODT_HIP_CHECK(hipMemset(d_stamps, 0, 64 * sizeof(int)));
-        }
-        if (halves == 2)
-            hipLaunchKernelGGL(correlation_sp_kernel<2>, dim3(grid), dim3(512), kSpLds, ctx->stream,
-                               d_a, d_b, H, W, max_displacement, pad, OH, OW, d_list, n, d_out, d_stamps);
-        else
-            hipLaunchKernelGGL(correlation_sp_kernel<1>, dim3(grid), dim3(256), kSpLds, ctx->stream,
-                               d_a, d_b, H, W, max_displacement, pad, OH, OW, d_list, n, d_out, d_stamps);
-        DODT_LAUNCH_CHECK();
-        if (want_stamps) {
-            int h[64];
-            (void)hipStreamSynchronize(ctx->stream);
-            (void)hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost);
-            fprintf(stderr, "[dodt] correlation, workgroup 9, us per phase: wait copies | barrier | arithmetic | barrier | "
-                            "early copies + outputs to LDS | stores | barrier + late copies\n");
-            for (int t = 0; t < 4; ++t) {
-                fprintf(stderr, "[dodt]   tile %d:", t);
-                for (int k = 0; k < 7; ++k) fprintf(stderr, " %6.2f", (h[t * 8 + k + 1] - h[t * 8 + k]) / 100.0);
-                fprintf(stderr, "   next tile's top +%.2f\n", (h[(t + 1) * 8] - h[t * 8]) / 100.0);
-            }
-        }
+        if (int rc = launch_sp(ctx, d_a, d_b, H, W, max_displacement, pad, OH, OW, d_list, ty * tx, nullptr, d_out))
+            return rc;
         return DODT_OK;
     }
     const int R = r * stride_2;
@@ -617,4 +717,47 @@ extern "C" int dodt_correlation(dodt_ctx* ctx, const float* d_a, const float* d_
     if (int rc = go(&correlation_kernel<2, 16, 2>, 16)) return rc;
     DODT_LAUNCH_CHECK();
     return DODT_OK;
+}
+
+namespace {
+// the shapes the one-pass kernel takes (its tile coordinates are 16 bits, its byte offsets 31)
+bool sp_ok(int H, int W) {
+    return (size_t)H * W * kC * 4 < (1ull << 31) && H < 65536 * kSpT && W < 65536 * kSpT;
+}
+}  // namespace
+
+extern "C" int dodt_correlation_tile_list(dodt_ctx* ctx, int OH, int OW, const float* d_boxes, int n_boxes,
+                                          const int32_t* d_box_idx, int n, const int32_t* d_n, int crop_h,
+                                          int crop_w, int32_t* d_tiles, int capacity, int32_t* d_n_tiles) {
+    DODT_REQUIRE(ctx && d_tiles && d_n_tiles && (n == 0 || d_boxes), "dodt_correlation_tile_list: NULL argument");
+    DODT_REQUIRE(OH > 0 && OW > 0 && n >= 0 && n_boxes >= 0 && crop_h > 0 && crop_w > 0,
+                 "dodt_correlation_tile_list: bad sizes");
+    const int ty = dodt::ceil_div(OH, kSpT), tx = dodt::ceil_div(OW, kSpT);
+    DODT_REQUIRE(ty * tx <= kListMaxTiles && ty < 65536 && tx < 65536,
+                 "dodt_correlation_tile_list: %d x %d tiles, at most %d", ty, tx, kListMaxTiles);
+    DODT_REQUIRE(capacity >= ty * tx, "dodt_correlation_tile_list: room for %d tiles, the map has %d", capacity,
+                 ty * tx);
+    const int* d_curve = nullptr;
+    if (int rc = sp_tile_list(ctx, ty, tx, &d_curve)) return rc;
+    hipLaunchKernelGGL(corr_tile_list_kernel, dim3(1), dim3(kListThreads), 0, ctx->stream, OH, OW, d_boxes, n_boxes,
+                       d_box_idx, n, d_n, crop_h, crop_w, d_curve, d_tiles, d_n_tiles);
+    DODT_LAUNCH_CHECK();
+    return DODT_OK;
+}
+
+extern "C" int dodt_correlation_tiles(dodt_ctx* ctx, const float* d_a, const float* d_b, int H, int W, int C,
+                                      int max_displacement, int stride_2, int pad, const int32_t* d_tiles,
+                                      int capacity, const int32_t* d_n_tiles, float* d_out) {
+    DODT_REQUIRE(ctx && d_a && d_b && d_out && d_tiles && d_n_tiles, "dodt_correlation_tiles: NULL argument");
+    DODT_REQUIRE(C == kC, "dodt_correlation_tiles: C = %d, only %d channels are supported", C, kC);
+    DODT_REQUIRE(H > 0 && W > 0 && max_displacement >= 0 && stride_2 >= 1 && pad >= 0 && capacity >= 0,
+                 "dodt_correlation_tiles: bad sizes");
+    const int OH = H + 2 * pad - 2 * max_displacement, OW = W + 2 * pad - 2 * max_displacement;
+    DODT_REQUIRE(OH >= 1 && OW >= 1, "dodt_correlation_tiles: empty output");
+    if (!(stride_2 == 2 && max_displacement / stride_2 == 2 && sp_ok(H, W))) {
+        dodt::set_error("dodt_correlation_tiles: only the 5 x 5 grid of displacements two pixels apart");
+        return DODT_ERR_UNSUPPORTED;
+    }
+    if (capacity == 0) return DODT_OK;
+    return launch_sp(ctx, d_a, d_b, H, W, max_displacement, pad, OH, OW, d_tiles, capacity, d_n_tiles, d_out);
 }

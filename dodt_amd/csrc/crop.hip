@@ -7,7 +7,12 @@
 // eight adjacent lanes read one pixel's 128 contiguous bytes per tap (float4
 // each) and write 128 contiguous output bytes.  Float32, unfused, in TF's order:
 // top = tl + (tr - tl) * lx ; bot = bl + (br - bl) * lx ; out = top + (bot - top) * ly.
+//
+// Indexed form (dodt_crop_and_resize_indexed): output row j is the crop at box box_idx[j] -- the gather by NMS #2's
+// indices folded into the crop, for the T branch that runs at the kept detections only.  Same kernel, same
+// expressions: a row is bit-equal to the un-indexed crop of that box.
 #include "common.h"
+#include "crop_coords.h"
 
 namespace {
 
@@ -15,7 +20,7 @@ template <int VEC>
 __global__ void __launch_bounds__(256)
 crop_kernel(const float* __restrict__ img, int H, int W, int C, const float* __restrict__ boxes,
             int n, const int* __restrict__ d_n, int ch, int cw, float* __restrict__ out,
-            long long out_stride) {
+            long long out_stride, const int* __restrict__ box_idx, int n_boxes) {
     const int groups = C / VEC;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int lim = d_n ? min(*d_n, n) : n;
@@ -26,15 +31,15 @@ crop_kernel(const float* __restrict__ img, int H, int W, int C, const float* __r
     const int ix = (int)(r % cw); r /= cw;
     const int iy = (int)(r % ch);
     const int b = (int)(r / ch);
-    const float4 bx = reinterpret_cast<const float4*>(boxes)[b];
-    const float y1 = bx.x, x1 = bx.y, y2 = bx.z, x2 = bx.w;
+    // (indexed: row b of the output is box box_idx[b]; an index outside the boxes gives a zero crop)
+    const int src = box_idx ? box_idx[b] : b;
+    const bool have = !box_idx || (src >= 0 && src < n_boxes);
+    const float4 bx = have ? reinterpret_cast<const float4*>(boxes)[src] : make_float4(0.f, 0.f, 0.f, 0.f);
     const float hm1 = (float)(H - 1), wm1 = (float)(W - 1);
-    const float hs = (ch > 1) ? (y2 - y1) * hm1 / (float)(ch - 1) : 0.0f;
-    const float ws = (cw > 1) ? (x2 - x1) * wm1 / (float)(cw - 1) : 0.0f;
-    const float in_y = (ch > 1) ? y1 * hm1 + (float)iy * hs : 0.5f * (y1 + y2) * hm1;
-    const float in_x = (cw > 1) ? x1 * wm1 + (float)ix * ws : 0.5f * (x1 + x2) * wm1;
+    const float in_y = dodt::crop_coord(bx.x, bx.z, H, ch, iy);
+    const float in_x = dodt::crop_coord(bx.y, bx.w, W, cw, ix);
     float* o = out + (size_t)b * out_stride + (((size_t)iy * cw + ix) * C + (size_t)g * VEC);
-    const bool ok = (in_y >= 0.0f) && (in_y <= hm1) && (in_x >= 0.0f) && (in_x <= wm1);
+    const bool ok = have && (in_y >= 0.0f) && (in_y <= hm1) && (in_x >= 0.0f) && (in_x <= wm1);
     if (!ok) {  // also catches NaN coordinates
 #pragma unroll
         for (int k = 0; k < VEC; ++k) o[k] = 0.0f;
@@ -56,18 +61,9 @@ crop_kernel(const float* __restrict__ img, int H, int W, int C, const float* __r
     }
 }
 
-}  // namespace
-
-extern "C" int dodt_crop_and_resize(dodt_ctx* ctx, const float* d_image, int H, int W, int C,
-                                    const float* d_boxes, int n, const int32_t* d_n, int crop_h,
-                                    int crop_w, float* d_out) {
-    return dodt_crop_and_resize_strided(ctx, d_image, H, W, C, d_boxes, n, d_n, crop_h, crop_w, d_out,
-                                        (long long)crop_h * crop_w * C);
-}
-
-extern "C" int dodt_crop_and_resize_strided(dodt_ctx* ctx, const float* d_image, int H, int W, int C,
-                                            const float* d_boxes, int n, const int32_t* d_n, int crop_h,
-                                            int crop_w, float* d_out, long long out_box_stride) {
+int launch_crop(dodt_ctx* ctx, const float* d_image, int H, int W, int C, const float* d_boxes, int n,
+                const int32_t* d_n, int crop_h, int crop_w, float* d_out, long long out_box_stride,
+                const int32_t* d_box_idx, int n_boxes) {
     DODT_REQUIRE(ctx && d_image && d_out && (n == 0 || d_boxes),
                  "dodt_crop_and_resize: NULL argument");
     DODT_REQUIRE(H > 0 && W > 0 && C > 0 && crop_h > 0 && crop_w > 0 && n >= 0,
@@ -81,10 +77,34 @@ extern "C" int dodt_crop_and_resize_strided(dodt_ctx* ctx, const float* d_image,
     const int blocks = (int)((total + 255) / 256);
     if (vec == 4)
         hipLaunchKernelGGL(crop_kernel<4>, dim3(blocks), dim3(256), 0, ctx->stream, d_image, H, W,
-                           C, d_boxes, n, d_n, crop_h, crop_w, d_out, out_box_stride);
+                           C, d_boxes, n, d_n, crop_h, crop_w, d_out, out_box_stride, d_box_idx, n_boxes);
     else
         hipLaunchKernelGGL(crop_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, d_image, H, W,
-                           C, d_boxes, n, d_n, crop_h, crop_w, d_out, out_box_stride);
+                           C, d_boxes, n, d_n, crop_h, crop_w, d_out, out_box_stride, d_box_idx, n_boxes);
     DODT_LAUNCH_CHECK();
     return DODT_OK;
+}
+
+}  // namespace
+
+extern "C" int dodt_crop_and_resize(dodt_ctx* ctx, const float* d_image, int H, int W, int C,
+                                    const float* d_boxes, int n, const int32_t* d_n, int crop_h,
+                                    int crop_w, float* d_out) {
+    return dodt_crop_and_resize_strided(ctx, d_image, H, W, C, d_boxes, n, d_n, crop_h, crop_w, d_out,
+                                        (long long)crop_h * crop_w * C);
+}
+
+extern "C" int dodt_crop_and_resize_strided(dodt_ctx* ctx, const float* d_image, int H, int W, int C,
+                                            const float* d_boxes, int n, const int32_t* d_n, int crop_h,
+                                            int crop_w, float* d_out, long long out_box_stride) {
+    return launch_crop(ctx, d_image, H, W, C, d_boxes, n, d_n, crop_h, crop_w, d_out, out_box_stride, nullptr, n);
+}
+
+extern "C" int dodt_crop_and_resize_indexed(dodt_ctx* ctx, const float* d_image, int H, int W, int C,
+                                            const float* d_boxes, int n_boxes, const int32_t* d_box_idx, int n,
+                                            const int32_t* d_n, int crop_h, int crop_w, float* d_out,
+                                            long long out_box_stride) {
+    DODT_REQUIRE(d_box_idx && n_boxes >= 0, "dodt_crop_and_resize_indexed: NULL index list");
+    return launch_crop(ctx, d_image, H, W, C, d_boxes, n, d_n, crop_h, crop_w, d_out, out_box_stride, d_box_idx,
+                       n_boxes);
 }

@@ -181,6 +181,17 @@ def crop_and_resize(ctx, d_image, hwc, d_boxes, n, d_n, crop_hw, d_out, out_box_
         'dodt_crop_and_resize')
 
 
+def crop_and_resize_indexed(ctx, d_image, hwc, d_boxes, n_boxes, d_box_idx, n, d_n, crop_hw, d_out,
+                            out_box_stride=None):
+    """crop_and_resize whose output row j (j < min(n, *d_n)) is the crop at box d_box_idx[j] of the n_boxes boxes."""
+    if out_box_stride is None:
+        out_box_stride = int(crop_hw[0]) * int(crop_hw[1]) * int(hwc[2])
+    _lib.check(ctx.lib.dodt_crop_and_resize_indexed(
+        ctx.handle, _p(d_image), int(hwc[0]), int(hwc[1]), int(hwc[2]), _p(d_boxes), int(n_boxes),
+        _p(d_box_idx), int(n), _p(d_n), int(crop_hw[0]), int(crop_hw[1]), _p(d_out), int(out_box_stride)),
+        'dodt_crop_and_resize_indexed')
+
+
 def nms(ctx, d_boxes, d_scores, n, d_n, max_out, iou_threshold, d_sel, d_count):
     _lib.check(ctx.lib.dodt_nms(
         ctx.handle, _p(d_boxes), _p(d_scores), int(n), _p(d_n), int(max_out),
@@ -255,6 +266,15 @@ def pack_detections(ctx, d_boxes_3d, d_scores, d_sel, d_count, max_det, frame_ma
         'dodt_pack_detections')
 
 
+def pack_detections_compact(ctx, d_boxes_3d, d_scores, d_sel, d_count, max_det, frame_mark,
+                            d_rec, d_count_out, d_det_offsets=None, d_orientations=None):
+    """pack_detections with one row of offsets per detection: d_det_offsets (max_det, 3), row j for box d_sel[j]."""
+    _lib.check(ctx.lib.dodt_pack_detections_compact(
+        ctx.handle, _p(d_boxes_3d), _p(d_scores), _p(d_orientations), _p(d_det_offsets),
+        _p(d_sel), _p(d_count), int(max_det), float(frame_mark), _p(d_rec), _p(d_count_out)),
+        'dodt_pack_detections_compact')
+
+
 def fetch_i32_begin(ctx, d_src, n, slot):
     _lib.check(ctx.lib.dodt_fetch_i32_begin(ctx.handle, _p(d_src), int(n), int(slot)),
                'dodt_fetch_i32_begin')
@@ -271,6 +291,30 @@ def correlation(ctx, d_a, d_b, hwc, max_displacement, stride_2, pad, d_out):
     _lib.check(ctx.lib.dodt_correlation(
         ctx.handle, _p(d_a), _p(d_b), int(hwc[0]), int(hwc[1]), int(hwc[2]),
         int(max_displacement), int(stride_2), int(pad), _p(d_out)), 'dodt_correlation')
+
+
+def correlation_tile_list(ctx, out_hw, d_boxes, n_boxes, d_box_idx, n, d_n, crop_hw, d_tiles, capacity, d_n_tiles):
+    """The 16 x 16 tiles of an out_hw correlation map that crops at boxes d_box_idx[0 .. min(n, *d_n)) can read
+    (a superset), in the kernel's walking order, into d_tiles (capacity ints) and their number into d_n_tiles."""
+    _lib.check(ctx.lib.dodt_correlation_tile_list(
+        ctx.handle, int(out_hw[0]), int(out_hw[1]), _p(d_boxes), int(n_boxes), _p(d_box_idx), int(n), _p(d_n),
+        int(crop_hw[0]), int(crop_hw[1]), _p(d_tiles), int(capacity), _p(d_n_tiles)), 'dodt_correlation_tile_list')
+
+
+def correlation_tiles(ctx, d_a, d_b, hwc, max_displacement, stride_2, pad, d_tiles, capacity, d_n_tiles, d_out):
+    """correlation() over the listed tiles only; the rest of d_out is left as it is."""
+    _lib.check(ctx.lib.dodt_correlation_tiles(
+        ctx.handle, _p(d_a), _p(d_b), int(hwc[0]), int(hwc[1]), int(hwc[2]), int(max_displacement),
+        int(stride_2), int(pad), _p(d_tiles), int(capacity), _p(d_n_tiles), _p(d_out)), 'dodt_correlation_tiles')
+
+
+# the largest map correlation_tile_list takes, in tiles (its flags live in one workgroup's LDS: kListMaxTiles)
+CORR_TILE_LIST_MAX = 8192
+
+
+def correlation_tile_capacity(out_hw):
+    """Entries a tile list of an out_hw map needs."""
+    return -(-int(out_hw[0]) // 16) * -(-int(out_hw[1]) // 16)
 
 
 def mean_fusion(ctx, d_a, d_b, rows, d_n, row_floats, d_out):

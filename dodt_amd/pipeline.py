@@ -61,7 +61,7 @@ class FramePairPipeline(object):
                  image_wh=_config.KITTI_IMAGE_WH, n_points_max=120000, rpn_nms_size=1024,
                  pairs_per_step=1, side_streams=None, head_params=None, conv_dtype='f32',
                  head_dtype='f32', reuse_streams_of=None, tail_sets=None, temporal=None, tracker=None,
-                 bev_input_skip=True, bev_frame_tables=True):
+                 bev_input_skip=True, bev_frame_tables=True, t_branch_rows=None):
         """temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
         module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it.
         tracker: None, or dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3, classes=('Car',),
@@ -71,7 +71,24 @@ class FramePairPipeline(object):
         bev_input_skip: the fp32 BEV net skips the tiles that no BEV cell inside the camera's frustum reaches (their
         values depend on the weights alone, dodt_extractor_set_input_support); False: full tables.
         bev_frame_tables: with bev_input_skip, every step also filters those tables on the device by the cells that are
-        non-zero in its own BEV maps (dodt_extractor_set_frame_tables); False: the static tables alone."""
+        non-zero in its own BEV maps (dodt_extractor_set_frame_tables); False: the static tables alone.
+        t_branch_rows: the rows the T branch (correlation map, its crops, the correlation head) is computed for when the
+        pipeline computes its heads.  'proposals': all P proposals of a pair's frame 0, the map on the image stream
+        behind the image stack; fr[f]['corr_rois'] / ['corr_offsets'] then hold every proposal's row (inspection
+        outputs of this form only).  'detections': the <= MAX_DET boxes NMS #2 keeps, the only rows the records read --
+        behind frame 0's NMS #2 on its own stream: the map at the tiles those boxes' crops touch, the crops, the head at
+        MAX_DET rows (fr[f]['det_corr_rois'] / ['det_corr_offsets'], row j for box det_idx[j]); the same records, bit for
+        bit.  None (default): 'detections' when the records go to caller-owned memory (use_record_buffers /
+        use_record_ring called before the first run(): the streaming use, whose caller reads records and nothing else),
+        'proposals' otherwise.  The tile list of 'detections' is built in one workgroup's LDS, which holds a map of up to
+        ops.CORR_TILE_LIST_MAX 16 x 16 tiles (the 700 x 800 map has 2200): on a larger map None means 'proposals' and
+        'detections' is refused here.  t_branch_form() gives the form in use; the first run() fixes it.  Injected heads
+        keep their per-proposal offsets array whatever the argument."""
+        if t_branch_rows not in (None, 'proposals', 'detections'):
+            raise ValueError("t_branch_rows must be None, 'proposals' or 'detections'")
+        self.t_branch_rows = t_branch_rows
+        self._t_form = None                         # (the first run() fixes it, _resolve_t_branch)
+        self._caller_records = False
         self.ctx = ctx
         self.cfg = cfg
         self.p2 = np.asarray(p2, dtype=np.float64)
@@ -205,9 +222,12 @@ class FramePairPipeline(object):
                                             if self.fps == 2 else None)
                                        for _ in sides] for sides, _ in self.stream_sets]
             self.head_scratch = self.head_scratch_sets[0]
-            # the pairs' correlation maps, by step parity (written behind the image stack on its stream, see run())
-            self.corr_maps = [[ctx.empty((self.bev_fh, self.bev_fw, CORR_CH), f32) for _ in range(self.pairs)]
-                              for _ in range(2)] if self.fps == 2 else None
+            # the pairs' correlation maps, by step parity (written behind the image stack on its stream, see run();
+            # 'proposals' form only: made by _resolve_t_branch at the first run())
+            self.corr_maps = None
+            if t_branch_rows == 'detections' and self.corr_head is not None and not self._tile_list_fits():
+                raise ValueError("t_branch_rows='detections': the %d x %d map has more than %d tiles"
+                                 % (self.bev_fh, self.bev_fw, ops.CORR_TILE_LIST_MAX))
 
         # ---- work buffers ----------------------------------------------------------------
         FC = self.feat_c
@@ -324,11 +344,53 @@ class FramePairPipeline(object):
         frame = (pad_top + shape[0]) * row
         return [arr.offset(frame * f + pad_top * row, shape) for f in range(self.nf)]
 
+    def _tile_list_fits(self):
+        return ops.correlation_tile_capacity((self.bev_fh, self.bev_fw)) <= ops.CORR_TILE_LIST_MAX
+
+    def t_branch_form(self):
+        """'proposals' or 'detections': t_branch_rows, None resolved by the rule of __init__ -- as it stands now until
+        the first run(), as that run found it from then on."""
+        if self._t_form is not None:
+            return self._t_form
+        if self.t_branch_rows is not None:
+            return self.t_branch_rows
+        return 'detections' if self._caller_records and self._tile_list_fits() else 'proposals'
+
+    def _t_detections(self):
+        return self.corr_head is not None and self.t_branch_form() == 'detections'
+
+    def _resolve_t_branch(self):
+        """Fix the T branch's form at the first run() and make that form's buffers."""
+        if self._t_form is not None:
+            return
+        self._t_form = self.t_branch_form()
+        if self.corr_head is None:
+            return
+        ctx, f32, i32 = self.ctx, np.float32, np.int32
+        if self._t_form == 'proposals':
+            self.corr_maps = [[ctx.empty((self.bev_fh, self.bev_fw, CORR_CH), f32) for _ in range(self.pairs)]
+                              for _ in range(2)]
+            return
+        self.corr_tile_cap = ops.correlation_tile_capacity((self.bev_fh, self.bev_fw))
+        for scratch in self.head_scratch_sets:
+            for s in scratch:          # one tile list per side stream, beside its correlation map
+                s.update(corr_tiles=ctx.empty((self.corr_tile_cap,), i32), corr_ntiles=ctx.zeros((1,), i32))
+        for frames in self.fr2:
+            for f, b in enumerate(frames):
+                if f % 2 == 0:
+                    # row j: the crop / the offsets of box det_idx[j] (zeros behind each 7x7x25 crop, as in corr_rois;
+                    # the offsets start as zeros: DODT_PIPE_NO_CORR=1 leaves them so)
+                    b.update(det_corr_rois=ctx.zeros((MAX_DET, self.corr_head.in_ld), f32),
+                             det_corr_offsets=ctx.zeros((MAX_DET, 3), f32))
+        ctx.sync()
+
     def use_record_buffers(self, rec_ptrs, cnt_ptrs):
         """Write detection records into caller-owned device memory (e.g. buffers registered with
-        a communication library): R >= 2 of each, step k fills number k % R."""
+        a communication library): R >= 2 of each, step k fills number k % R.  Called before the first run() on a
+        pipeline built with t_branch_rows=None, it also selects the T branch's 'detections' form (see __init__)."""
         if len(rec_ptrs) < 2 or len(rec_ptrs) != len(cnt_ptrs):
             raise ValueError('use_record_buffers: at least two record and count buffers, as many of each')
+        self._caller_records = True
         self.rec2 = [self.ctx.wrap(p, (self.pairs, self.fps, MAX_DET, REC_COLS), np.float32)
                      for p in rec_ptrs]
         self.cnt2 = [self.ctx.wrap(p, (self.pairs, self.fps), np.int32) for p in cnt_ptrs]
@@ -464,6 +526,7 @@ class FramePairPipeline(object):
         main, nf = self.ctx, self.nf
         if (heads is None) != (self.rpn_head is not None):
             raise ValueError('pass `heads` exactly when the pipeline has no head_params')
+        self._resolve_t_branch()
         if recover is not None:
             if self.temporal is None:
                 raise ValueError('recover: the pipeline has no temporal module')
@@ -495,6 +558,7 @@ class FramePairPipeline(object):
         # call, in front of that prep, as before round 3)
         main.mark(self.CONV_DONE_MARK + cur)
         self.img_ctx.mark(self.CONV_DONE_MARK + cur)
+        # (t_branch_rows == 'proposals'; the 'detections' form has no work here, see _tail.)
         # The T branch's correlation map needs the two frames' BEV maps and nothing else: it runs HERE, behind the image
         # stack on its stream (the shorter of the two stacks), not inside a frame's tail, whose dependent launch chain
         # -- with its prep what bounds the bf16 step -- it made 50 us longer (DODT_PIPE_CORR_MAP=f1: round 4's first form,
@@ -651,7 +715,7 @@ class FramePairPipeline(object):
 
     def _corr_on_img(self):
         """The T branch's correlation runs behind the image stack (run()) instead of inside a frame's tail."""
-        return (self.rpn_head is not None and self.fps == 2 and len(self.sides) >= 2
+        return (self.rpn_head is not None and self.fps == 2 and len(self.sides) >= 2 and not self._t_detections()
                 and not os.environ.get('DODT_PIPE_NO_CORR') and os.environ.get('DODT_PIPE_CORR_ON_F1', '1') != '0'
                 and os.environ.get('DODT_PIPE_CORR_MAP', 'img') == 'img')
 
@@ -696,8 +760,11 @@ class FramePairPipeline(object):
         # correlates, crops and marks CORR_ROIS_MARK, which frame 0's stream waits for in front of the correlation
         # head.  The frames' launches are enqueued in that order: frame 0 up to its head, frame 1 whole, frame
         # 0's rest (DODT_PIPE_CORR_ON_F1=0: all of the branch on frame 0's stream).
+        # (t_branch_rows == 'detections': none of that -- the branch runs for the kept boxes only, behind frame 0's NMS #2
+        #  on frame 0's own stream, see frame())
+        t_det = computed and self._t_detections()
         split_t = computed and self.fps == 2 and ns >= 2 and not os.environ.get('DODT_PIPE_NO_CORR') \
-            and os.environ.get('DODT_PIPE_CORR_ON_F1', '1') != '0'
+            and os.environ.get('DODT_PIPE_CORR_ON_F1', '1') != '0' and not t_det
         corr_img = split_t and self._corr_on_img()
         fused_tail = os.environ.get('DODT_PIPE_FUSED_TAIL', '1') != '0'
 
@@ -771,7 +838,7 @@ class FramePairPipeline(object):
                                        scratch['fc'])
                 self._mark(c, st['step'], 'tail%d_fc2' % f)
                 yield 'head'
-                if pair and f % 2 == 0 and not os.environ.get('DODT_PIPE_NO_CORR'):
+                if pair and f % 2 == 0 and not os.environ.get('DODT_PIPE_NO_CORR') and not t_det:
                     # T branch: correlate the pair's BEV features, crop with frame 0's
                     # proposals (dt_rpn_model.py:324-331, dt_avod_model.py:267-273,300-304)
                     if corr_img:
@@ -809,6 +876,32 @@ class FramePairPipeline(object):
                     ops.angle_vector_to_orientation(c, h['angle_vectors'], self.P, b['top_count'],
                                                     b['orientations'])
             yield 'pack'
+            if t_det and pair and f % 2 == 0:
+                # T branch for the boxes NMS #2 kept: the tiles of the correlation map their crops can read, the map at
+                # those tiles, the crops at top_bev[det_idx], the correlation head at MAX_DET rows (the same GEMM kernels
+                # as at P rows: the same sums), and records that read row j of the offsets for box det_idx[j]
+                if not os.environ.get('DODT_PIPE_NO_CORR'):
+                    fb1 = feat['bev_feat'].offset(4 * bev_px * FC * (f + 1), bev_hw + (FC,))
+                    ops.correlation_tile_list(c, bev_hw, b['top_bev'], self.P, b['det_idx'], MAX_DET, b['det_count'],
+                                              (ROI, ROI), scratch['corr_tiles'], self.corr_tile_cap,
+                                              scratch['corr_ntiles'])
+                    ops.correlation_tiles(c, feat_b, fb1, bev_hw + (FC,), CORR_MAX_DISP, CORR_STRIDE2, CORR_PAD,
+                                          scratch['corr_tiles'], self.corr_tile_cap, scratch['corr_ntiles'],
+                                          scratch['corr_map'])
+                    self._mark(c, st['step'], 'tail%d_corrmap' % f)
+                    ops.crop_and_resize_indexed(c, scratch['corr_map'], bev_hw + (CORR_CH,), b['top_bev'], self.P,
+                                                b['det_idx'], MAX_DET, b['det_count'], (ROI, ROI),
+                                                b['det_corr_rois'], out_box_stride=self.corr_head.in_ld)
+                    self.corr_head.forward(c, b['det_corr_rois'], None, MAX_DET, b['det_count'],
+                                           [b['det_corr_offsets']], scratch['fc'])
+                ops.pack_detections_compact(
+                    c, b['boxes_3d'], b['det_scores'], b['det_idx'], b['det_count'], MAX_DET,
+                    float(f % self.fps),
+                    self.d_records.offset(4 * MAX_DET * REC_COLS * f, (MAX_DET, REC_COLS)),
+                    self.d_rec_counts.offset(4 * f, (1,), np.int32), d_det_offsets=b['det_corr_offsets'],
+                    d_orientations=b['orientations'] if self.box_4ca else None)
+                self._mark(c, st['step'], 'tail%d_end' % f)
+                return
             ops.pack_detections(
                 c, b['boxes_3d'], b['det_scores'], b['det_idx'], b['det_count'], MAX_DET,
                 float(f % self.fps),
@@ -821,6 +914,13 @@ class FramePairPipeline(object):
             for _ in g:
                 pass
 
+        if t_det and ns >= 2:
+            # the frames of a pair are independent chains on two streams: their launches alternate stage by stage
+            for f0 in range(0, nf, 2):
+                gens = [frame(f0), frame(f0 + 1)]
+                while gens:
+                    gens = [g for g in gens if next(g, None) is not None]
+            return
         if not split_t:
             for f in range(nf):
                 drain(frame(f))
@@ -885,7 +985,8 @@ class FramePairPipeline(object):
         counts = anchor_counts or self.last_anchor_counts
         return (sum(self.rpn_head.flops(a) for a in counts)
                 + self.nf * self.avod_head.flops(self.P)
-                + (self.pairs * self.corr_head.flops(self.P) if self.corr_head else 0.0))
+                + (self.pairs * self.corr_head.flops(MAX_DET if self._t_detections() else self.P)
+                   if self.corr_head else 0.0))
 
     def flops_per_pair(self):
         return self.flops_per_step() / self.pairs

@@ -390,6 +390,13 @@ int dodt_crop_and_resize(dodt_ctx* ctx, const float* d_image, int H, int W, int 
 int dodt_crop_and_resize_strided(dodt_ctx* ctx, const float* d_image, int H, int W, int C,
                                  const float* d_boxes, int n, const int32_t* d_n, int crop_h,
                                  int crop_w, float* d_out, long long out_box_stride);
+/* The strided form with a row index: row j of d_out (j < min(n, *d_n)) is the crop at box d_box_idx[j] of the
+ * n_boxes boxes -- the gather folded into the crop, no launch of its own.  Same kernel and float expressions:
+ * a row is bit-equal to the un-indexed crop of that box.  An index outside [0, n_boxes) gives a zero crop. */
+int dodt_crop_and_resize_indexed(dodt_ctx* ctx, const float* d_image, int H, int W, int C,
+                                 const float* d_boxes, int n_boxes, const int32_t* d_box_idx, int n,
+                                 const int32_t* d_n, int crop_h, int crop_w, float* d_out,
+                                 long long out_box_stride);
 
 /* ---- T branch: correlation of the two frames' BEV feature maps ------------------------
  * Stands behind avod/core/corr_layers/correlation.py:7-27 -> the Correlation custom op
@@ -399,6 +406,23 @@ int dodt_crop_and_resize_strided(dodt_ctx* ctx, const float* d_image, int H, int
  * W+2*pad-2*max_displacement, (2*(max_displacement/stride_2)+1)^2). */
 int dodt_correlation(dodt_ctx* ctx, const float* d_a, const float* d_b, int H, int W, int C,
                      int max_displacement, int stride_2, int pad, float* d_out);
+/* The map at the tiles a set of crops reads, for callers that read the map through those crops only (the T
+ * branch at the kept detections).
+ * dodt_correlation_tile_list: one launch.  For boxes d_box_idx[0 .. min(n, *d_n)) of d_boxes (n_boxes, 4) -- or
+ * boxes 0.. when d_box_idx is NULL -- flags the 16 x 16 tiles of the (OH, OW) map that meet the pixel rectangle a
+ * crop_h x crop_w crop of the box can read (floor of the smallest sample coordinate to floor of the largest + 1,
+ * clipped to the map, one pixel wider on every side; the coordinates are the crop kernel's own), and writes them
+ * to d_tiles (capacity >= the map's tile count) in the order the kernel walks the full map, their number to
+ * *d_n_tiles.
+ * dodt_correlation_tiles: dodt_correlation over d_tiles[0 .. min(capacity, *d_n_tiles)) only.  A listed tile is
+ * bit-equal to the full map's; nothing is written outside the listed tiles.  Only the configuration's grid
+ * (stride_2 2, max_displacement / stride_2 == 2); anything else is DODT_ERR_UNSUPPORTED. */
+int dodt_correlation_tile_list(dodt_ctx* ctx, int OH, int OW, const float* d_boxes, int n_boxes,
+                               const int32_t* d_box_idx, int n, const int32_t* d_n, int crop_h, int crop_w,
+                               int32_t* d_tiles, int capacity, int32_t* d_n_tiles);
+int dodt_correlation_tiles(dodt_ctx* ctx, const float* d_a, const float* d_b, int H, int W, int C,
+                           int max_displacement, int stride_2, int pad, const int32_t* d_tiles, int capacity,
+                           const int32_t* d_n_tiles, float* d_out);
 
 /* ---- dense heads: fully connected layers (fp32 MFMA) ------------------------------------
  * y[M][N] = act(x[M][K] . w[K][N] + bias[N]); stands behind slim.fully_connected / the 1x1
@@ -518,6 +542,12 @@ int dodt_pack_detections(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_
                          const float* d_orientations, const float* d_corr_offsets,
                          const int32_t* d_sel, const int32_t* d_count, int max_det,
                          float frame_mark, float* d_rec_out, int32_t* d_count_out);
+/* The same with one row of offsets per detection: d_det_offsets (max_det, 3), row j belongs to box d_sel[j]
+ * (the correlation head run at the kept detections only). */
+int dodt_pack_detections_compact(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores,
+                                 const float* d_orientations, const float* d_det_offsets,
+                                 const int32_t* d_sel, const int32_t* d_count, int max_det,
+                                 float frame_mark, float* d_rec_out, int32_t* d_count_out);
 /* Stage-2 decode (models/dt_avod_model.py:464-469,575-603):
  *   anchors_to_box_3d(fix_lw) -> tf_box_3d_to_box_4c -> + offsets ->
  *   tf_box_4c_to_box_3d -> tf_box_3d_to_anchor -> project_to_bev (metres) ->
