@@ -11,21 +11,27 @@ index-exact parity tests use.
 
 Frame pairs are independent (batch size 1 in the reference, no cross-pair state),
 so a step may carry several pairs: all their frames go through the conv stacks as
-one batch.  Streams: the two conv stacks each have their own (they run side by
-side); every frame has a side stream for its "prep" (points -> BEV maps, anchors, image
-preprocessing) and its "tail" (crops, heads, decode, NMS), so the single-workgroup
-stages (NMS scan) of different frames overlap (four streams in all at one pair per
-step: the hardware-queue budget of a process).  A frame's prep and tail share its side
-stream, so the order on that stream is prep k, tail k-1, prep k+1, ...: the prep of step
-k+1 is enqueued by run(k+1) behind the tail of step k-1 and in front of the convs of its own
-step (0.1 ms; it does NOT run under the convs of step k); what overlaps is the tail of step
-k with the convs of step k+1.  Inputs, feature maps, per-frame buffers and detection records
-are double-buffered by step parity for that, and `finish()` drains the last step.
+one batch.
+
+Streams (four at one pair per step: the hardware-queue budget of a process -- a fifth shares a queue
+with another one and runs behind its launches): `ctx`, the main stream, carries the BEV stack; `img_ctx`
+the image stack and, behind it, the 'img' placement's correlation maps, the temporal module and the
+tracker; every frame of a pair has a side stream (`sides`) for its "prep" (points -> BEV maps, anchors,
+image preprocessing) and its "tail" (crops, heads, decode, NMS, records), so the single-workgroup stages
+(NMS scan) of different frames overlap.  The order on a side stream is prep k, tail k-1, prep k+1, ...:
+run(k) enqueues the prep of step k behind the tail of step k-2 and in front of the convs of its own step
+(0.1 ms), then the tail of step k-1, which waits for that step's convs (CONV_DONE_MARK) and so runs under
+the convs of step k.  With look-ahead run(k) also enqueues the prep of step k+1, in front of the tail of
+step k-1.  Inputs, feature maps, per-frame buffers and detection records are double-buffered by step
+parity for that (what a prep leaves for its tail three deep), and `finish()` drains the last step.
+Where the T branch of a computed pair runs -- its placement -- is one value, resolved with the
+environment's switches by resolve_schedule() when the pipeline is built.
 Everything stays on the device; the only host round trip per step is the kept-anchor count
 of each frame, fetched one step after it was produced (the host runs one step ahead of the
 GPU and otherwise waits in that read).
 """
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -47,6 +53,66 @@ ROI = 7                  # avod_proposal_roi_crop_size
 CORR_MAX_DISP, CORR_STRIDE2, CORR_PAD = 5, 2, 5     # correlation_config; correlation.py:7
 CORR_CH = (2 * (CORR_MAX_DISP // CORR_STRIDE2) + 1) ** 2
 
+# Mark slots (Context.mark / wait_mark; slots below 64 are the timing marks of _mark):    recorded by -> waited for by
+PREP_DONE_MARK = 244    # .. 246, by step % 3: every side stream at the end of a step's prep (_prep) -> the main and the
+                        # image stream in front of that step's conv stacks (run)
+TAIL_DONE_MARK = 247    # every side stream at the end of a step's tail (run) -> the main stream (the step's records are
+                        # complete there; the next BEV stack of that parity overwrites maps the tail reads) and the image
+                        # stream (the same for the image net's maps; the temporal module and the tracker read the records)
+CORR_MAP_MARK = 248     # 249, by parity: the image stream behind a step's correlation maps (run, placement 'img')
+                        # -> frame 1's side stream in front of the T branch's crops (_pair_img)
+CONV_DONE_MARK = 250    # 251, by parity: the main and the image stream behind a step's stacks (run) -> the side streams in
+                        # front of that step's tail (_wait_convs) and of the look-ahead prep of the step after next (_prep);
+                        # the main stream's also -> the image stream in front of the correlation maps (run)
+PROPOSALS_MARK = 252    # frame 0's side stream where its proposals stand -> frame 1's in front of the T branch's crops
+CORR_ROIS_MARK = 253    # frame 1's side stream behind its share of the T branch -> frame 0's in front of what reads it
+
+
+class Schedule(namedtuple('Schedule', 'fused_tail no_tail no_corr no_rpn t_branch two_streams corr_map_img')):
+    """What resolve_schedule() found: the tail's elementwise runs as one launch each (fused_tail), tools/' switches that
+    leave work out (no_tail, no_corr, no_rpn), and what places the T branch once its form is known."""
+    __slots__ = ()
+
+    def t_placement(self, t_form):
+        """(placement, alternate) for the T branch's form, 'proposals' or 'detections'.  placement: where the branch
+        (correlation map, its crops, the correlation head) of a pair runs --
+        'none': nowhere (injected heads, single frames, DODT_PIPE_NO_CORR);
+        'detections': behind frame 0's NMS #2 on frame 0's stream, for the kept boxes;
+        'img': the map behind the image stack on its stream, crops and head on frame 1's stream;
+        'f1': map and crops on frame 1's stream, the head on frame 0's;
+        'f0': all of it on frame 0's stream (one side stream).
+        alternate: the launches of a pair's two frames alternate stage by stage ('detections' form on two streams: two
+        independent chains) instead of one frame after the other; 'img' and 'f1' have orders of their own."""
+        if not self.t_branch:
+            return 'none', False
+        if t_form == 'detections':
+            return ('none' if self.no_corr else 'detections'), self.two_streams
+        if self.no_corr:
+            return 'none', False
+        if not self.two_streams:
+            return 'f0', False
+        return ('img' if self.corr_map_img else 'f1'), False
+
+
+def resolve_schedule(environ, computed_heads, frames_per_sample, n_side_streams):
+    """The pipeline's schedule from the DODT_PIPE_* switches of `environ` (a mapping; None: the process's own) and how it
+    was built: the one place that reads them, once per pipeline.  DODT_PIPE_FUSED_TAIL=0: the tail's elementwise ops as
+    separate launches; DODT_PIPE_CORR_MAP other than 'img': placement 'f1' instead of 'img'; DODT_PIPE_NO_TAIL /
+    _NO_CORR / _NO_RPN (any non-empty value): tools/' steps without the tail / the T branch / the RPN head."""
+    if environ is None:
+        environ = os.environ
+    return Schedule(fused_tail=environ.get('DODT_PIPE_FUSED_TAIL', '1') != '0',
+                    no_tail=bool(environ.get('DODT_PIPE_NO_TAIL')), no_corr=bool(environ.get('DODT_PIPE_NO_CORR')),
+                    no_rpn=bool(environ.get('DODT_PIPE_NO_RPN')),
+                    t_branch=bool(computed_heads) and frames_per_sample == 2, two_streams=n_side_streams >= 2,
+                    corr_map_img=environ.get('DODT_PIPE_CORR_MAP', 'img') == 'img')
+
+
+# One tail's state (FramePairPipeline._tail): the step and its parity, every frame's buffers (its own + what its prep
+# left), feature-map views, kept-anchor count and head outputs (its own buffers when the pipeline computes them), and the
+# side streams' head scratch
+_TailState = namedtuple('_TailState', 'step cur fr feat counts heads scratch')
+
 
 class FramePairPipeline(object):
     """One GPU's pipeline over samples of the configuration: frame pairs for DODT
@@ -60,7 +126,7 @@ class FramePairPipeline(object):
                  r0_rect=_config.KITTI_R0_RECT, tr_velo_to_cam=_config.KITTI_TR_VELO_TO_CAM,
                  image_wh=_config.KITTI_IMAGE_WH, n_points_max=120000, rpn_nms_size=1024,
                  pairs_per_step=1, side_streams=None, head_params=None, conv_dtype='f32',
-                 head_dtype='f32', reuse_streams_of=None, tail_sets=None, temporal=None, tracker=None,
+                 head_dtype='f32', reuse_streams_of=None, temporal=None, tracker=None,
                  bev_input_skip=True, bev_frame_tables=True, t_branch_rows=None):
         """temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
         module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it.
@@ -99,34 +165,8 @@ class FramePairPipeline(object):
         self.fps = int(cfg.get('frames_per_sample', 2))
         if self.fps not in (1, 2):
             raise ValueError('frames_per_sample must be 1 or 2')
-        self.temporal = None
-        if temporal is not None:
-            if self.fps != 2:
-                raise ValueError('temporal: needs frame pairs (frames_per_sample == 2)')
-            t = dict(temporal)
-            tm = dict(n_frames=int(t.pop('n_frames')), threshold=float(t.pop('threshold', 0.1)),
-                      on_conflict=t.pop('on_conflict', 'raise'))
-            if t:
-                raise ValueError('temporal: unknown keys %s' % sorted(t))
-            if tm['on_conflict'] not in ('raise', 'next_best'):
-                raise ValueError("temporal: on_conflict must be 'raise' or 'next_best'")
-            if not 1 <= tm['n_frames'] <= 64:
-                raise ValueError('temporal: n_frames must be 1..64')
-            self.temporal = tm
-        self.tracker = None
-        if tracker is not None:
-            if self.fps != 2:
-                raise ValueError('tracker: needs frame pairs (frames_per_sample == 2)')
-            t = dict(tracker)
-            tk = dict(score_threshold=float(t.pop('score_threshold', 0.1)),
-                      high_threshold=float(t.pop('high_threshold', 0.5)),
-                      iou_threshold=float(t.pop('iou_threshold', 0.005)), t_min=int(t.pop('t_min', 3)),
-                      classes=tuple(t.pop('classes', ('Car',))), max_sequence_dets=int(t.pop('max_sequence_dets', 65536)))
-            if t:
-                raise ValueError('tracker: unknown keys %s' % sorted(t))
-            if tk['max_sequence_dets'] < 1:
-                raise ValueError('tracker: max_sequence_dets must be >= 1')
-            self.tracker = tk
+        self.temporal = self._temporal_args(temporal)
+        self.tracker = self._tracker_args(tracker)
         self.nf = self.fps * self.pairs                # frames per step
         self.bev_h, self.bev_w = cfg['bev_dims']
         self.img_h, self.img_w = cfg['img_dims']
@@ -134,31 +174,19 @@ class FramePairPipeline(object):
         self.bev_extents_flat = np.asarray(cfg['bev_extents'], np.float64).reshape(-1)
         self.bp = ops.make_bev_params(cfg, _config.velo_to_cam(r0_rect, tr_velo_to_cam),
                                       self.p2, self.image_wh)
-        # streams: conv stacks of the two nets side by side, per-frame work on its own.
-        # A second pipeline in the same process takes the first one's streams
-        # (`reuse_streams_of`): new ones would share hardware queues with them (see below).
-        # `tail_sets` (1, the default, or 2; DODT_PIPE_TAIL_SETS overrides): sets of side streams.  With one set a
-        # frame's stream carries prep k, tail k-1, prep k+1, tail k, ... in a row.  With two sets the steps alternate
-        # between them by parity (set p: prep k, tail k, prep k+2, tail k+2, ...): the tails of consecutive steps
-        # may overlap, every buffer a step touches is still used in stream order by its own parity's streams.
-        # Built in round 4 for the bf16 path, whose step looked bound by a tail's dependent launch chain, and
-        # measured: SLOWER in every mode (fp32 324 -> 276 pairs/s, bf16 convs + heads 836 -> 522: six streams
-        # instead of four) -- opt-in only.
-        if tail_sets is None:
-            tail_sets = 1
-        tail_sets = int(os.environ.get('DODT_PIPE_TAIL_SETS', tail_sets))
-        if tail_sets not in (1, 2):
-            raise ValueError('tail_sets must be 1 or 2')
+        # streams: conv stacks of the two nets side by side, per-frame work on its own.  A second pipeline in the same
+        # process takes the first one's streams (`reuse_streams_of`): new ones would share hardware queues with them
         if reuse_streams_of is not None:
-            self.img_ctx = reuse_streams_of.img_ctx
-            self.stream_sets = list(reuse_streams_of.stream_sets)
-            while len(self.stream_sets) < tail_sets:
-                self.stream_sets.append(self._make_side_streams(ctx, side_streams))
-            self.stream_sets = self.stream_sets[:tail_sets]
+            self.img_ctx, self.sides = reuse_streams_of.img_ctx, reuse_streams_of.sides
         else:
+            # one side stream per frame of a pair (or `side_streams`): ROCm maps a process's streams onto 4 hardware
+            # queues; a fifth stream shares a queue with another one and runs behind its launches (measured: 6 streams
+            # 164, 5 streams 180, 4 streams 191 pairs/s), so a frame's prep and tail share a stream
             self.img_ctx = device.Context(ctx.device_id)
-            self.stream_sets = [self._make_side_streams(ctx, side_streams) for _ in range(tail_sets)]
-        self.sides, self.preps = self.stream_sets[0]      # (the first set: what one-set callers see)
+            n_side = min(self.nf, 2) if side_streams is None else int(side_streams)
+            self.sides = [device.Context(ctx.device_id) for _ in range(max(n_side, 1))]
+        self.sched = resolve_schedule(None, head_params is not None, self.fps, len(self.sides))
+        self.placement = self.alternate = None      # (of the T branch: the first run() fixes them with its form)
         # ---- constants of the configuration, resident on the device ----------------
         boxes = gen.tile_anchors_3d(cfg['area_extents'], cfg['anchor_sizes'],
                                     cfg['anchor_stride'], cfg['ground_plane'])
@@ -197,12 +225,15 @@ class FramePairPipeline(object):
                        for _ in range(2)]
         self.in_img = [ctx.zeros((self.nf, self.img_net.PAD_TOP + self.img_h, self.img_w, 4), np.float32)
                        for _ in range(2)]
-        self.d_bev_in = self._views(self.in_bev[0], (self.bev_h, self.bev_w, cfg['bev_depth']), self.bev_pad)
+        # per-frame views of them, by parity
+        self.bev_in = [self._views(a, (self.bev_h, self.bev_w, cfg['bev_depth']), self.bev_pad) for a in self.in_bev]
+        self.img_in = [self._views(a, (self.img_h, self.img_w, 4), self.img_net.PAD_TOP) for a in self.in_img]
+        self.d_bev_in = self.bev_in[0]             # (of the most recently finished step)
 
         # ---- dense heads (weights shared, scratch per side stream) ------------------------
         f32, i32 = np.float32, np.int32
         N, P = self.n_all, self.P
-        self.rpn_head = self.avod_head = self.corr_head = None
+        self.rpn_head = self.avod_head = self.corr_head = self.head_scratch = None
         rep = cfg.get('box_representation', 'box_4ca')
         if rep not in ('box_4c', 'box_4ca'):
             raise NotImplementedError('Regression not implemented for %s' % rep)
@@ -215,13 +246,9 @@ class FramePairPipeline(object):
             if self.fps == 2:
                 self.corr_head = EarlyFusionFcLayers(ctx, head_params['corr'],
                                                      outputs=('off_out',), dtype=head_dtype)
-            # one scratch set per side stream of every set (the tails of two sets overlap)
-            self.head_scratch_sets = [[dict(rpn=self.rpn_head.make_scratch(N),
-                                            fc=self.avod_head.make_scratch(P),
-                                            corr_map=ctx.empty((self.bev_fh, self.bev_fw, CORR_CH), f32)
-                                            if self.fps == 2 else None)
-                                       for _ in sides] for sides, _ in self.stream_sets]
-            self.head_scratch = self.head_scratch_sets[0]
+            self.head_scratch = [dict(rpn=self.rpn_head.make_scratch(N), fc=self.avod_head.make_scratch(P),
+                                      corr_map=ctx.empty((self.bev_fh, self.bev_fw, CORR_CH), f32)
+                                      if self.fps == 2 else None) for _ in self.sides]
             # the pairs' correlation maps, by step parity (written behind the image stack on its stream, see run();
             # 'proposals' form only: made by _resolve_t_branch at the first run())
             self.corr_maps = None
@@ -236,6 +263,9 @@ class FramePairPipeline(object):
             bev_bneck=ctx.empty((self.nf, self.bev_fh, self.bev_fw, 1), f32),
             img_feat=ctx.empty((self.nf, self.img_fh, self.img_fw, FC), f32),
             img_bneck=ctx.empty((self.nf, self.img_fh, self.img_fw, 1), f32)) for _ in range(2)]
+        # per-frame views of them: feat_views[parity][frame][name]
+        self.feat_views = [[{name: a.offset(a.nbytes // self.nf * f, a.shape[1:]) for name, a in d.items()}
+                            for f in range(self.nf)] for d in self.feat]
         # what a step's prep leaves for its tail, THREE deep (step k: set k % 3): with look-ahead (run(...,
         # lookahead=)) the prep of step k + 1 is enqueued in front of the tail of step k - 1, which still reads
         # the set of its own step
@@ -297,9 +327,40 @@ class FramePairPipeline(object):
             self.img_ctx.wait_for(self.ctx)          # (the state's reset went on the main stream)
             self.last_sequence_tracks = None
         self.mark_steps = ()           # tools/pipe_marks.py: steps whose stages get timing marks
-        self.early_prep = os.environ.get('DODT_PIPE_EARLY_PREP', '1') != '0'
         self.marks = {}                # name -> (context, slot)
         ctx.sync()
+
+    def _temporal_args(self, temporal):
+        if temporal is None:
+            return None
+        if self.fps != 2:
+            raise ValueError('temporal: needs frame pairs (frames_per_sample == 2)')
+        t = dict(temporal)
+        tm = dict(n_frames=int(t.pop('n_frames')), threshold=float(t.pop('threshold', 0.1)),
+                  on_conflict=t.pop('on_conflict', 'raise'))
+        if t:
+            raise ValueError('temporal: unknown keys %s' % sorted(t))
+        if tm['on_conflict'] not in ('raise', 'next_best'):
+            raise ValueError("temporal: on_conflict must be 'raise' or 'next_best'")
+        if not 1 <= tm['n_frames'] <= 64:
+            raise ValueError('temporal: n_frames must be 1..64')
+        return tm
+
+    def _tracker_args(self, tracker):
+        if tracker is None:
+            return None
+        if self.fps != 2:
+            raise ValueError('tracker: needs frame pairs (frames_per_sample == 2)')
+        t = dict(tracker)
+        tk = dict(score_threshold=float(t.pop('score_threshold', 0.1)),
+                  high_threshold=float(t.pop('high_threshold', 0.5)),
+                  iou_threshold=float(t.pop('iou_threshold', 0.005)), t_min=int(t.pop('t_min', 3)),
+                  classes=tuple(t.pop('classes', ('Car',))), max_sequence_dets=int(t.pop('max_sequence_dets', 65536)))
+        if t:
+            raise ValueError('tracker: unknown keys %s' % sorted(t))
+        if tk['max_sequence_dets'] < 1:
+            raise ValueError('tracker: max_sequence_dets must be >= 1')
+        return tk
 
     def _mark(self, c, step, name):
         """Timing mark `name` of step `step` on context c (only for steps in mark_steps)."""
@@ -308,35 +369,6 @@ class FramePairPipeline(object):
             if slot < 64:
                 c.mark(slot)
                 self.marks['%d:%s' % (step, name)] = (c, slot)
-
-    def _make_side_streams(self, ctx, side_streams):
-        """One set of side streams: (tails, preps), one of each per frame of a pair (or `side_streams`)."""
-        n_side = min(self.nf, 2) if side_streams is None else int(side_streams)
-        hp = os.environ.get('DODT_PIPE_PRIO', '0') == '1'
-        sides = [device.Context(ctx.device_id, high_priority=hp)
-                 for _ in range(max(n_side, 1))]   # tails
-        # ROCm maps a process's streams onto 4 hardware queues; a fifth stream shares a queue
-        # with another one and runs behind its launches (measured: 6 streams 164, 5 streams
-        # 180, 4 streams 191 pairs/s), so by default a frame's prep and tail share a stream
-        mode = os.environ.get('DODT_PIPE_STREAMS', 'shared')
-        if mode == 'shared':      # frame f's prep and tail on one stream
-            preps = sides
-        elif mode == 'conv':      # (round 4, late) the preps on the two conv streams: frame 0's behind the BEV stack, frame 1's
-            # behind the image stack -- with look-ahead they are the NEXT step's, which those stacks' successors wait for
-            # anyway, and a frame's side stream carries its tails only (no new stream).  Measured: 996 against 1 015 pairs/s
-            # (bf16, same box) -- the stacks, not the side streams, then carry the preps' 0.2 ms; opt-in
-            preps = [ctx if i % 2 == 0 else self.img_ctx for i in range(len(sides))]
-        elif mode == 'one':       # all preps on one extra stream
-            one = device.Context(ctx.device_id, high_priority=hp)
-            preps = [one for _ in sides]
-        else:
-            preps = [device.Context(ctx.device_id, high_priority=hp)
-                     for _ in range(max(n_side, 1))]
-        return sides, preps
-
-    def _streams(self, cur):
-        """(tail streams, prep streams) of the steps with parity `cur`."""
-        return self.stream_sets[cur % len(self.stream_sets)]
 
     def _views(self, arr, shape, pad_top=0):
         """Per-frame views of a batch buffer whose frames are pad_top + shape[0] rows tall: the rows behind the pad."""
@@ -364,6 +396,7 @@ class FramePairPipeline(object):
         if self._t_form is not None:
             return
         self._t_form = self.t_branch_form()
+        self.placement, self.alternate = self.sched.t_placement(self._t_form)
         if self.corr_head is None:
             return
         ctx, f32, i32 = self.ctx, np.float32, np.int32
@@ -372,9 +405,8 @@ class FramePairPipeline(object):
                               for _ in range(2)]
             return
         self.corr_tile_cap = ops.correlation_tile_capacity((self.bev_fh, self.bev_fw))
-        for scratch in self.head_scratch_sets:
-            for s in scratch:          # one tile list per side stream, beside its correlation map
-                s.update(corr_tiles=ctx.empty((self.corr_tile_cap,), i32), corr_ntiles=ctx.zeros((1,), i32))
+        for s in self.head_scratch:    # one tile list per side stream, beside its correlation map
+            s.update(corr_tiles=ctx.empty((self.corr_tile_cap,), i32), corr_ntiles=ctx.zeros((1,), i32))
         for frames in self.fr2:
             for f, b in enumerate(frames):
                 if f % 2 == 0:
@@ -422,10 +454,9 @@ class FramePairPipeline(object):
 
     # ------------------------------------------------------------------------------------
     def _stage_from_host(self, k, h_points, n_points, h_images):
-        """Enqueue the copies of step k's raw frames from pinned host memory on its prep streams."""
+        """Enqueue the copies of step k's raw frames from pinned host memory on its frames' side streams."""
         cur = k & 1
-        _, preps = self._streams(cur)
-        ns = len(preps)
+        ns = len(self.sides)
         if not hasattr(self, 'stage'):
             H, W = self.image_wh[1], self.image_wh[0]
             self.stage = [[(self.ctx.empty((self.n_points_max, 4), np.float32),
@@ -433,7 +464,7 @@ class FramePairPipeline(object):
                           for _ in range(2)]
         d_pts, d_imgs = [], []
         for f in range(self.nf):
-            c = preps[f % ns]
+            c = self.sides[f % ns]
             dp, di = self.stage[cur][f]
             if n_points[f] > self.n_points_max:
                 raise ValueError('frame %d has more than n_points_max points' % f)
@@ -446,7 +477,7 @@ class FramePairPipeline(object):
     def run_from_host(self, h_points, n_points, h_images, heads=None, ego_motion=None, lookahead=None):
         """run() for raw frames still in (page-locked) host memory: lists of PinnedArray --
         points (n_max,4) float32 of which n_points[f] rows are valid, images (H,W,3) uint8.
-        The copies are enqueued on each frame's prep stream in front of its prep kernels, so
+        The copies are enqueued on each frame's side stream in front of its prep kernels, so
         they travel under the kernels of the previous step; the host does not wait for them
         (the caller keeps the pinned buffers untouched until that step's prep has run, e.g.
         by alternating two sets)."""
@@ -455,32 +486,27 @@ class FramePairPipeline(object):
         else:
             d_pts, d_imgs = self._stage_from_host(self.step_idx, h_points, n_points, h_images)
         if lookahead is not None:
-            # (the copies of step k + 1 go behind what its prep streams hold now, i.e. behind step k's prep)
+            # (the copies of step k + 1 go behind what its side streams hold now, i.e. behind step k's prep)
             la = tuple(lookahead) + (None,) * (4 - len(lookahead))
             nd_pts, nd_imgs = self._stage_from_host(self.step_idx + 1, la[0], la[1], la[2])
             lookahead = (nd_pts, la[1], nd_imgs, la[3])
         return self.run(d_pts, n_points, d_imgs, heads, ego_motion, lookahead)
 
-    PREP_DONE_MARK = 244        # mark slots 244..246 of the prep contexts: end of a step's prep, by step % 3
-
     def _prep(self, k, d_points, n_points, d_images, ego_motion, ahead):
-        """a0-a7 of step k: the data side of the reference's create_feed_dict, one frame per prep stream; its end
+        """a0-a7 of step k: the data side of the reference's create_feed_dict, one frame per side stream; its end
         is marked on those streams (PREP_DONE_MARK + k % 3).  `ahead`: enqueued by the previous step's run()
-        (look-ahead): the conv inputs of this parity were last read by the convs of step k - 2, which the prep
+        (look-ahead): the conv inputs of this parity were last read by the convs of step k - 2, which the side
         streams are told to wait for (with the usual order, behind the tail of step k - 2, that is implied)."""
-        nf = self.nf
         mean = (self.img_net._R_MEAN, self.img_net._G_MEAN, self.img_net._B_MEAN)
         cur = k & 1
-        sides, preps = self._streams(cur)
-        ns = len(sides)
-        bev_in = self._views(self.in_bev[cur], (self.bev_h, self.bev_w, self.cfg['bev_depth']), self.bev_pad)
-        img_in = self._views(self.in_img[cur], (self.img_h, self.img_w, 4), self.img_net.PAD_TOP)
+        ns = len(self.sides)
+        bev_in, img_in = self.bev_in[cur], self.img_in[cur]
         if ahead and k >= 2:
-            for c in set(preps):
-                c.wait_mark(self.ctx, self.CONV_DONE_MARK + cur)
-                c.wait_mark(self.img_ctx, self.CONV_DONE_MARK + cur)
-        for f in range(nf):
-            c, b = preps[f % ns], self.prep3[k % 3][f]
+            for c in self.sides:
+                c.wait_mark(self.ctx, CONV_DONE_MARK + cur)
+                c.wait_mark(self.img_ctx, CONV_DONE_MARK + cur)
+        for f in range(self.nf):
+            c, b = self.sides[f % ns], self.prep3[k % 3][f]
             self._mark(c, k, 'prep%d_start' % f)
             bp = self.bp
             if ego_motion is not None and self.fps == 2 and f % 2 == 1 \
@@ -496,8 +522,8 @@ class FramePairPipeline(object):
             ops.img_preprocess(c, d_images[f], (self.image_wh[1], self.image_wh[0]),
                                (self.img_h, self.img_w), 4, mean, img_in[f])
             self._mark(c, k, 'prep%d_end' % f)
-        for c in set(preps):
-            c.mark(self.PREP_DONE_MARK + k % 3)
+        for c in self.sides:
+            c.mark(PREP_DONE_MARK + k % 3)
         self.prepped = k
 
     def run(self, d_points, n_points, d_images, heads=None, ego_motion=None, lookahead=None, recover=None):
@@ -523,7 +549,7 @@ class FramePairPipeline(object):
         detections of the PREVIOUS step are complete on the main stream when this returns
         (self.d_records / self.fr / self.last_anchor_counts then describe that step);
         call finish() after the last step (run(); finish() is the unpipelined form)."""
-        main, nf = self.ctx, self.nf
+        main, img = self.ctx, self.img_ctx
         if (heads is None) != (self.rpn_head is not None):
             raise ValueError('pass `heads` exactly when the pipeline has no head_params')
         self._resolve_t_branch()
@@ -535,43 +561,34 @@ class FramePairPipeline(object):
             n = self.temporal['n_frames']
             # slot k % R was last read by M of step k - R, enqueued on `main` before this copy
             self.ego2[self.step_idx % len(self.rec2)].upload(np.stack([ops.temporal_ego(e, n) for e in recover]))
-        cur = self.step_idx & 1
-        sides, preps = self._streams(cur)
-        ns = len(sides)
-        fr, feat = self.fr2[cur], self.feat[cur]
         k = self.step_idx
+        cur = k & 1
+        feat = self.feat[cur]
         if self.prepped != k:      # (else: enqueued by the previous call's look-ahead)
             self._prep(k, d_points, n_points, d_images, ego_motion, ahead=False)
-        for c in set(preps):
-            main.wait_mark(c, self.PREP_DONE_MARK + k % 3)
-            self.img_ctx.wait_mark(c, self.PREP_DONE_MARK + k % 3)
+        for c in self.sides:
+            main.wait_mark(c, PREP_DONE_MARK + k % 3)
+            img.wait_mark(c, PREP_DONE_MARK + k % 3)
         # -- a8-a10: conv stacks, all frames per launch, the two nets side by side --------
         self._mark(main, k, 'bev_start')
-        self._mark(self.img_ctx, k, 'img_start')
+        self._mark(img, k, 'img_start')
         self.bev_net.forward_device_padded(self.in_bev[cur], feat['bev_feat'], feat['bev_bneck'])
         self.img_net.forward_device_padded(self.in_img[cur], feat['img_feat'], feat['img_bneck'])
         self._mark(main, k, 'bev_end')
-        self._mark(self.img_ctx, k, 'img_end')
+        self._mark(img, k, 'img_end')
         # The tail of THIS step (next call) starts when these convs are done.  The point is marked now and waited
         # for when the tail is enqueued -- behind the NEXT step's prep on the same side stream, which therefore
-        # runs under these convs instead of behind them (DODT_PIPE_EARLY_PREP=0: the wait goes in at the end of this
-        # call, in front of that prep, as before round 3)
-        main.mark(self.CONV_DONE_MARK + cur)
-        self.img_ctx.mark(self.CONV_DONE_MARK + cur)
-        # (t_branch_rows == 'proposals'; the 'detections' form has no work here, see _tail.)
-        # The T branch's correlation map needs the two frames' BEV maps and nothing else: it runs HERE, behind the image
-        # stack on its stream (the shorter of the two stacks), not inside a frame's tail, whose dependent launch chain
-        # -- with its prep what bounds the bf16 step -- it made 50 us longer (DODT_PIPE_CORR_MAP=f1: round 4's first form,
-        # map and crops on frame 1's stream between its crops and its head, the correlation head on frame 0's)
-        if self._corr_on_img():
-            self.img_ctx.wait_mark(main, self.CONV_DONE_MARK + cur)
-            bev_hw, px = (self.bev_fh, self.bev_fw), self.bev_fh * self.bev_fw
+        # runs under these convs instead of behind them
+        main.mark(CONV_DONE_MARK + cur)
+        img.mark(CONV_DONE_MARK + cur)
+        # Placement 'img': the T branch's correlation map needs the two frames' BEV maps and nothing else: it runs HERE,
+        # behind the image stack on its stream (the shorter of the two stacks), not inside a frame's tail, whose dependent
+        # launch chain -- with its prep what bounds the bf16 step -- it made 50 us longer
+        if self.placement == 'img':
+            img.wait_mark(main, CONV_DONE_MARK + cur)
             for pair in range(self.pairs):
-                fb0 = feat['bev_feat'].offset(4 * px * self.feat_c * (2 * pair), bev_hw + (self.feat_c,))
-                fb1 = feat['bev_feat'].offset(4 * px * self.feat_c * (2 * pair + 1), bev_hw + (self.feat_c,))
-                ops.correlation(self.img_ctx, fb0, fb1, bev_hw + (self.feat_c,), CORR_MAX_DISP, CORR_STRIDE2, CORR_PAD,
-                                self.corr_maps[cur][pair])
-            self.img_ctx.mark(self.CORR_MAP_MARK + cur)
+                self._correlation_map(img, cur, 2 * pair, self.corr_maps[cur][pair])
+            img.mark(CORR_MAP_MARK + cur)
         # -- the next step's prep, when the caller has given its inputs: in front of the previous step's tail ----
         if lookahead is not None:
             la = tuple(lookahead) + (None,) * (4 - len(lookahead))
@@ -580,29 +597,20 @@ class FramePairPipeline(object):
         if self.pending is not None:
             self._wait_convs(self.pending)
             self._tail(self.pending)
-            p_sides, p_preps = self._streams(self.pending['cur'])
-            for i, s in enumerate(p_sides):
-                # one event at the tail's end, three waiters: `main` (the previous step's records are complete there, and
-                # the BEV stack of the next step of that parity overwrites the maps the tail reads), the image stream (the
-                # same for the image net's maps: without look-ahead that wait is implied -- the next prep sits behind the
-                # tail on the side stream and the conv streams wait for the prep --, with look-ahead the prep is in front
-                # of it), and a prep stream of its own, if any.  (A mark after the tail's LAST READ of the image maps
-                # instead -- its stage-2 crops -- was measured: the extra event inside the tail's launch chain costs more
-                # than the earlier release returns, 868 against 899 pairs/s with the bf16 path; DODT_PIPE_IMG_WAIT=none is
-                # the racy form the first look-ahead build had, 907.)
-                s.mark(self.TAIL_DONE_MARK)
-                main.wait_mark(s, self.TAIL_DONE_MARK)
-                if os.environ.get('DODT_PIPE_IMG_WAIT', 'tail') != 'none':
-                    self.img_ctx.wait_mark(s, self.TAIL_DONE_MARK)
-                if p_preps[i] is not s:
-                    p_preps[i].wait_mark(s, self.TAIL_DONE_MARK)
+            for s in self.sides:
+                # one event at the tail's end, two waiters: `main` (the previous step's records are complete there, and
+                # the BEV stack of the next step of that parity overwrites the maps the tail reads) and the image stream
+                # (the same for the image net's maps: without look-ahead that wait is implied -- the next prep sits behind
+                # the tail on the side stream and the conv streams wait for the prep --, with look-ahead the prep is in
+                # front of it).  (A mark after the tail's LAST READ of the image maps instead -- its stage-2 crops -- was
+                # measured: the extra event inside the tail's launch chain costs more than the earlier release returns,
+                # 868 against 899 pairs/s with the bf16 path.)
+                s.mark(TAIL_DONE_MARK)
+                main.wait_mark(s, TAIL_DONE_MARK)
+                img.wait_mark(s, TAIL_DONE_MARK)
             self._temporal_step(self.pending)
             self._tracker_step(self.pending)
         self.pending = dict(cur=cur, heads=heads, step=k, rslot=k % len(self.rec2), recover=recover is not None)
-        if not self.early_prep:
-            for s in sides:
-                s.wait_for(main)
-                s.wait_for(self.img_ctx)
         self.step_idx += 1
         return cur
 
@@ -613,9 +621,8 @@ class FramePairPipeline(object):
             self._wait_convs(st)
             self._tail(st)
             self.pending = None
-        for sides, preps in self.stream_sets:
-            for s in set(sides) | set(preps):
-                self.ctx.wait_for(s)
+        for s in self.sides:
+            self.ctx.wait_for(s)
         self.ctx.wait_for(self.img_ctx)
         if st is not None and (self.temporal is not None or self.tracker is not None):
             self.img_ctx.wait_for(self.ctx)         # (the main stream has joined every stream, the last tails included)
@@ -633,9 +640,6 @@ class FramePairPipeline(object):
         if self.temporal is None:
             return
         T, r, c = self.temporal, st['rslot'], self.img_ctx
-        if os.environ.get('DODT_PIPE_IMG_WAIT', 'tail') == 'none':      # (then run() does not make it wait for them)
-            for s in self._streams(st['cur'])[0]:
-                c.wait_mark(s, self.TAIL_DONE_MARK)
         self._mark(c, st['step'], 'temporal_start')
         ops.interpolate_pairs(c, self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, T['n_frames'], T['threshold'],
                               T['on_conflict'], self.frames2[r], self.fcnt2[r], self.fst2[r],
@@ -652,9 +656,6 @@ class FramePairPipeline(object):
         if self.tracker is None:
             return
         r, c = st['rslot'], self.img_ctx
-        if self.temporal is None and os.environ.get('DODT_PIPE_IMG_WAIT', 'tail') == 'none':
-            for s in self._streams(st['cur'])[0]:
-                c.wait_mark(s, self.TAIL_DONE_MARK)
         self._mark(c, st['step'], 'tracker_start')
         self.track_state.track_records(self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, self.p2, self.image_wh, ctx=c)
         self._mark(c, st['step'], 'tracker_end')
@@ -710,259 +711,233 @@ class FramePairPipeline(object):
         return unpack_frames(self.d_frames.download(), self.d_frame_counts.download(),
                              self.d_frame_status.download(), self.temporal['on_conflict'])
 
-    CONV_DONE_MARK = 250        # mark slots 250, 251 of the conv contexts: end of a step's stacks, by parity
-    CORR_MAP_MARK = 248         # ... 248, 249 of the image context: the step's correlation maps stand, by parity
-
-    def _corr_on_img(self):
-        """The T branch's correlation runs behind the image stack (run()) instead of inside a frame's tail."""
-        return (self.rpn_head is not None and self.fps == 2 and len(self.sides) >= 2 and not self._t_detections()
-                and not os.environ.get('DODT_PIPE_NO_CORR') and os.environ.get('DODT_PIPE_CORR_ON_F1', '1') != '0'
-                and os.environ.get('DODT_PIPE_CORR_MAP', 'img') == 'img')
-
     def _wait_convs(self, st):
         """The side streams wait for the conv stacks of step `st` (marked at the end of its run())."""
-        if self.early_prep:
-            for s in self._streams(st['cur'])[0]:
-                s.wait_mark(self.ctx, self.CONV_DONE_MARK + st['cur'])
-                s.wait_mark(self.img_ctx, self.CONV_DONE_MARK + st['cur'])
+        for s in self.sides:
+            s.wait_mark(self.ctx, CONV_DONE_MARK + st['cur'])
+            s.wait_mark(self.img_ctx, CONV_DONE_MARK + st['cur'])
 
     def _tail(self, st):
-        """Stages after the extractors for every frame of step `st` (a11-a14)."""
-        cfg, nf = self.cfg, self.nf
-        cur = st['cur']
-        sides, preps = self._streams(cur)
-        ns = len(sides)
-        head_scratch = self.head_scratch_sets[cur % len(self.stream_sets)] if self.rpn_head is not None else None
-        fr, feat = self.fr2[cur], self.feat[cur]
-        heads = st['heads']
-        # kept-anchor counts of that step: fetched by its prep streams, long complete
-        k3 = st['step'] % 3
-        counts = [ops.fetch_i32_end(preps[f % ns], 3 * f + k3, 1)[0]
-                  for f in range(nf)]
+        """Stages after the extractors for every frame of step `st` (a11-a14): the per-step state, then the stages of
+        its frames in the order of the T branch's placement (Schedule.t_placement)."""
+        cur, k3, nf, ns = st['cur'], st['step'] % 3, self.nf, len(self.sides)
+        # kept-anchor counts of that step: fetched by its side streams, long complete
+        counts = [ops.fetch_i32_end(self.sides[f % ns], 3 * f + k3, 1)[0] for f in range(nf)]
         self.last_anchor_counts = counts
-        fr = [dict(b, **p) for b, p in zip(fr, self.prep3[k3])]      # the tail's buffers + what its prep left
-        self.fr = fr
+        self.fr = [dict(b, **p) for b, p in zip(self.fr2[cur], self.prep3[k3])]   # the tail's buffers + what its prep left
         self.d_records, self.d_rec_counts = self.rec2[st['rslot']], self.cnt2[st['rslot']]
-        self.d_bev_in = self._views(self.in_bev[cur], (self.bev_h, self.bev_w, self.cfg['bev_depth']), self.bev_pad)
-        bev_px = self.bev_fh * self.bev_fw
-        img_px = self.img_fh * self.img_fw
-        FC = self.feat_c
-        bev_hw, img_hw = (self.bev_fh, self.bev_fw), (self.img_fh, self.img_fw)
-        plane = cfg['ground_plane']
-        if os.environ.get('DODT_PIPE_NO_TAIL'):      # (tools/: the step without its tail)
+        self.d_bev_in = self.bev_in[cur]
+        if self.sched.no_tail:      # (tools/: the step without its tail)
             return
         if self.on_records_reuse is not None:
-            self.on_records_reuse(st['rslot'], sides)
-        computed = heads is None
-        # The T branch of a pair hangs on frame 0's tail, which makes it half as long again as frame 1's.  Its map
-        # and crops (not the head) therefore go onto frame 1's stream, between that frame's own crops and head:
-        # frame 0's stream marks the point where its proposals stand (slot PROPOSALS_MARK), frame 1's waits for it,
-        # correlates, crops and marks CORR_ROIS_MARK, which frame 0's stream waits for in front of the correlation
-        # head.  The frames' launches are enqueued in that order: frame 0 up to its head, frame 1 whole, frame
-        # 0's rest (DODT_PIPE_CORR_ON_F1=0: all of the branch on frame 0's stream).
-        # (t_branch_rows == 'detections': none of that -- the branch runs for the kept boxes only, behind frame 0's NMS #2
-        #  on frame 0's own stream, see frame())
-        t_det = computed and self._t_detections()
-        split_t = computed and self.fps == 2 and ns >= 2 and not os.environ.get('DODT_PIPE_NO_CORR') \
-            and os.environ.get('DODT_PIPE_CORR_ON_F1', '1') != '0' and not t_det
-        corr_img = split_t and self._corr_on_img()
-        fused_tail = os.environ.get('DODT_PIPE_FUSED_TAIL', '1') != '0'
-
-        def t_branch_crops(cc, f0, scratch):
-            """Correlation map of pair (f0, f0 + 1) and its 7x7 crops at frame f0's proposals, on context cc."""
-            fb0 = feat['bev_feat'].offset(4 * bev_px * FC * f0, bev_hw + (FC,))
-            fb1 = feat['bev_feat'].offset(4 * bev_px * FC * (f0 + 1), bev_hw + (FC,))
-            ops.correlation(cc, fb0, fb1, bev_hw + (FC,), CORR_MAX_DISP, CORR_STRIDE2, CORR_PAD,
-                            scratch['corr_map'])
-            ops.crop_and_resize(cc, scratch['corr_map'], bev_hw + (CORR_CH,), fr[f0]['top_bev'], self.P,
-                                fr[f0]['top_count'], (ROI, ROI), fr[f0]['corr_rois'],
-                                out_box_stride=self.corr_head.in_ld)
-
-        def frame(f):
-            c, b, A = sides[f % ns], fr[f], counts[f]
-            h = b if computed else heads[f]
-            scratch = head_scratch[f % ns] if computed else None
-            self._mark(c, st['step'], 'tail%d_start' % f)
-            bneck_b = feat['bev_bneck'].offset(4 * bev_px * f, bev_hw + (1,))
-            bneck_i = feat['img_bneck'].offset(4 * img_px * f, img_hw + (1,))
-            feat_b = feat['bev_feat'].offset(4 * bev_px * FC * f, bev_hw + (FC,))
-            feat_i = feat['img_feat'].offset(4 * img_px * FC * f, img_hw + (FC,))
-            # -- a11: RPN crops (3x3 on the 1-channel bottlenecks) ------------------------
-            ops.crop_and_resize(c, bneck_b, bev_hw + (1,), b['bev_norm'], A, None,
-                                (3, 3), b['rpn_bev_roi'])
-            ops.crop_and_resize(c, bneck_i, img_hw + (1,), b['img_norm'], A, None,
-                                (3, 3), b['rpn_img_roi'])
-            self._mark(c, st['step'], 'tail%d_crops' % f)
-            if computed and not os.environ.get('DODT_PIPE_NO_RPN'):      # (tools/: timing experiment)
-                self.rpn_head.forward(c, b['rpn_bev_roi'], b['rpn_img_roi'], A, b['rpn_logits'],
-                                      b['rpn_offsets'], scratch['rpn'])
-            self._mark(c, st['step'], 'tail%d_rpn' % f)
-            # -- a12, a5, a13: decode, project, NMS #1 --------------------------------------
-            # (round 4: the elementwise runs of a frame's launch chain are one launch each -- rpn_decode, gather_project,
-            #  final_decode below: the same arithmetic value for value, six launches fewer per frame;
-            #  DODT_PIPE_FUSED_TAIL=0: the separate ops)
-            if fused_tail:
-                ops.rpn_decode(c, b['anchors'], h['rpn_offsets'], h['rpn_logits'], A, None, self.bev_extents_flat,
-                               b['regressed'], b['prop_bev'], b['scores'])
-            else:
-                ops.offset_to_anchor(c, b['anchors'], h['rpn_offsets'], A, None, b['regressed'])
-                ops.project_anchors_f32(c, b['regressed'], A, None, self.bev_extents_flat, self.p2,
-                                        self.image_wh, d_bev_norm_tf=b['prop_bev'])
-                ops.softmax_fg(c, h['rpn_logits'], A, None, b['scores'])
-            ops.nms(c, b['prop_bev'], b['scores'], A, None, self.P,
-                    cfg['rpn_nms_iou_thresh'], b['top_idx'], b['top_count'])
-            if fused_tail:
-                # -- stage 2: the kept proposals and their projections, 7x7 crops ---------------
-                ops.gather_project(c, b['regressed'], b['top_idx'], self.P, b['top_count'], self.bev_extents_flat,
-                                   self.p2, self.image_wh, b['top_anchors'], b['top_bev'], b['top_img'])
-                self._mark(c, st['step'], 'tail%d_nms1' % f)
-            else:
-                ops.gather_rows(c, b['regressed'], 6, b['top_idx'], self.P, b['top_count'],
-                                b['top_anchors'])
-                self._mark(c, st['step'], 'tail%d_nms1' % f)
-                ops.project_anchors_f32(c, b['top_anchors'], self.P, b['top_count'],
-                                        self.bev_extents_flat, self.p2, self.image_wh,
-                                        d_bev_norm_tf=b['top_bev'], d_img_norm_tf=b['top_img'])
-            ops.crop_and_resize(c, feat_b, bev_hw + (FC,), b['top_bev'], self.P,
-                                b['top_count'], (ROI, ROI), b['bev_rois'])
-            ops.crop_and_resize(c, feat_i, img_hw + (FC,), b['top_img'], self.P,
-                                b['top_count'], (ROI, ROI), b['img_rois'])
-            yield 'crops'
-            pair = self.fps == 2
-            corr_offsets = h.get('corr_offsets') if pair and f % 2 == 0 else None
-            self._mark(c, st['step'], 'tail%d_crops2' % f)
-            if computed:
-                self.avod_head.forward(c, b['bev_rois'], b['img_rois'], self.P, b['top_count'],
-                                       [b['cls_logits'], b['offsets_4c']]
-                                       + ([b['angle_vectors']] if self.box_4ca else []),
-                                       scratch['fc'])
-                self._mark(c, st['step'], 'tail%d_fc2' % f)
-                yield 'head'
-                if pair and f % 2 == 0 and not os.environ.get('DODT_PIPE_NO_CORR') and not t_det:
-                    # T branch: correlate the pair's BEV features, crop with frame 0's
-                    # proposals (dt_rpn_model.py:324-331, dt_avod_model.py:267-273,300-304)
-                    if corr_img:
-                        pass        # (crops and head on frame 1's stream, below; the records wait for them)
-                    else:
-                        if split_t:
-                            c.wait_mark(sides[(f + 1) % ns], self.CORR_ROIS_MARK)
-                        else:
-                            t_branch_crops(c, f, scratch)
-                        self._mark(c, st['step'], 'tail%d_corrmap' % f)
-                        self.corr_head.forward(c, b['corr_rois'], None, self.P, b['top_count'],
-                                               [b['corr_offsets']], scratch['fc'])
-            self._mark(c, st['step'], 'tail%d_heads' % f)
-            # -- a14, a13: box_4c decode, NMS #2 ---------------------------------------------
-            # record score = softmax over [background, class] (dt_evaluator.py:1226-1248)
-            # box_4ca: all_orientations = atan2 of the angle vectors (dt_avod_model.py:547-548),
-            # gathered with the boxes by NMS #2's indices (:631-634) inside the record kernel,
-            # which applies the evaluator's heading correction (dt_evaluator.py:1166-1212)
-            if fused_tail:
-                ops.final_decode(c, b['top_anchors'], h['offsets_4c'], h['cls_logits'],
-                                 h['angle_vectors'] if self.box_4ca else None, self.P, b['top_count'], plane,
-                                 self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'],
-                                 b['nms2_scores'], b['det_scores'], b['orientations'] if self.box_4ca else None)
-                ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
-                        cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
-            else:
-                ops.box_4c_decode(c, b['top_anchors'], h['offsets_4c'], self.P, b['top_count'],
-                                  plane, self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'],
-                                  b['nms2_boxes'])
-                ops.max_fg_logit(c, h['cls_logits'], 2, self.P, b['top_count'], b['nms2_scores'])
-                ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
-                        cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
-                ops.softmax_fg(c, h['cls_logits'], self.P, b['top_count'], b['det_scores'])
-                if self.box_4ca:
-                    ops.angle_vector_to_orientation(c, h['angle_vectors'], self.P, b['top_count'],
-                                                    b['orientations'])
-            yield 'pack'
-            if t_det and pair and f % 2 == 0:
-                # T branch for the boxes NMS #2 kept: the tiles of the correlation map their crops can read, the map at
-                # those tiles, the crops at top_bev[det_idx], the correlation head at MAX_DET rows (the same GEMM kernels
-                # as at P rows: the same sums), and records that read row j of the offsets for box det_idx[j]
-                if not os.environ.get('DODT_PIPE_NO_CORR'):
-                    fb1 = feat['bev_feat'].offset(4 * bev_px * FC * (f + 1), bev_hw + (FC,))
-                    ops.correlation_tile_list(c, bev_hw, b['top_bev'], self.P, b['det_idx'], MAX_DET, b['det_count'],
-                                              (ROI, ROI), scratch['corr_tiles'], self.corr_tile_cap,
-                                              scratch['corr_ntiles'])
-                    ops.correlation_tiles(c, feat_b, fb1, bev_hw + (FC,), CORR_MAX_DISP, CORR_STRIDE2, CORR_PAD,
-                                          scratch['corr_tiles'], self.corr_tile_cap, scratch['corr_ntiles'],
-                                          scratch['corr_map'])
-                    self._mark(c, st['step'], 'tail%d_corrmap' % f)
-                    ops.crop_and_resize_indexed(c, scratch['corr_map'], bev_hw + (CORR_CH,), b['top_bev'], self.P,
-                                                b['det_idx'], MAX_DET, b['det_count'], (ROI, ROI),
-                                                b['det_corr_rois'], out_box_stride=self.corr_head.in_ld)
-                    self.corr_head.forward(c, b['det_corr_rois'], None, MAX_DET, b['det_count'],
-                                           [b['det_corr_offsets']], scratch['fc'])
-                ops.pack_detections_compact(
-                    c, b['boxes_3d'], b['det_scores'], b['det_idx'], b['det_count'], MAX_DET,
-                    float(f % self.fps),
-                    self.d_records.offset(4 * MAX_DET * REC_COLS * f, (MAX_DET, REC_COLS)),
-                    self.d_rec_counts.offset(4 * f, (1,), np.int32), d_det_offsets=b['det_corr_offsets'],
-                    d_orientations=b['orientations'] if self.box_4ca else None)
-                self._mark(c, st['step'], 'tail%d_end' % f)
-                return
-            ops.pack_detections(
-                c, b['boxes_3d'], b['det_scores'], b['det_idx'], b['det_count'], MAX_DET,
-                float(f % self.fps),
-                self.d_records.offset(4 * MAX_DET * REC_COLS * f, (MAX_DET, REC_COLS)),
-                self.d_rec_counts.offset(4 * f, (1,), np.int32), d_corr_offsets=corr_offsets,
-                d_orientations=b['orientations'] if self.box_4ca else None)
-            self._mark(c, st['step'], 'tail%d_end' % f)
-
-        def drain(g):
-            for _ in g:
-                pass
-
-        if t_det and ns >= 2:
+            self.on_records_reuse(st['rslot'], self.sides)
+        t = _TailState(step=st['step'], cur=cur, fr=self.fr, feat=self.feat_views[cur], counts=counts,
+                       heads=self.fr if st['heads'] is None else st['heads'], scratch=self.head_scratch)
+        if self.placement == 'img':
+            for f0 in range(0, nf, 2):
+                self._pair_img(t, f0)
+        elif self.placement == 'f1':
+            for f0 in range(0, nf, 2):
+                self._pair_f1(t, f0)
+        elif self.alternate:
             # the frames of a pair are independent chains on two streams: their launches alternate stage by stage
             for f0 in range(0, nf, 2):
-                gens = [frame(f0), frame(f0 + 1)]
-                while gens:
-                    gens = [g for g in gens if next(g, None) is not None]
-            return
-        if not split_t:
+                for stage in (self._proposals, self._head2, self._decode_nms2, self._records):
+                    stage(t, f0)
+                    stage(t, f0 + 1)
+        else:
             for f in range(nf):
-                drain(frame(f))
-            return
-        for f0 in range(0, nf, 2):
-            c0, c1 = sides[f0 % ns], sides[(f0 + 1) % ns]
-            g0, g1 = frame(f0), frame(f0 + 1)
-            while next(g0) != 'crops':          # frame 0 up to its 7x7 crops: its proposals stand
-                pass
-            c0.mark(self.PROPOSALS_MARK)
-            if corr_img:
-                # The map stands since the convs ended (run()).  Its crops at frame 0's proposals and the correlation head
-                # go onto frame 1's stream, in front of that frame's own head -- frame 0's stream, which carried them,
-                # was the longer chain by their 0.1 ms -- and frame 0's records wait for the offsets.
-                while next(g0) != 'pack':
-                    pass
-                while next(g1) != 'crops':
-                    pass
-                c1.wait_mark(c0, self.PROPOSALS_MARK)
-                c1.wait_mark(self.img_ctx, self.CORR_MAP_MARK + cur)
-                ops.crop_and_resize(c1, self.corr_maps[cur][f0 // 2], bev_hw + (CORR_CH,), fr[f0]['top_bev'], self.P,
-                                    fr[f0]['top_count'], (ROI, ROI), fr[f0]['corr_rois'],
-                                    out_box_stride=self.corr_head.in_ld)
-                self.corr_head.forward(c1, fr[f0]['corr_rois'], None, self.P, fr[f0]['top_count'],
-                                       [fr[f0]['corr_offsets']], head_scratch[(f0 + 1) % ns]['fc'])
-                c1.mark(self.CORR_ROIS_MARK)
-                c0.wait_mark(c1, self.CORR_ROIS_MARK)
-                drain(g0)
-                drain(g1)
-                continue
-            while next(g0) != 'head':           # ... and its stage-2 head
-                pass
-            while next(g1) != 'crops':          # frame 1 up to its crops, then the T branch's map and crops
-                pass
-            c1.wait_mark(c0, self.PROPOSALS_MARK)
-            t_branch_crops(c1, f0, head_scratch[(f0 + 1) % ns])
-            c1.mark(self.CORR_ROIS_MARK)
-            drain(g1)
-            drain(g0)                           # waits for CORR_ROIS_MARK: correlation head, NMS #2, records
+                self._proposals(t, f)
+                self._head2(t, f)
+                if self.placement == 'f0' and f % 2 == 0:
+                    self._t_map_crops(t, f, on=f)
+                    self._mark(self.sides[f % ns], t.step, 'tail%d_corrmap' % f)
+                    self._t_head(t, f, on=f)
+                self._decode_nms2(t, f)
+                self._records(t, f)
 
-    PROPOSALS_MARK, CORR_ROIS_MARK = 252, 253   # mark slots of the side contexts (the T branch's hand-overs)
-    TAIL_DONE_MARK = 247                        # ... : the end of a step's tail on that stream
+    def _pair_img(self, t, f0):
+        """Placement 'img', pair (f0, f0 + 1).  The map stands since the convs ended (run()).  Its crops at frame 0's
+        proposals and the correlation head go onto frame 1's stream, in front of that frame's own head -- frame 0's
+        stream, which carried them, was the longer chain by their 0.1 ms -- and frame 0's records wait for the offsets."""
+        ns = len(self.sides)
+        c0, c1 = self.sides[f0 % ns], self.sides[(f0 + 1) % ns]
+        self._proposals(t, f0)
+        c0.mark(PROPOSALS_MARK)
+        self._head2(t, f0)
+        self._decode_nms2(t, f0)
+        self._proposals(t, f0 + 1)
+        c1.wait_mark(c0, PROPOSALS_MARK)
+        c1.wait_mark(self.img_ctx, CORR_MAP_MARK + t.cur)
+        self._t_crops(t, f0, f0 + 1, self.corr_maps[t.cur][f0 // 2])
+        self._t_head(t, f0, on=f0 + 1)
+        c1.mark(CORR_ROIS_MARK)
+        c0.wait_mark(c1, CORR_ROIS_MARK)
+        self._records(t, f0)
+        self._head2(t, f0 + 1)
+        self._decode_nms2(t, f0 + 1)
+        self._records(t, f0 + 1)
+
+    def _pair_f1(self, t, f0):
+        """Placement 'f1', pair (f0, f0 + 1).  The T branch hangs on frame 0's tail, which makes it half as long again
+        as frame 1's: its map and crops (not the head) go onto frame 1's stream, between that frame's own crops and
+        head, and frame 0's stream waits for them in front of the correlation head."""
+        ns = len(self.sides)
+        c0, c1 = self.sides[f0 % ns], self.sides[(f0 + 1) % ns]
+        self._proposals(t, f0)
+        c0.mark(PROPOSALS_MARK)
+        self._head2(t, f0)
+        self._proposals(t, f0 + 1)
+        c1.wait_mark(c0, PROPOSALS_MARK)
+        self._t_map_crops(t, f0, on=f0 + 1)
+        c1.mark(CORR_ROIS_MARK)
+        self._head2(t, f0 + 1)
+        self._decode_nms2(t, f0 + 1)
+        self._records(t, f0 + 1)
+        c0.wait_mark(c1, CORR_ROIS_MARK)
+        self._mark(c0, t.step, 'tail%d_corrmap' % f0)
+        self._t_head(t, f0, on=f0)
+        self._decode_nms2(t, f0)
+        self._records(t, f0)
+
+    def _proposals(self, t, f):
+        """Frame f up to its 7x7 crops: RPN crops, RPN head, decode, NMS #1, the kept proposals and their projections."""
+        c, b, h, A, v = self.sides[f % len(self.sides)], t.fr[f], t.heads[f], t.counts[f], t.feat[f]
+        bev_hw, img_hw, FC = (self.bev_fh, self.bev_fw), (self.img_fh, self.img_fw), self.feat_c
+        self._mark(c, t.step, 'tail%d_start' % f)
+        # -- a11: RPN crops (3x3 on the 1-channel bottlenecks) ------------------------
+        ops.crop_and_resize(c, v['bev_bneck'], bev_hw + (1,), b['bev_norm'], A, None, (3, 3), b['rpn_bev_roi'])
+        ops.crop_and_resize(c, v['img_bneck'], img_hw + (1,), b['img_norm'], A, None, (3, 3), b['rpn_img_roi'])
+        self._mark(c, t.step, 'tail%d_crops' % f)
+        if self.rpn_head is not None and not self.sched.no_rpn:      # (no_rpn: tools/' timing experiment)
+            self.rpn_head.forward(c, b['rpn_bev_roi'], b['rpn_img_roi'], A, b['rpn_logits'],
+                                  b['rpn_offsets'], t.scratch[f % len(self.sides)]['rpn'])
+        self._mark(c, t.step, 'tail%d_rpn' % f)
+        # -- a12, a5, a13: decode, project, NMS #1; stage 2: the kept proposals and their projections ---------
+        # (the elementwise runs of a frame's launch chain are one launch each -- rpn_decode, gather_project, final_decode
+        #  below: the same arithmetic value for value, six launches fewer per frame; DODT_PIPE_FUSED_TAIL=0: the separate ops)
+        if self.sched.fused_tail:
+            ops.rpn_decode(c, b['anchors'], h['rpn_offsets'], h['rpn_logits'], A, None, self.bev_extents_flat,
+                           b['regressed'], b['prop_bev'], b['scores'])
+        else:
+            ops.offset_to_anchor(c, b['anchors'], h['rpn_offsets'], A, None, b['regressed'])
+            ops.project_anchors_f32(c, b['regressed'], A, None, self.bev_extents_flat, self.p2,
+                                    self.image_wh, d_bev_norm_tf=b['prop_bev'])
+            ops.softmax_fg(c, h['rpn_logits'], A, None, b['scores'])
+        ops.nms(c, b['prop_bev'], b['scores'], A, None, self.P, self.cfg['rpn_nms_iou_thresh'], b['top_idx'], b['top_count'])
+        if self.sched.fused_tail:
+            ops.gather_project(c, b['regressed'], b['top_idx'], self.P, b['top_count'], self.bev_extents_flat,
+                               self.p2, self.image_wh, b['top_anchors'], b['top_bev'], b['top_img'])
+            self._mark(c, t.step, 'tail%d_nms1' % f)
+        else:
+            ops.gather_rows(c, b['regressed'], 6, b['top_idx'], self.P, b['top_count'], b['top_anchors'])
+            self._mark(c, t.step, 'tail%d_nms1' % f)
+            ops.project_anchors_f32(c, b['top_anchors'], self.P, b['top_count'], self.bev_extents_flat, self.p2,
+                                    self.image_wh, d_bev_norm_tf=b['top_bev'], d_img_norm_tf=b['top_img'])
+        ops.crop_and_resize(c, v['bev_feat'], bev_hw + (FC,), b['top_bev'], self.P, b['top_count'], (ROI, ROI),
+                            b['bev_rois'])
+        ops.crop_and_resize(c, v['img_feat'], img_hw + (FC,), b['top_img'], self.P, b['top_count'], (ROI, ROI),
+                            b['img_rois'])
+
+    def _head2(self, t, f):
+        """Frame f's stage-2 head on its 7x7 crops (computed heads)."""
+        c, b = self.sides[f % len(self.sides)], t.fr[f]
+        self._mark(c, t.step, 'tail%d_crops2' % f)
+        if self.rpn_head is not None:
+            self.avod_head.forward(c, b['bev_rois'], b['img_rois'], self.P, b['top_count'],
+                                   [b['cls_logits'], b['offsets_4c']] + ([b['angle_vectors']] if self.box_4ca else []),
+                                   t.scratch[f % len(self.sides)]['fc'])
+            self._mark(c, t.step, 'tail%d_fc2' % f)
+
+    def _correlation_map(self, c, cur, f0, d_map):
+        """The correlation map of pair (f0, f0 + 1) from the BEV feature maps of parity `cur`, on context c."""
+        v = self.feat_views[cur]
+        ops.correlation(c, v[f0]['bev_feat'], v[f0 + 1]['bev_feat'], (self.bev_fh, self.bev_fw, self.feat_c),
+                        CORR_MAX_DISP, CORR_STRIDE2, CORR_PAD, d_map)
+
+    def _t_crops(self, t, f0, on, d_map):
+        """T branch ('proposals' form): 7x7 crops of the pair's map at frame f0's proposals, on frame `on`'s stream
+        (dt_rpn_model.py:324-331, dt_avod_model.py:267-273,300-304)."""
+        b = t.fr[f0]
+        ops.crop_and_resize(self.sides[on % len(self.sides)], d_map, (self.bev_fh, self.bev_fw, CORR_CH), b['top_bev'],
+                            self.P, b['top_count'], (ROI, ROI), b['corr_rois'], out_box_stride=self.corr_head.in_ld)
+
+    def _t_map_crops(self, t, f0, on):
+        """... the map in that stream's scratch first."""
+        i = on % len(self.sides)
+        self._correlation_map(self.sides[i], t.cur, f0, t.scratch[i]['corr_map'])
+        self._t_crops(t, f0, on, t.scratch[i]['corr_map'])
+
+    def _t_head(self, t, f0, on):
+        """... the correlation head on those crops, on frame `on`'s stream with its scratch."""
+        i, b = on % len(self.sides), t.fr[f0]
+        self.corr_head.forward(self.sides[i], b['corr_rois'], None, self.P, b['top_count'], [b['corr_offsets']],
+                               t.scratch[i]['fc'])
+
+    def _decode_nms2(self, t, f):
+        """a14, a13 of frame f: box_4c decode, NMS #2."""
+        c, b, h, plane = self.sides[f % len(self.sides)], t.fr[f], t.heads[f], self.cfg['ground_plane']
+        self._mark(c, t.step, 'tail%d_heads' % f)
+        # record score = softmax over [background, class] (dt_evaluator.py:1226-1248)
+        # box_4ca: all_orientations = atan2 of the angle vectors (dt_avod_model.py:547-548),
+        # gathered with the boxes by NMS #2's indices (:631-634) inside the record kernel,
+        # which applies the evaluator's heading correction (dt_evaluator.py:1166-1212)
+        if self.sched.fused_tail:
+            ops.final_decode(c, b['top_anchors'], h['offsets_4c'], h['cls_logits'],
+                             h['angle_vectors'] if self.box_4ca else None, self.P, b['top_count'], plane,
+                             self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'],
+                             b['nms2_scores'], b['det_scores'], b['orientations'] if self.box_4ca else None)
+            ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
+                    self.cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
+        else:
+            ops.box_4c_decode(c, b['top_anchors'], h['offsets_4c'], self.P, b['top_count'],
+                              plane, self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'])
+            ops.max_fg_logit(c, h['cls_logits'], 2, self.P, b['top_count'], b['nms2_scores'])
+            ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
+                    self.cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
+            ops.softmax_fg(c, h['cls_logits'], self.P, b['top_count'], b['det_scores'])
+            if self.box_4ca:
+                ops.angle_vector_to_orientation(c, h['angle_vectors'], self.P, b['top_count'], b['orientations'])
+
+    def _records(self, t, f):
+        """Frame f's detection records; in the 'detections' form, behind the T branch of its pair on frame 0."""
+        c, b = self.sides[f % len(self.sides)], t.fr[f]
+        frame0 = self.fps == 2 and f % 2 == 0
+        d_rec = self.d_records.offset(4 * MAX_DET * REC_COLS * f, (MAX_DET, REC_COLS))
+        d_cnt = self.d_rec_counts.offset(4 * f, (1,), np.int32)
+        d_orient = b['orientations'] if self.box_4ca else None
+        if frame0 and self._t_detections():
+            if self.placement == 'detections':
+                self._t_detection_rows(t, f)
+            # (placement 'none', DODT_PIPE_NO_CORR: the offsets stay the zeros they were made as)
+            ops.pack_detections_compact(c, b['boxes_3d'], b['det_scores'], b['det_idx'], b['det_count'], MAX_DET,
+                                        float(f % self.fps), d_rec, d_cnt, d_det_offsets=b['det_corr_offsets'],
+                                        d_orientations=d_orient)
+        else:
+            ops.pack_detections(c, b['boxes_3d'], b['det_scores'], b['det_idx'], b['det_count'], MAX_DET,
+                                float(f % self.fps), d_rec, d_cnt,
+                                d_corr_offsets=t.heads[f].get('corr_offsets') if frame0 else None,
+                                d_orientations=d_orient)
+        self._mark(c, t.step, 'tail%d_end' % f)
+
+    def _t_detection_rows(self, t, f):
+        """T branch for the boxes NMS #2 kept of frame f (placement 'detections'): the tiles of the correlation map their
+        crops can read, the map at those tiles, the crops at top_bev[det_idx], the correlation head at MAX_DET rows (the
+        same GEMM kernels as at P rows: the same sums); the records read row j of the offsets for box det_idx[j]."""
+        i = f % len(self.sides)
+        c, b, scratch, v = self.sides[i], t.fr[f], t.scratch[i], t.feat
+        bev_hw, FC = (self.bev_fh, self.bev_fw), self.feat_c
+        ops.correlation_tile_list(c, bev_hw, b['top_bev'], self.P, b['det_idx'], MAX_DET, b['det_count'],
+                                  (ROI, ROI), scratch['corr_tiles'], self.corr_tile_cap, scratch['corr_ntiles'])
+        ops.correlation_tiles(c, v[f]['bev_feat'], v[f + 1]['bev_feat'], bev_hw + (FC,), CORR_MAX_DISP, CORR_STRIDE2,
+                              CORR_PAD, scratch['corr_tiles'], self.corr_tile_cap, scratch['corr_ntiles'],
+                              scratch['corr_map'])
+        self._mark(c, t.step, 'tail%d_corrmap' % f)
+        ops.crop_and_resize_indexed(c, scratch['corr_map'], bev_hw + (CORR_CH,), b['top_bev'], self.P,
+                                    b['det_idx'], MAX_DET, b['det_count'], (ROI, ROI),
+                                    b['det_corr_rois'], out_box_stride=self.corr_head.in_ld)
+        self.corr_head.forward(c, b['det_corr_rois'], None, MAX_DET, b['det_count'],
+                               [b['det_corr_offsets']], scratch['fc'])
 
     def sync(self):
         self.ctx.sync()

@@ -108,3 +108,18 @@ def test_records_equal_with_two_pairs_per_step(ctx, frames):
 def test_records_equal_with_bf16_convs_and_heads(ctx, frames):
     for p in _three_forms(ctx, frames, 1, conv_dtype='bf16', head_dtype='bf16')[0]:
         p.close()
+
+
+def test_records_equal_with_one_side_stream(ctx, frames):
+    """side_streams=1: both frames' preps and tails on one stream, one frame after the other, and the whole T branch
+    (map, crops, correlation head) between frame 0's stage-2 head and its decode on that stream (placement 'f0')."""
+    p_two, two = _run(ctx, frames, 1, [], t_branch_rows='proposals')
+    p_one, one = _run(ctx, frames, 1, [], t_branch_rows='proposals', side_streams=1)      # (streams of its own)
+    assert len(p_two.sides) == 2 and p_two.placement == 'img'
+    assert len(p_one.sides) == 1 and p_one.placement == 'f0' and p_one.t_branch_form() == 'proposals'
+    counts = two[-1][1]
+    assert counts.shape == (1, 2) and counts.min() > 0
+    assert np.abs(one[-1][0][:, 0, :, 9:16]).max() > 0           # frame 0's shifted boxes are there
+    _same(two, one)
+    for p in (p_two, p_one):
+        p.close()
