@@ -47,8 +47,18 @@ struct GemmArgs {
     float* y;
     int M, K, Kp, N, ldx, ldy, relu;
     const int* d_m;    // may be NULL: rows >= *d_m are skipped
-    unsigned long long* clock_probe = nullptr;   // tools/ (DODT_FC_CLOCK=1): shader and 100 MHz clock of one workgroup's K loop
 };
+
+// the rows a launch computes: the host's M, cut down by the device-side count where there is one
+__device__ __forceinline__ int resolved_rows(const int* d_m, int M) { return d_m ? min(*d_m, M) : M; }
+
+// XCD-aware tile order of the one-dimensional grids: workgroup id -> XCD id % 8 (round-robin dispatch); XCD j takes
+// the j-th eighth of the tile list
+__device__ __forceinline__ int xcd_tile(int tiles) {
+    int tile = blockIdx.x;
+    if (tiles % 8 == 0) tile = (int)(blockIdx.x % 8) * (tiles / 8) + (int)(blockIdx.x / 8);
+    return tile;
+}
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -63,11 +73,31 @@ __device__ __forceinline__ float bf16_value(float packed, int which) {
     return __builtin_bit_cast(float, which ? (u & 0xffff0000u) : (u << 16));
 }
 
+// Epilogue of one 32x32 MFMA tile: bias + activation + store.  The lane owns feature n (bias b) and the 16 samples
+// m_lane + (r & 3) + 8 (r >> 2), m_lane = the tile's first row + 4 * (lane >> 5).  YBF16: round to nearest even.
+template <bool YBF16>
+__device__ __forceinline__ void store_tile32(const GemmArgs& a, const f32x16& acc, float b, int m_lane, int n, int M) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = m_lane + (r & 3) + 8 * (r >> 2);
+        if (m < M && n < a.N) {
+            float v = acc[r] + b;
+            if (a.relu) v = fmaxf(v, 0.0f);
+            if constexpr (YBF16)
+                reinterpret_cast<unsigned short*>(a.y)[(size_t)m * a.ldy + n] =
+                    (unsigned short)(__builtin_bit_cast(unsigned, pack_bf16(v, 0.0f)) & 0xffffu);
+            else
+                a.y[(size_t)m * a.ldy + n] = v;
+        }
+    }
+}
+
 // kBK = k per stage.  BF16: x is rounded to bf16 on its way into LDS, the weights are stored
 // as bf16, one v_mfma_f32_32x32x16_bf16 replaces four fp32 MFMAs; a 16-byte LDS fragment
 // holds KB = 8 k-values instead of 4, so the LDS images of a stage have the geometry of an
 // fp32 stage of half the depth (G).
-template <int BM, int BN, int WM, int WN, bool XVEC, int WBN, int kBK, bool FUSE, bool BF16>
+// The weights are blocked BN columns wide, so a workgroup's block is contiguous.
+template <int BM, int BN, int WM, int WN, bool XVEC, int kBK, bool FUSE, bool BF16>
 __global__ void __launch_bounds__(256)
 fc_mfma_kernel(const GemmArgs a) {
     constexpr int MT = BM / 32 / WM, NT = BN / 32 / WN;
@@ -84,13 +114,10 @@ fc_mfma_kernel(const GemmArgs a) {
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
     const int m0 = blockIdx.x * BM, nt0 = blockIdx.y;
-    const int M = a.d_m ? min(*a.d_m, a.M) : a.M;
+    const int M = resolved_rows(a.d_m, a.M);
     if (m0 >= M) return;
     const int nstages = a.Kp / kBK;
-    // weights are blocked WBN columns wide; this kernel's BN columns are a slice of them
-    static_assert(WBN % BN == 0, "tile must divide the blocked width");
-    const f32x4* wblk = reinterpret_cast<const f32x4*>(a.w) +
-                        (size_t)(nt0 * BN / WBN) * (a.Kp / (2 * KB)) * 2 * WBN + (nt0 * BN) % WBN;
+    const f32x4* wblk = reinterpret_cast<const f32x4*>(a.w) + (size_t)nt0 * (a.Kp / (2 * KB)) * 2 * BN;
 
     // staging slot j < NX: x float4 (tid + 256 j); slot NX + j: weight float4 (tid + 256 j).
     // Loads are unconditional (clamped addresses), zero-fill happens by select.
@@ -114,7 +141,7 @@ fc_mfma_kernel(const GemmArgs a) {
             l_off[j] = row * kXS + q * 4;
         } else {
             const int t = min(tid + (j - NX) * 256, WITEMS - 1);
-            g_off[j] = (t / BN) * WBN + t % BN;
+            g_off[j] = t;
             l_off[j] = BM * kXS + t * 4;
         }
     }
@@ -145,7 +172,7 @@ fc_mfma_kernel(const GemmArgs a) {
                 }
             }
         } else {
-            pre[j] = wblk[(size_t)st * (G / 4 * WBN) + g_off[j]];
+            pre[j] = wblk[(size_t)st * (G / 4 * BN) + g_off[j]];
         }
     };
     auto store_slot = [&](int j, int buf, int st) {   // st: the stage the registers hold
@@ -261,45 +288,41 @@ fc_mfma_kernel(const GemmArgs a) {
         const float b = a.bias[n];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + (wm * MT + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m < M && n < a.N) {
-                    float v = acc[mt * NT + nt][r] + b;
-                    if (a.relu) v = fmaxf(v, 0.0f);
-                    a.y[(size_t)m * a.ldy + n] = v;
-                }
-            }
+            store_tile32<false>(a, acc[mt * NT + nt], b, m0 + (wm * MT + mt) * 32 + 4 * lh, n, M);
     }
 }
 
-template <int BM, int BN, int WM, int WN, int WBN = BN, int kBK = 32, bool BF16 = false>
+// Allows `kernel` its `lds` bytes of dynamic LDS: one attribute call per kernel and process.
+hipError_t allow_dynamic_lds(const void* kernel, size_t lds) {
+    static std::mutex mu;
+    static std::set<const void*> prepared;
+    std::lock_guard<std::mutex> lock(mu);
+    if (prepared.count(kernel)) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) prepared.insert(kernel);
+    return e;
+}
+
+// Launches a 256-lane kernel that needs dynamic LDS.
+template <typename... Params, typename... Args>
+hipError_t launch_with_lds(void (*kernel)(Params...), dim3 grid, size_t lds, hipStream_t s, const Args&... args) {
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, args...);
+    return hipSuccess;
+}
+
+template <int BM, int BN, int WM, int WN, int kBK, bool BF16>
 int launch_fc(hipStream_t s, const GemmArgs& a, int Npad) {
     constexpr int G = BF16 ? kBK / 2 : kBK;
     constexpr size_t lds = 2 * (size_t)(BM * (G + 4) + G * BN) * sizeof(float);
     const bool vec = (a.ldx % 4 == 0) && (a.K % (BF16 ? 8 : 4) == 0);
-    dim3 grid(dodt::ceil_div(a.M, BM), Npad / BN);
-    auto go = [&](auto kernel) -> hipError_t {
-        static std::mutex mu;
-        static std::set<const void*> prepared;   // one attribute call per kernel
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            if (!prepared.count(reinterpret_cast<const void*>(kernel))) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)lds);
-                if (e != hipSuccess) return e;
-                prepared.insert(reinterpret_cast<const void*>(kernel));
-            }
-        }
-        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, a);
-        return hipSuccess;
-    };
+    const dim3 grid(dodt::ceil_div(a.M, BM), Npad / BN);
     hipError_t e;
-    if (vec && a.x2) e = go(&fc_mfma_kernel<BM, BN, WM, WN, true, WBN, kBK, true, BF16>);
-    else if (vec) e = go(&fc_mfma_kernel<BM, BN, WM, WN, true, WBN, kBK, false, BF16>);
-    else if (a.x2) e = go(&fc_mfma_kernel<BM, BN, WM, WN, false, WBN, kBK, true, BF16>);
-    else e = go(&fc_mfma_kernel<BM, BN, WM, WN, false, WBN, kBK, false, BF16>);
+    if (vec && a.x2) e = launch_with_lds(&fc_mfma_kernel<BM, BN, WM, WN, true, kBK, true, BF16>, grid, lds, s, a);
+    else if (vec) e = launch_with_lds(&fc_mfma_kernel<BM, BN, WM, WN, true, kBK, false, BF16>, grid, lds, s, a);
+    else if (a.x2) e = launch_with_lds(&fc_mfma_kernel<BM, BN, WM, WN, false, kBK, true, BF16>, grid, lds, s, a);
+    else e = launch_with_lds(&fc_mfma_kernel<BM, BN, WM, WN, false, kBK, false, BF16>, grid, lds, s, a);
     DODT_HIP_CHECK(e);
     DODT_LAUNCH_CHECK();
     return DODT_OK;
@@ -347,14 +370,10 @@ fc_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, lh = lane >> 5;
-    // XCD-aware tile order: workgroup id -> XCD id % 8 (round-robin dispatch); XCD j takes the j-th
-    // eighth of the tile list (n fastest)
-    const int T = tiles_m * tiles_n;
-    int tile = blockIdx.x;
-    if (T % 8 == 0) tile = (int)(blockIdx.x % 8) * (T / 8) + (int)(blockIdx.x / 8);
+    const int tile = xcd_tile(tiles_m * tiles_n);   // n fastest
     const int mt = tile / tiles_n, nt0 = tile % tiles_n;
     const int m0 = mt * kDmaBM;
-    const int M = a.d_m ? min(*a.d_m, a.M) : a.M;
+    const int M = resolved_rows(a.d_m, a.M);
     if (m0 >= M) return;
     const int nstages = a.K / kDmaBK;
 
@@ -463,79 +482,33 @@ fc_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
     };
     issue(0, 0);
     if (nstages > 1) issue(1, 1);
-    const bool probe = a.clock_probe != nullptr && blockIdx.x == 17 && tid == 0;
-    unsigned long long c0 = 0, r0 = 0;
-    if (probe) { c0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
     for (int st = 0; st < nstages; st += 3) {
         stage(std::integral_constant<int, 0>{}, st);
         if (st + 1 < nstages) stage(std::integral_constant<int, 1>{}, st + 1);
         if (st + 2 < nstages) stage(std::integral_constant<int, 2>{}, st + 2);
     }
-    if (probe) {
-        a.clock_probe[0] = __builtin_amdgcn_s_memtime() - c0;
-        a.clock_probe[1] = __builtin_amdgcn_s_memrealtime() - r0;
-    }
     // epilogue: bias + activation; lane = feature, registers = samples
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int n = n0 + wn * 32 * NT + nt * 32 + li;
-        const float b = a.bias[n];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (m < M && n < a.N) {
-                float v = acc[nt][r] + b;
-                if (a.relu) v = fmaxf(v, 0.0f);
-                a.y[(size_t)m * a.ldy + n] = v;
-            }
-        }
+        store_tile32<false>(a, acc[nt], a.bias[n], m0 + wm * 32 + 4 * lh, n, M);
     }
 }
 
-int launch_fc_dma(hipStream_t s, const GemmArgs& a_in, int Npad) {
-    GemmArgs a = a_in;
-    // DODT_FC_CLOCK=1 (tools/gemm_one.py): shader clock inside the K loop of workgroup 17, from s_memtime against the
-    // 100 MHz s_memrealtime -- the clock the fp32 matrix pipe actually runs at under this kernel
-    static const bool want_clock = getenv("DODT_FC_CLOCK") != nullptr;
-    static unsigned long long* d_probe = nullptr;
-    if (want_clock) {
-        if (!d_probe) DODT_HIP_CHECK(hipMalloc(&d_probe, 2 * sizeof(unsigned long long)));
-        a.clock_probe = d_probe;
-    }
-    // 64 x 128 tiles (two MFMA tiles per wave) when that still gives two workgroups per CU
-    static const int force_nt = getenv("DODT_FC_NT") ? atoi(getenv("DODT_FC_NT")) : 0;
-    const int nt = force_nt ? force_nt
-                            : (!a.x2 && (long)dodt::ceil_div(a.M, kDmaBM) * (Npad / 128) >= 2 * 256 ? 2 : 1);
+// nt: 1 or 2 MFMA tiles per wave (select_fc_form); a second input selects the fused-mean instance, which has nt = 1 only.
+// (Round 4 read the shader clock inside the K loop with a probe compiled into this kernel, s_memtime against the 100 MHz
+//  s_memrealtime: 1.91-1.94 GHz, DESIGN.md 5b and profiles/r4_experiments.md; the probe is removed again.)
+int launch_fc_dma(hipStream_t s, const GemmArgs& a, int Npad, int nt) {
     const int tiles_m = dodt::ceil_div(a.M, kDmaBM), tiles_n = Npad / (64 * nt);
-    auto go = [&](auto kernel, size_t lds) -> hipError_t {
-        static std::mutex mu;
-        static std::set<const void*> prepared;
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            if (!prepared.count(reinterpret_cast<const void*>(kernel))) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-                prepared.insert(reinterpret_cast<const void*>(kernel));
-            }
-        }
-        hipLaunchKernelGGL(kernel, dim3(tiles_m * tiles_n), dim3(256), lds, s, a, tiles_m, tiles_n);
-        return hipSuccess;
-    };
+    const dim3 grid(tiles_m * tiles_n);
+    const size_t x_floats = (size_t)kDmaXFloats * (a.x2 ? 2 : 1);
+    const size_t lds = kDmaStages * (x_floats + (size_t)kDmaBK * 64 * nt) * sizeof(float);
     hipError_t e;
-    if (a.x2) e = go(&fc_dma_kernel<true, 1>, (size_t)kDmaStages * (2 * kDmaXFloats + kDmaBK * 64) * 4);
-    else if (nt == 2) e = go(&fc_dma_kernel<false, 2>, (size_t)kDmaStages * (kDmaXFloats + kDmaBK * 128) * 4);
-    else e = go(&fc_dma_kernel<false, 1>, (size_t)kDmaStages * (kDmaXFloats + kDmaBK * 64) * 4);
+    if (a.x2) e = launch_with_lds(&fc_dma_kernel<true, 1>, grid, lds, s, a, tiles_m, tiles_n);
+    else if (nt == 2) e = launch_with_lds(&fc_dma_kernel<false, 2>, grid, lds, s, a, tiles_m, tiles_n);
+    else e = launch_with_lds(&fc_dma_kernel<false, 1>, grid, lds, s, a, tiles_m, tiles_n);
     DODT_HIP_CHECK(e);
     DODT_LAUNCH_CHECK();
-    if (want_clock) {
-        unsigned long long h[2] = {0, 0};
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, d_probe, sizeof(h), hipMemcpyDeviceToHost);
-        if (h[1])
-            fprintf(stderr, "[dodt] fc_dma_kernel M %d K %d N %d: K loop of workgroup 17: %llu shader cycles in %.2f us = %.3f GHz\n",
-                    a.M, a.K, a.N, h[0], h[1] / 100.0, (double)h[0] / h[1] * 0.1);
-    }
     return DODT_OK;
 }
 
@@ -560,13 +533,14 @@ int launch_fc_dma(hipStream_t s, const GemmArgs& a_in, int Npad) {
 constexpr int kBfBM = 64, kBfBN = 128, kBfStages = 3;
 __host__ __device__ constexpr int bf_swz(int r, int S) { return (r / (16 / S)) & (S - 1); }
 
-template <bool YBF16, int BK, int R = kBfStages>
+// (The end of round 4 tried a ring of SIX stage images with BK = 32 -- at M = 1024 a layer is 256 workgroups, one per CU,
+//  and two 12 KB stages on their way per CU are less than the memory system's latency x bandwidth: 16.7 -> 14.8 us at
+//  M = 1024, but 27.8 -> 29.5 / 52.6 -> 59.2 us at M = 2048 / 4096 (two workgroups per CU) and 980-992 against 995-1 012
+//  pairs/s in the bf16 pipeline; removed again.)
+template <bool YBF16, int BK>
 __global__ void __launch_bounds__(256, 2)
 fc_bf16_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
-    // R: ring of stage images (three; six with DODT_FC_BF16_DMA_RING=6 and BK = 32: at M = 1024 a layer is 256 workgroups,
-    // one per CU, and two 12 KB stages on their way per CU are less than the memory system's latency x bandwidth -- see
-    // launch_fc_bf16_dma for what that bought)
-    static_assert((R - 2) * ((kBfBM + kBfBN) * BK * 2 / 1024 / 4) <= 63, "vmcnt is six bits");
+    static_assert(kBfStages == 3, "the stage loop is unrolled for a ring of three");
     using dodt::i32x4_t;
     using dodt::kOob;
     using dodt::make_rsrc;
@@ -574,6 +548,7 @@ fc_bf16_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
     constexpr int kXBytes = kBfBM * BK * 2, kWBytes = kBfBN * BK * 2, kStage = kXBytes + kWBytes;
     constexpr int kXPieces = kXBytes / 1024 / 4, kWPieces = kWBytes / 1024 / 4;   // 1 KB copies per wave and stage
     constexpr int kPerStage = kXPieces + kWPieces;
+    static_assert(kPerStage <= 63, "vmcnt is six bits");
     constexpr int kRowsPerPiece = 1024 / (BK * 2);
     constexpr int NQ = BK / 16;                                // MFMA k-steps per stage
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -581,13 +556,10 @@ fc_bf16_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, lh = lane >> 5;
-    // XCD-aware tile order (as fc_dma_kernel): XCD j takes the j-th eighth of the tile list, n fastest
-    const int T = tiles_m * tiles_n;
-    int tile = blockIdx.x;
-    if (T % 8 == 0) tile = (int)(blockIdx.x % 8) * (T / 8) + (int)(blockIdx.x / 8);
+    const int tile = xcd_tile(tiles_m * tiles_n);   // n fastest
     const int mt = tile / tiles_n, nt0 = tile % tiles_n;
     const int m0 = mt * kBfBM;
-    const int M = a.d_m ? min(*a.d_m, a.M) : a.M;
+    const int M = resolved_rows(a.d_m, a.M);
     if (m0 >= M) return;
     const int nstages = a.Kp / BK;          // (Kp: K rounded up to 64 for this kernel)
     const int rows = min(M - m0, kBfBM);
@@ -626,11 +598,11 @@ fc_bf16_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
     const int w_base = kXBytes + (wn * 64 + li) * (BK * 2);
     auto stage = [&](auto bufc, int st) {
         constexpr int BUF = decltype(bufc)::value;
-        // stage st has landed once all but the copies of stages st + 1 .. st + R - 2 are done (fewer near the end: drain)
-        if (st + R - 2 < nstages) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R - 2) * kPerStage) : "memory");
+        // stage st has landed once all but the copies of stage st + 1 are done
+        if (st + 1 < nstages) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kPerStage) : "memory");
         else __builtin_amdgcn_s_waitcnt(0x0f70);                                  // vmcnt(0)
-        __builtin_amdgcn_s_barrier();     // ... for every wave; buffer (BUF + R - 1) % R is free
-        const bool more = st + R - 1 < nstages;
+        __builtin_amdgcn_s_barrier();     // ... for every wave; buffer (BUF + 2) % 3 is free
+        const bool more = st + 2 < nstages;
         const char* sS = reinterpret_cast<const char*>(smem) + BUF * kStage;
         f32x4 xf[NQ], wf[NQ][2];
         auto read_q = [&](int q) {
@@ -653,7 +625,7 @@ fc_bf16_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
                 // the copies of stage st + 2 spread over the k-steps
                 constexpr int kPerQ = (kPerStage + NQ - 1) / NQ;
 #pragma unroll
-                for (int n = q * kPerQ; n < (q + 1) * kPerQ && n < kPerStage; ++n) issue_one(st + R - 1, (BUF + R - 1) % R, n);
+                for (int n = q * kPerQ; n < (q + 1) * kPerQ && n < kPerStage; ++n) issue_one(st + 2, (BUF + 2) % kBfStages, n);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -663,68 +635,31 @@ fc_bf16_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
         for (int n = 0; n < kPerStage; ++n) issue_one(st, buf, n);
     };
 #pragma unroll
-    for (int b = 0; b < R - 1; ++b)
+    for (int b = 0; b < kBfStages - 1; ++b)
         if (b < nstages) issue(b, b);
-    for (int st = 0; st < nstages; st += R) {
+    for (int st = 0; st < nstages; st += kBfStages) {
         stage(std::integral_constant<int, 0>{}, st);
         if (st + 1 < nstages) stage(std::integral_constant<int, 1>{}, st + 1);
         if (st + 2 < nstages) stage(std::integral_constant<int, 2>{}, st + 2);
-        if constexpr (R > 3) {
-            if (st + 3 < nstages) stage(std::integral_constant<int, 3 % R>{}, st + 3);
-            if (st + 4 < nstages) stage(std::integral_constant<int, 4 % R>{}, st + 4);
-            if (st + 5 < nstages) stage(std::integral_constant<int, 5 % R>{}, st + 5);
-        }
-        static_assert(R == 3 || R == 6, "the stage loop is unrolled for rings of three or six");
     }
     // epilogue: bias + activation; lane = feature, registers = samples; bf16 output: round to nearest even
     const int n0 = nt0 * kBfBN;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
         const int n = n0 + wn * 64 + nt * 32 + li;
-        const float b = a.bias[n];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (m < M && n < a.N) {
-                float v = acc[nt][r] + b;
-                if (a.relu) v = fmaxf(v, 0.0f);
-                if constexpr (YBF16)
-                    reinterpret_cast<unsigned short*>(a.y)[(size_t)m * a.ldy + n] =
-                        (unsigned short)(__builtin_bit_cast(unsigned, pack_bf16(v, 0.0f)) & 0xffffu);
-                else
-                    a.y[(size_t)m * a.ldy + n] = v;
-            }
-        }
+        store_tile32<YBF16>(a, acc[nt], a.bias[n], m0 + wm * 32 + 4 * lh, n, M);
     }
 }
 
 int launch_fc_bf16_dma(hipStream_t s, const GemmArgs& a, int Npad, bool y_bf16, int bk) {
     const int tiles_m = dodt::ceil_div(a.M, kBfBM), tiles_n = Npad / kBfBN;
-    // (DODT_FC_BF16_DMA_RING=6: six stage images instead of three -- measured at the end of round 4: 16.7 -> 14.8 us at
-    //  M = 1024 (one workgroup per CU), 27.8 -> 29.5 / 52.6 -> 59.2 us at M = 2048 / 4096 (two per CU), and 980-992 against
-    //  995-1 012 pairs/s in the bf16 pipeline: opt-in)
-    static const int ring = getenv("DODT_FC_BF16_DMA_RING") && atoi(getenv("DODT_FC_BF16_DMA_RING")) == 6 ? 6 : 3;
-    const int stages = bk == 64 ? kBfStages : ring;
-    const size_t lds = (size_t)stages * (kBfBM + kBfBN) * bk * 2;
-    auto go = [&](auto kernel) -> hipError_t {
-        static std::mutex mu;
-        static std::set<const void*> prepared;
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            if (!prepared.count(reinterpret_cast<const void*>(kernel))) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-                prepared.insert(reinterpret_cast<const void*>(kernel));
-            }
-        }
-        hipLaunchKernelGGL(kernel, dim3(tiles_m * tiles_n), dim3(256), lds, s, a, tiles_m, tiles_n);
-        return hipSuccess;
-    };
+    const dim3 grid(tiles_m * tiles_n);
+    const size_t lds = (size_t)kBfStages * (kBfBM + kBfBN) * bk * 2;
     hipError_t e;
-    if (bk == 64) e = y_bf16 ? go(&fc_bf16_dma_kernel<true, 64>) : go(&fc_bf16_dma_kernel<false, 64>);
-    else if (stages == 6) e = y_bf16 ? go(&fc_bf16_dma_kernel<true, 32, 6>) : go(&fc_bf16_dma_kernel<false, 32, 6>);
-    else e = y_bf16 ? go(&fc_bf16_dma_kernel<true, 32>) : go(&fc_bf16_dma_kernel<false, 32>);
+    if (bk == 64 && y_bf16) e = launch_with_lds(&fc_bf16_dma_kernel<true, 64>, grid, lds, s, a, tiles_m, tiles_n);
+    else if (bk == 64) e = launch_with_lds(&fc_bf16_dma_kernel<false, 64>, grid, lds, s, a, tiles_m, tiles_n);
+    else if (y_bf16) e = launch_with_lds(&fc_bf16_dma_kernel<true, 32>, grid, lds, s, a, tiles_m, tiles_n);
+    else e = launch_with_lds(&fc_bf16_dma_kernel<false, 32>, grid, lds, s, a, tiles_m, tiles_n);
     DODT_HIP_CHECK(e);
     DODT_LAUNCH_CHECK();
     return DODT_OK;
@@ -768,7 +703,7 @@ fc_skinny_kernel(const GemmArgs a, const SplitOut so) {
     __shared__ f32x4 s_part[8][2][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 15, g = lane >> 4;
-    const int M = a.d_m ? min(*a.d_m, a.M) : a.M;
+    const int M = resolved_rows(a.d_m, a.M);
     const int m0 = blockIdx.x * 16;
     if (m0 >= M) return;
     // A operand: lane (g, i) holds sample m0 + i at k-slot g; a 16-byte load covers the slot's four k of a step
@@ -867,7 +802,7 @@ fc_skinny_kernel(const GemmArgs a, const SplitOut so) {
 template <bool BF16>
 __global__ void __launch_bounds__(256)
 fc_smallk_kernel(const GemmArgs a, const float* __restrict__ w_plain) {
-    const int M = a.d_m ? min(*a.d_m, a.M) : a.M;
+    const int M = resolved_rows(a.d_m, a.M);
     const int n4 = a.N >> 2;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int m = (int)(t / n4), c = (int)(t - (long long)m * n4) * 4;
@@ -896,16 +831,19 @@ fc_smallk_kernel(const GemmArgs a, const float* __restrict__ w_plain) {
     }
 }
 
-// the conditions of fc_skinny_kernel (weights blocked for BN = 32, no second input)
-bool skinny_ok(int Npad, int K, const GemmArgs& a) {
-    static const bool on = !(getenv("DODT_FC_SKINNY") && atoi(getenv("DODT_FC_SKINNY")) == 0);
-    return on && Npad == 32 && K % 16 == 0 && a.ldx % 4 == 0 && (size_t)a.x % 16 == 0 && !a.x2;
-}
-
-int launch_fc_skinny(hipStream_t s, const GemmArgs& a, const SplitOut& so, bool bf16, bool x_bf16 = false) {
+int launch_fc_skinny(hipStream_t s, const GemmArgs& a, const SplitOut& so, bool bf16, bool x_bf16) {
     if (x_bf16) hipLaunchKernelGGL((fc_skinny_kernel<true, true>), dim3(dodt::ceil_div(a.M, 16)), dim3(512), 0, s, a, so);
     else if (bf16) hipLaunchKernelGGL(fc_skinny_kernel<true>, dim3(dodt::ceil_div(a.M, 16)), dim3(512), 0, s, a, so);
     else hipLaunchKernelGGL(fc_skinny_kernel<false>, dim3(dodt::ceil_div(a.M, 16)), dim3(512), 0, s, a, so);
+    DODT_LAUNCH_CHECK();
+    return DODT_OK;
+}
+
+int launch_fc_smallk(hipStream_t s, const GemmArgs& a, const float* w_plain, bool bf16) {
+    const long long threads = (long long)a.M * (a.N / 4);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (bf16) hipLaunchKernelGGL(fc_smallk_kernel<true>, grid, dim3(256), 0, s, a, w_plain);
+    else hipLaunchKernelGGL(fc_smallk_kernel<false>, grid, dim3(256), 0, s, a, w_plain);
     DODT_LAUNCH_CHECK();
     return DODT_OK;
 }
@@ -998,7 +936,121 @@ struct dodt_fc {
     void* d_w_dma = nullptr;      // bf16 layers with N % 128 == 0: stage images for fc_bf16_dma_kernel
     int Kd = 0;                   //   ... of K rounded up to 64
     int dma_bk = 0;               //   ... blocked for stages of this many k
+    // what the layer alone allows (dodt_fc_create_ex); the call decides the rest (select_fc_form)
+    bool smallk = false;          // fc_smallk_kernel: the plain weights exist and N >= 64
+    bool skinny = false;          // fc_skinny_kernel: N <= 32 and K % 16 == 0
+    bool dma = false;             // fc_dma_kernel: fp32, 128-wide blocking, K a multiple of a stage and at least two
 };
+
+namespace {
+
+// The kernel forms a layer can run on.  select_fc_form is the only place that picks one.
+enum class FcForm {
+    kNone,             // bf16 rows only: the layer or the call has no kernel that reads them
+    kSmallK,           // fc_smallk_kernel, float32 or bf16 arithmetic as the layer says
+    kSkinny,           // fc_skinny_kernel<false>
+    kSkinnyBf16,       // fc_skinny_kernel<true>: float32 rows rounded on load
+    kSkinnyBf16Rows,   // fc_skinny_kernel<true, true>
+    kDmaNt1,           // fc_dma_kernel<false, 1>: 64 x 64 tiles
+    kDmaNt2,           // fc_dma_kernel<false, 2>: 64 x 128 tiles
+    kDmaFused,         // fc_dma_kernel<true, 1>: the mean of two inputs taken on the fragment
+    kBf16RowsDma32,    // fc_bf16_dma_kernel<., 32>, float32 or bf16 output as the call says
+    kBf16RowsDma64,    // fc_bf16_dma_kernel<., 64>
+    kTiled64x128,      // fc_mfma_kernel, register-staged, 64-k stages
+    kTiled128x32,      //   ... 32-k stages
+    kTiled64x128Bf16,  //   ... bf16 arithmetic on float32 rows, 32-k stages
+    kTiled128x32Bf16,  //   ... 64-k stages
+};
+
+// The kernel form of one call of a layer.  The call: a (x, x2, y, M, ldx, ldy), whether x holds bf16 rows, whether y
+// takes bf16.  The split entries pass a.y = NULL; they accept the skinny forms only.
+FcForm select_fc_form(const dodt_fc& f, const GemmArgs& a, bool x_bf16, bool y_bf16) {
+    if (x_bf16) {
+        if (f.d_w_dma) return f.dma_bk == 64 ? FcForm::kBf16RowsDma64 : FcForm::kBf16RowsDma32;
+        if (f.skinny && a.ldx % 4 == 0 && (size_t)a.x % 8 == 0 && !y_bf16) return FcForm::kSkinnyBf16Rows;
+        return FcForm::kNone;
+    }
+    if (f.smallk && (size_t)a.y % 16 == 0) return FcForm::kSmallK;
+    // (weights blocked for BN = 32, no second input)
+    if (f.skinny && a.ldx % 4 == 0 && (size_t)a.x % 16 == 0 && !a.x2) return f.bf16 ? FcForm::kSkinnyBf16 : FcForm::kSkinny;
+    if (f.bf16) {
+        // Stage depth of the 64 x 128 form.  128 k is the fastest layer alone (343 TFLOP/s at M = 1024, N = K = 2048;
+        // 64: 320, 32: 264) but its two 50 KB buffers leave room for one workgroup per CU and none beside a conv
+        // workgroup; in the frame-pair pipeline, where the heads' GEMMs run in what two resident conv workgroups leave
+        // of a CU (42 KB of LDS, 224 registers), 32 k (27 KB) wins: 802 -> 823 pairs/s with bf16 convs and heads.  The
+        // 64-k and 128-k instances are removed again.
+        return f.BN == 128 ? FcForm::kTiled64x128Bf16 : FcForm::kTiled128x32Bf16;
+    }
+    if (f.BN != 128) return FcForm::kTiled128x32;
+    // the 2048-wide layers: the LDS-DMA staged kernel where the rows are 16-byte aligned
+    if (f.dma && a.ldx % 4 == 0 && (size_t)a.x % 16 == 0 && (!a.x2 || (size_t)a.x2 % 16 == 0)) {
+        if (a.x2) return FcForm::kDmaFused;
+        // 64 x 128 tiles (two MFMA tiles per wave) when that still gives two workgroups per CU -- both frames'
+        // proposals in one launch --, else 64 x 64; never with the fused mean
+        const long tiles128 = (long)dodt::ceil_div(a.M, kDmaBM) * (f.Npad / 128);
+        return tiles128 >= 2 * 256 ? FcForm::kDmaNt2 : FcForm::kDmaNt1;
+    }
+    // Tile shapes of the register-staged kernel measured at the heads' sizes (M = 1024, N = K = 2048): 64x128 with a
+    // 64-deep stage 97 TFLOP/s; 64x64 tiles and 32-deep stages within 3 % of it; 128x128 (2x2 MFMA tiles per wave) 106
+    // at M = 4096 but only 128 workgroups at M = 1024.  Only the first is kept.
+    return FcForm::kTiled64x128;
+}
+
+int launch_fc_form(FcForm form, const dodt_fc& f, hipStream_t s, GemmArgs a, const SplitOut& so, bool y_bf16) {
+    switch (form) {
+    case FcForm::kSmallK: return launch_fc_smallk(s, a, f.d_w_plain, f.bf16);
+    case FcForm::kSkinny: return launch_fc_skinny(s, a, so, false, false);
+    case FcForm::kSkinnyBf16: return launch_fc_skinny(s, a, so, true, false);
+    case FcForm::kSkinnyBf16Rows: return launch_fc_skinny(s, a, so, true, true);
+    case FcForm::kDmaNt1:
+    case FcForm::kDmaFused: return launch_fc_dma(s, a, f.Npad, 1);
+    case FcForm::kDmaNt2: return launch_fc_dma(s, a, f.Npad, 2);
+    case FcForm::kBf16RowsDma32:
+    case FcForm::kBf16RowsDma64:
+        a.w = reinterpret_cast<const float*>(f.d_w_dma);
+        a.Kp = f.Kd;
+        return launch_fc_bf16_dma(s, a, f.Npad, y_bf16, f.dma_bk);
+    case FcForm::kTiled64x128: return launch_fc<64, 128, 2, 2, 64, false>(s, a, f.Npad);
+    case FcForm::kTiled128x32: return launch_fc<128, 32, 4, 1, 32, false>(s, a, f.Npad);
+    case FcForm::kTiled64x128Bf16: return launch_fc<64, 128, 2, 2, 32, true>(s, a, f.Npad);
+    case FcForm::kTiled128x32Bf16: return launch_fc<128, 32, 4, 1, 64, true>(s, a, f.Npad);
+    case FcForm::kNone: break;
+    }
+    dodt::set_error("dodt_fc: no kernel form selected");
+    return DODT_ERR_UNSUPPORTED;
+}
+
+GemmArgs fc_args(const dodt_fc& f, const void* d_x, const float* d_x2, int ldx, int M, const int32_t* d_m, void* d_y,
+                 int ldy) {
+    GemmArgs a;
+    a.x = reinterpret_cast<const float*>(d_x); a.x2 = d_x2; a.w = f.d_w; a.bias = f.d_b; a.y = reinterpret_cast<float*>(d_y);
+    a.M = M; a.K = f.K; a.Kp = f.Kp; a.N = f.N; a.ldx = ldx; a.ldy = ldy; a.relu = f.relu;
+    a.d_m = d_m;
+    return a;
+}
+
+// all columns to one array
+SplitOut whole_out(const dodt_fc& f, void* d_y, int ldy) {
+    float* y = reinterpret_cast<float*>(d_y);
+    return SplitOut{{y, y, y}, {f.N, f.N, f.N}, {ldy, ldy, ldy}};
+}
+
+// the columns of `parts` dense arrays (who: the entry point, for the error texts)
+int split_out(const char* who, const dodt_fc& f, int parts, const int* widths, float* const* d_ys, SplitOut* so) {
+    int end = 0;
+    for (int p = 0; p < 3; ++p) {
+        const int q = p < parts ? p : parts - 1;
+        DODT_REQUIRE(widths[q] >= 1 && d_ys[q], "%s: part %d is empty", who, q);
+        if (p < parts) end += widths[p];
+        so->y[p] = d_ys[q];
+        so->n_end[p] = p < parts ? end : f.N + 1;
+        so->ld[p] = widths[q];
+    }
+    DODT_REQUIRE(end == f.N, "%s: the parts have %d columns, the layer %d", who, end, f.N);
+    return DODT_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1022,6 +1074,8 @@ int dodt_fc_create_ex(dodt_ctx* ctx, int K, int N, const float* w, const float* 
     f->Kp = (int)dodt::align_up((size_t)K, bf16 ? 2 * kKAlign : kKAlign);
     f->BN = (N >= 128) ? 128 : 32;
     f->Npad = (int)dodt::align_up((size_t)N, (size_t)f->BN);
+    f->skinny = f->Npad == 32 && K % 16 == 0;
+    f->dma = !bf16 && f->BN == 128 && K % kDmaBK == 0 && K >= 2 * kDmaBK;
     // blocked weights [n-tile][Kp/8][h][BN][4]; k = 8q + 4h + s
     std::vector<float> blk((size_t)f->Kp * f->Npad, 0.0f), b(f->Npad, 0.0f);
     //   bf16: [n-tile][Kp/16][h][BN][8] bf16 (k = 16q + 8h + s), in the first half of blk
@@ -1080,6 +1134,7 @@ int dodt_fc_create_ex(dodt_ctx* ctx, int K, int N, const float* w, const float* 
         }
         DODT_HIP_CHECK(hipMemcpyAsync(f->d_w_plain, plain.data(), plain.size() * sizeof(float),
                                       hipMemcpyHostToDevice, ctx->stream));
+        f->smallk = N >= 64;
     }
     DODT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     *out = f;
@@ -1101,56 +1156,9 @@ int dodt_fc_forward(dodt_fc* f, dodt_ctx* ctx, const float* d_x, const float* d_
     DODT_REQUIRE(f && d_x && d_y, "dodt_fc_forward: NULL argument");
     DODT_REQUIRE(M >= 0 && ldx >= f->K && ldy >= f->N, "dodt_fc_forward: bad strides");
     if (M == 0) return DODT_OK;
-    GemmArgs a;
-    a.x = d_x; a.x2 = d_x2; a.w = f->d_w; a.bias = f->d_b; a.y = d_y;
-    a.M = M; a.K = f->K; a.Kp = f->Kp; a.N = f->N; a.ldx = ldx; a.ldy = ldy; a.relu = f->relu;
-    a.d_m = d_m;
-    hipStream_t s = (ctx ? ctx : f->ctx)->stream;
-    static const bool smallk = !(getenv("DODT_FC_SMALLK") && atoi(getenv("DODT_FC_SMALLK")) == 0);
-    if (smallk && f->d_w_plain && f->N >= 64 && (size_t)d_y % 16 == 0) {
-        const long long threads = (long long)M * (f->N / 4);
-        if (f->bf16)
-            hipLaunchKernelGGL(fc_smallk_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a,
-                               f->d_w_plain);
-        else
-            hipLaunchKernelGGL(fc_smallk_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a,
-                               f->d_w_plain);
-        DODT_LAUNCH_CHECK();
-        return DODT_OK;
-    }
-    if (skinny_ok(f->Npad, f->K, a)) {
-        SplitOut so = {{d_y, d_y, d_y}, {f->N, f->N, f->N}, {ldy, ldy, ldy}};
-        return launch_fc_skinny(s, a, so, f->bf16);
-    }
-    if (f->bf16) {
-        if (f->BN == 128) {
-            // Stage depth (DODT_FC_BF16_BK).  128 k is the fastest layer alone (343 TFLOP/s at M = 1024, N = K = 2048;
-            // 64: 320, 32: 264) but its two 50 KB buffers leave room for one workgroup per CU and none beside a conv
-            // workgroup; in the frame-pair pipeline, where the heads' GEMMs run in what two resident conv workgroups leave
-            // of a CU (42 KB of LDS, 224 registers), 32 k (27 KB) wins: 802 -> 823 pairs/s with bf16 convs and heads.
-            static const int bk = getenv("DODT_FC_BF16_BK") ? atoi(getenv("DODT_FC_BF16_BK")) : 32;
-            if (bk == 64) return launch_fc<64, 128, 2, 2, 128, 64, true>(s, a, f->Npad);
-            if (bk == 32) return launch_fc<64, 128, 2, 2, 128, 32, true>(s, a, f->Npad);
-            return launch_fc<64, 128, 2, 2, 128, 128, true>(s, a, f->Npad);
-        }
-        return launch_fc<128, 32, 4, 1, 32, 64, true>(s, a, f->Npad);
-    }
-    if (f->BN == 128) {
-        // the 2048-wide layers: LDS-DMA staged kernel (DODT_FC_DMA=0: the register-staged one)
-        static const bool dma = !(getenv("DODT_FC_DMA") && atoi(getenv("DODT_FC_DMA")) == 0);
-        if (dma && f->K % kDmaBK == 0 && ldx % 4 == 0 && f->K >= 2 * kDmaBK &&
-            ((size_t)d_x % 16 == 0) && (!d_x2 || (size_t)d_x2 % 16 == 0))
-            return launch_fc_dma(s, a, f->Npad);
-        // tile shapes measured at the heads' sizes (M = 1024, N = K = 2048): 64x128 with a
-        // 64-deep stage 97 TFLOP/s; 64x64 tiles and 32-deep stages within 3 % of it; 128x128
-        // (2x2 MFMA tiles per wave) 106 at M = 4096 but only 128 workgroups at M = 1024
-        static const int tile = getenv("DODT_FC_TILE") ? atoi(getenv("DODT_FC_TILE")) : 0;
-        if (tile == 256) return launch_fc<128, 128, 2, 2, 128, 32>(s, a, f->Npad);
-        if (tile == 64) return launch_fc<64, 64, 2, 2, 128>(s, a, f->Npad);
-        if (tile == 32) return launch_fc<64, 128, 2, 2, 128, 32>(s, a, f->Npad);
-        return launch_fc<64, 128, 2, 2, 128, 64>(s, a, f->Npad);
-    }
-    return launch_fc<128, 32, 4, 1>(s, a, f->Npad);
+    const GemmArgs a = fc_args(*f, d_x, d_x2, ldx, M, d_m, d_y, ldy);
+    return launch_fc_form(select_fc_form(*f, a, false, false), *f, (ctx ? ctx : f->ctx)->stream, a,
+                          whole_out(*f, d_y, ldy), false);
 }
 
 int dodt_fc_forward_split(dodt_fc* f, dodt_ctx* ctx, const float* d_x, int ldx, int M, const int32_t* d_m,
@@ -1158,34 +1166,23 @@ int dodt_fc_forward_split(dodt_fc* f, dodt_ctx* ctx, const float* d_x, int ldx, 
     DODT_REQUIRE(f && d_x && widths && d_ys, "dodt_fc_forward_split: NULL argument");
     DODT_REQUIRE(parts >= 1 && parts <= 3, "dodt_fc_forward_split: %d parts (1..3)", parts);
     DODT_REQUIRE(M >= 0 && ldx >= f->K, "dodt_fc_forward_split: bad strides");
-    GemmArgs a;
-    a.x = d_x; a.x2 = nullptr; a.w = f->d_w; a.bias = f->d_b; a.y = nullptr;
-    a.M = M; a.K = f->K; a.Kp = f->Kp; a.N = f->N; a.ldx = ldx; a.ldy = 0; a.relu = f->relu;
-    a.d_m = d_m;
+    const GemmArgs a = fc_args(*f, d_x, nullptr, ldx, M, d_m, nullptr, 0);
     SplitOut so;
-    int end = 0;
-    for (int p = 0; p < 3; ++p) {
-        const int q = p < parts ? p : parts - 1;
-        DODT_REQUIRE(widths[q] >= 1 && d_ys[q], "dodt_fc_forward_split: part %d is empty", q);
-        if (p < parts) end += widths[p];
-        so.y[p] = d_ys[q];
-        so.n_end[p] = p < parts ? end : f->N + 1;
-        so.ld[p] = widths[q];
-    }
-    DODT_REQUIRE(end == f->N, "dodt_fc_forward_split: the parts have %d columns, the layer %d", end, f->N);
-    if (!skinny_ok(f->Npad, f->K, a)) {
+    if (int rc = split_out("dodt_fc_forward_split", *f, parts, widths, d_ys, &so)) return rc;
+    const FcForm form = select_fc_form(*f, a, false, false);
+    if (form != FcForm::kSkinny && form != FcForm::kSkinnyBf16) {
         dodt::set_error("dodt_fc_forward_split: layers with N <= 32, K %% 16 == 0 and 16-byte aligned rows only");
         return DODT_ERR_UNSUPPORTED;
     }
     if (M == 0) return DODT_OK;
-    return launch_fc_skinny((ctx ? ctx : f->ctx)->stream, a, so, f->bf16);
+    return launch_fc_form(form, *f, (ctx ? ctx : f->ctx)->stream, a, so, false);
 }
 
 int dodt_fc_bf16_row_elems(const dodt_fc* f) {
     // bf16 elements an input row of dodt_fc_forward_bf16 must hold (zeros beyond K): 0 = the layer has no such path
     if (!f || !f->bf16) return 0;
     if (f->d_w_dma) return f->Kd;
-    return (f->Npad == 32 && f->K % 16 == 0) ? f->K : 0;
+    return f->skinny ? f->K : 0;
 }
 
 int dodt_fc_forward_bf16(dodt_fc* f, dodt_ctx* ctx, const void* d_x_bf16, int ldx, int M, const int32_t* d_m,
@@ -1194,28 +1191,20 @@ int dodt_fc_forward_bf16(dodt_fc* f, dodt_ctx* ctx, const void* d_x_bf16, int ld
     DODT_REQUIRE(f->bf16, "dodt_fc_forward_bf16: the layer was not created with DODT_FC_BF16");
     DODT_REQUIRE(M >= 0 && ldy >= f->N, "dodt_fc_forward_bf16: bad strides");
     if (M == 0) return DODT_OK;
-    GemmArgs a;
-    a.x = reinterpret_cast<const float*>(d_x_bf16); a.x2 = nullptr; a.bias = f->d_b; a.y = reinterpret_cast<float*>(d_y);
-    a.M = M; a.K = f->K; a.N = f->N; a.ldx = ldx; a.ldy = ldy; a.relu = f->relu; a.d_m = d_m;
-    hipStream_t s = (ctx ? ctx : f->ctx)->stream;
-    if (f->d_w_dma) {
+    const GemmArgs a = fc_args(*f, d_x_bf16, nullptr, ldx, M, d_m, d_y, ldy);
+    const FcForm form = select_fc_form(*f, a, true, y_bf16 != 0);
+    if (form == FcForm::kBf16RowsDma32 || form == FcForm::kBf16RowsDma64) {
         DODT_REQUIRE(ldx >= f->Kd && ldx % 8 == 0 && (size_t)d_x_bf16 % 16 == 0,
                      "dodt_fc_forward_bf16: rows of >= %d bf16 (zeros beyond K = %d), 16-byte aligned", f->Kd, f->K);
         DODT_REQUIRE((size_t)M * ldx * 2 < (1ull << 31), "dodt_fc_forward_bf16: x block beyond 2 GB");
-        a.w = reinterpret_cast<const float*>(f->d_w_dma);
-        a.Kp = f->Kd;
-        return launch_fc_bf16_dma(s, a, f->Npad, y_bf16 != 0, f->dma_bk);
-    }
-    if (f->Npad == 32 && f->K % 16 == 0 && ldx % 4 == 0 && (size_t)d_x_bf16 % 8 == 0 && !y_bf16) {
+    } else if (form == FcForm::kSkinnyBf16Rows) {
         DODT_REQUIRE(ldx >= f->K, "dodt_fc_forward_bf16: bad strides");
-        a.w = f->d_w; a.Kp = f->Kp;
-        float* y = reinterpret_cast<float*>(d_y);
-        SplitOut so = {{y, y, y}, {f->N, f->N, f->N}, {ldy, ldy, ldy}};
-        return launch_fc_skinny(s, a, so, true, true);
+    } else {
+        dodt::set_error("dodt_fc_forward_bf16: layers with N %% 128 == 0 and K >= 128, or N <= 32 and K %% 16 == 0 with "
+                        "float32 output, only (K = %d, N = %d)", f->K, f->N);
+        return DODT_ERR_UNSUPPORTED;
     }
-    dodt::set_error("dodt_fc_forward_bf16: layers with N %% 128 == 0 and K >= 128, or N <= 32 and K %% 16 == 0 with "
-                    "float32 output, only (K = %d, N = %d)", f->K, f->N);
-    return DODT_ERR_UNSUPPORTED;
+    return launch_fc_form(form, *f, (ctx ? ctx : f->ctx)->stream, a, whole_out(*f, d_y, ldy), y_bf16 != 0);
 }
 
 int dodt_fc_forward_split_bf16(dodt_fc* f, dodt_ctx* ctx, const void* d_x_bf16, int ldx, int M, const int32_t* d_m,
@@ -1224,27 +1213,16 @@ int dodt_fc_forward_split_bf16(dodt_fc* f, dodt_ctx* ctx, const void* d_x_bf16, 
     DODT_REQUIRE(f->bf16, "dodt_fc_forward_split_bf16: the layer was not created with DODT_FC_BF16");
     DODT_REQUIRE(parts >= 1 && parts <= 3, "dodt_fc_forward_split_bf16: %d parts (1..3)", parts);
     DODT_REQUIRE(M >= 0 && ldx >= f->K, "dodt_fc_forward_split_bf16: bad strides");
-    GemmArgs a;
-    a.x = reinterpret_cast<const float*>(d_x_bf16); a.x2 = nullptr; a.w = f->d_w; a.bias = f->d_b; a.y = nullptr;
-    a.M = M; a.K = f->K; a.Kp = f->Kp; a.N = f->N; a.ldx = ldx; a.ldy = 0; a.relu = f->relu;
-    a.d_m = d_m;
+    const GemmArgs a = fc_args(*f, d_x_bf16, nullptr, ldx, M, d_m, nullptr, 0);
     SplitOut so;
-    int end = 0;
-    for (int p = 0; p < 3; ++p) {
-        const int q = p < parts ? p : parts - 1;
-        DODT_REQUIRE(widths[q] >= 1 && d_ys[q], "dodt_fc_forward_split_bf16: part %d is empty", q);
-        if (p < parts) end += widths[p];
-        so.y[p] = d_ys[q];
-        so.n_end[p] = p < parts ? end : f->N + 1;
-        so.ld[p] = widths[q];
-    }
-    DODT_REQUIRE(end == f->N, "dodt_fc_forward_split_bf16: the parts have %d columns, the layer %d", end, f->N);
-    if (!(f->Npad == 32 && f->K % 16 == 0 && ldx % 4 == 0 && (size_t)d_x_bf16 % 8 == 0)) {
+    if (int rc = split_out("dodt_fc_forward_split_bf16", *f, parts, widths, d_ys, &so)) return rc;
+    const FcForm form = select_fc_form(*f, a, true, false);
+    if (form != FcForm::kSkinnyBf16Rows) {
         dodt::set_error("dodt_fc_forward_split_bf16: layers with N <= 32, K %% 16 == 0 and 8-byte aligned rows only");
         return DODT_ERR_UNSUPPORTED;
     }
     if (M == 0) return DODT_OK;
-    return launch_fc_skinny((ctx ? ctx : f->ctx)->stream, a, so, true, true);
+    return launch_fc_form(form, *f, (ctx ? ctx : f->ctx)->stream, a, so, false);
 }
 
 double dodt_fc_flops(const dodt_fc* f, int M) {

@@ -4,7 +4,6 @@ These are what the frame-pair pipeline is made of; the avod.core-shaped host API
 in dodt_amd/core/ wraps them with numpy upload/download.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -365,8 +364,7 @@ class FullyConnected(object):
 
     def can_split(self, ldx=None):
         """Whether forward_split takes this layer (dodt_fc_forward_split's conditions)."""
-        return self.N <= 32 and self.K % 16 == 0 and \
-            (self.K if ldx is None else ldx) % 4 == 0 and os.environ.get('DODT_FC_SKINNY') != '0'
+        return self.N <= 32 and self.K % 16 == 0 and (self.K if ldx is None else ldx) % 4 == 0
 
     def forward_split(self, d_x, M, d_ys, widths, ldx=None, d_m=None, ctx=None):
         """One launch, columns [0, widths[0]) to d_ys[0] (M, widths[0]), the next widths[1] to d_ys[1], ..."""

@@ -70,6 +70,8 @@ def test_correlation_full_size_properties(ctx):
     (1000, 2048, 10, False, False),    # off_out
     (513, 1225, 2048, True, False),    # corr fc6: K not a multiple of 4
     (1, 40, 3, False, False), (64, 32, 128, True, False),
+    # N <= 32 with K % 16 != 0: the 128 x 32 register-staged kernel with scalar loads, the mean fused, K padded
+    (37, 9, 6, True, True),
     # the split-K kernel of the skinny layers (N <= 32, K % 16 == 0): few steps, ragged M, ReLU, 32 columns
     (1024, 2048, 2, False, False), (37, 16, 5, True, False), (5, 48, 32, False, False),
     (2000, 528, 17, True, False),
@@ -97,7 +99,9 @@ def test_fully_connected_matches_oracle(ctx, M, K, N, relu, fuse):
 
 @pytest.mark.parametrize('M,K,N,relu,fuse', [
     (300, 9, 512, True, True), (1024, 1568, 2048, True, True), (1000, 2048, 10, False, False),
-    (513, 1225, 2048, True, False), (777, 256, 6, False, False), (64, 40, 128, True, False)])
+    (513, 1225, 2048, True, False), (777, 256, 6, False, False), (64, 40, 128, True, False),
+    # N <= 32 with K % 16 != 0: the bf16 128 x 32 register-staged kernel, vector loads (K % 8 == 0) and scalar loads
+    (37, 40, 3, False, False), (37, 9, 6, True, True)])
 def test_fully_connected_bf16_matches_its_oracle(ctx, M, K, N, relu, fuse):
     """DODT_FC_BF16: same rounding points as the oracle's restatement, so only the fp32
     summation order differs: 1e-4 of the output scale like the fp32 layers.  Against the fp32
