@@ -160,6 +160,11 @@ SIGNATURES = {
     'dodt_pack_detections': (_i, [_vp, _pf, _pf, _pf, _pf, _pi32, _pi32, _i, _f, _pf, _pi32]),
     'dodt_pack_detections_compact': (_i, [_vp, _pf, _pf, _pf, _pf, _pi32, _pi32, _i, _f, _pf, _pi32]),
     'dodt_angle_vector_to_orientation': (_i, [_vp, _pf, _i, _pi32, _pf]),
+    'dodt_class_scores': (_i, [_vp, _pf, _i, _i, _pi32, _pf, _pi32]),
+    'dodt_final_decode_classes': (_i, [_vp, _pf, _pf, _pf, _i, _pf, _i, _pi32, C.POINTER(_f), C.POINTER(_f),
+                                       _pf, _pf, _pf, _pf, _pf, _pi32, _pf]),
+    'dodt_pack_detections_classes': (_i, [_vp, _pf, _pf, _pi32, _pf, _pf, _pi32, _pi32, _i, _f, _pf, _pi32]),
+    'dodt_pack_detections_compact_classes': (_i, [_vp, _pf, _pf, _pi32, _pf, _pf, _pi32, _pi32, _i, _f, _pf, _pi32]),
     'dodt_box_4c_decode': (_i, [_vp, _pf, _pf, _i, _pi32, C.POINTER(_f),
                                 C.POINTER(_f), _pf, _pf, _pf]),
     'dodt_comm_unique_id': (_i, [_vp]),

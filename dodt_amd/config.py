@@ -8,6 +8,18 @@ so they are stored here exactly as python sees them in the reference
 
   PYRAMID_DODT  avod/configs/pyramid_cars_with_aug_dt_5_tracking.config
   CARS_EXAMPLE  avod/configs/avod_cars_example.config
+
+and the second family of the reference's configurations, two classes in one model
+(throughput unmeasured):
+
+  PYRAMID_PEOPLE  avod/configs/pyramid_people_example.config
+  AVOD_PEOPLE     avod/configs/avod_people_example.config
+
+Class-aware keys: `classes` names the detected classes in the order of the stage-2 head's
+non-background columns; with `anchor_strides` (one [x, z] stride pair per class) `anchor_sizes`
+holds one list of clusters per class.  A configuration without `anchor_strides` has one
+class, whose clusters are `anchor_sizes` and whose stride is `anchor_stride`
+(class_anchor_params()).
 """
 import numpy as np
 
@@ -45,6 +57,7 @@ _COMMON = dict(
     # avod_box_representation (both configs, e.g. ...dt_5_tracking.config:29): box_4c offsets
     # plus a regressed angle vector that fixes the heading (dt_evaluator.py:1166-1212)
     box_representation='box_4ca',
+    classes=('Car',),
 )
 
 # frames_per_sample: 2 = DODT's Siamese model over a (t, t + tau) frame pair with the
@@ -66,6 +79,43 @@ CARS_EXAMPLE = dict(_COMMON,
                     extractor='vgg',
                     img_dims=(480, 1590),
                     img_depth=3)
+
+# Two classes (avod/configs/pyramid_people_example.config:143-152, avod_people_example.config:142-151): the anchor grid
+# is tiled once per class and concatenated, class-major (dt_rpn_model.py:894-909); the stage-2 head has one column per
+# class behind the background's.  The reference clusters the sizes from the training labels, which are not part of this
+# build; stand-ins (l, w, h), one cluster per class.
+_PEOPLE = dict(classes=('Pedestrian', 'Cyclist'),
+               anchor_sizes=[[[0.844, 0.661, 1.763]], [[1.763, 0.597, 1.737]]],
+               anchor_strides=[[_f32(0.5), _f32(0.5)], [_f32(0.5), _f32(0.5)]],
+               rpn_test_nms_size=1024)
+
+PYRAMID_PEOPLE = dict(_COMMON, **dict(_PEOPLE,
+                                      name='pyramid_people_example',
+                                      model='avod_model',
+                                      frames_per_sample=1,
+                                      extractor='vgg_pyr',
+                                      img_dims=(360, 1200),
+                                      img_depth=3))
+
+AVOD_PEOPLE = dict(_COMMON, **dict(_PEOPLE,
+                                   name='avod_people_example',
+                                   model='avod_model',
+                                   frames_per_sample=1,
+                                   extractor='vgg',
+                                   img_dims=(480, 1590),
+                                   img_depth=3))
+
+
+def class_anchor_params(cfg):
+    """(sizes_per_class, strides_per_class) of a configuration: its per-class keys, or the one class that
+    `anchor_sizes` / `anchor_stride` describe."""
+    if 'anchor_strides' in cfg:
+        sizes, strides = list(cfg['anchor_sizes']), list(cfg['anchor_strides'])
+        if len(sizes) != len(strides) or len(sizes) != len(cfg.get('classes', sizes)):
+            raise ValueError('anchor_sizes, anchor_strides and classes must have one entry per class')
+        return sizes, strides
+    return [cfg['anchor_sizes']], [cfg['anchor_stride']]
+
 
 # Calibration of the tracking sequence the reference's tests bundle
 # (avod/tests/datasets/Kitti/tracking/training/calib/0000.txt, numbers only) and the KITTI

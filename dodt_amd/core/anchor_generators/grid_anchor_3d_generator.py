@@ -32,6 +32,15 @@ def tile_anchors_3d(area_extents, anchor_3d_sizes, anchor_stride, ground_plane):
     return out
 
 
+def tile_anchors_3d_classes(area_extents, sizes_per_class, strides_per_class, ground_plane):
+    """tile_anchors_3d once per class, concatenated in class order (dt_rpn_model.py:894-909): sizes_per_class[c] the
+    (k_c, 3) clusters and strides_per_class[c] the [x, z] stride of class c."""
+    if len(sizes_per_class) != len(strides_per_class) or not len(sizes_per_class):
+        raise ValueError('one list of sizes and one stride pair per class')
+    return np.concatenate([tile_anchors_3d(area_extents, s, st, ground_plane)
+                           for s, st in zip(sizes_per_class, strides_per_class)], axis=0)
+
+
 def box_3d_to_anchor(boxes_3d, ortho_rotate=False):
     """avod/core/box_3d_encoder.py:85-132 (numpy branch, float64)."""
     b = np.asarray(boxes_3d, dtype=np.float64).reshape(-1, 7)

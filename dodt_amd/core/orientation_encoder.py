@@ -19,11 +19,12 @@ def tf_angle_vector_to_orientation(angle_vectors, ctx=None):
 
 
 def predicted_boxes_3d_and_scores(boxes_3d, scores, orientations=None, corr_offsets=None,
-                                  frame_mark=0, ctx=None):
+                                  frame_mark=0, ctx=None, types=None):
     """One frame's share of DtEvaluator.get_avod_predicted_boxes_3d_and_scores
     (dt_evaluator.py:1134-1259): (n,7) box_3d rows after NMS #2, their scores, the regressed
     orientations (box_4ca; None for box_4c) and, for frame 0 of a pair, the correlation offsets
-    -> (n,17) float32 records."""
+    -> (n,17) float32 records.  types: None (one class, column 8 is 0) or the (n,) class indices
+    of the boxes, np.argmax of the non-background softmax columns (:1226-1255)."""
     b = np.asarray(boxes_3d, dtype=np.float32)
     n = len(b)
     if b.ndim != 2 or b.shape[1] != 7:
@@ -34,11 +35,16 @@ def predicted_boxes_3d_and_scores(boxes_3d, scores, orientations=None, corr_offs
     d_rec, d_cnt = ctx.empty((n, 17), np.float32), ctx.empty((1,), np.int32)
     sel = ctx.array(np.arange(n, dtype=np.int32))
     cnt = ctx.array(np.array([n], np.int32))
-    ops.pack_detections(
-        ctx, ctx.array(b), ctx.array(np.asarray(scores, np.float32)), sel, cnt, n,
-        float(frame_mark), d_rec, d_cnt,
-        d_corr_offsets=None if corr_offsets is None
-        else ctx.array(np.asarray(corr_offsets, np.float32)),
-        d_orientations=None if orientations is None
-        else ctx.array(np.asarray(orientations, np.float32)))
+    d_corr = None if corr_offsets is None else ctx.array(np.asarray(corr_offsets, np.float32))
+    d_ori = None if orientations is None else ctx.array(np.asarray(orientations, np.float32))
+    d_scores = ctx.array(np.asarray(scores, np.float32))
+    if types is None:
+        ops.pack_detections(ctx, ctx.array(b), d_scores, sel, cnt, n, float(frame_mark), d_rec, d_cnt,
+                            d_corr_offsets=d_corr, d_orientations=d_ori)
+    else:
+        t = np.asarray(types, np.int32)
+        if t.shape != (n,):
+            raise ValueError('types must be (N,)')
+        ops.pack_detections_classes(ctx, ctx.array(b), d_scores, ctx.array(t), sel, cnt, n, float(frame_mark),
+                                    d_rec, d_cnt, d_corr_offsets=d_corr, d_orientations=d_ori)
     return d_rec.download()

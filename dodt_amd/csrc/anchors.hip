@@ -304,6 +304,54 @@ max_fg_logit_kernel(const float* __restrict__ logits, int n_cls, int n,
     out[i] = m;
 }
 
+// Several classes (dt_evaluator.py:1226-1255): tf.nn.softmax of a row of n_cls logits in float32 -- max-subtracted,
+// the exponentials summed in column order, each divided by the sum --, the record's score the largest non-background
+// value and its type that value's index among the non-background columns, the FIRST maximum as np.argmax gives (over
+// the softmax values, not the logits: two logits a rounding apart can share one).  nms: the largest non-background
+// logit (dt_avod_model.py:606).  At n_cls == 2 the score is softmax_fg_elem's, operation for operation.
+constexpr int kMaxClasses = 8;
+
+__device__ __forceinline__ void class_scores_elem(const float* __restrict__ l, int n_cls, float& score, int& type,
+                                                  float& nms) {
+    float e[kMaxClasses];
+    float m = l[0];
+#pragma unroll
+    for (int c = 1; c < kMaxClasses; ++c)
+        if (c < n_cls) m = fmaxf(m, l[c]);
+    float sum = 0.0f, fg = l[1];
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c)
+        if (c < n_cls) {
+            e[c] = expf(l[c] - m);
+            sum = c ? sum + e[c] : e[c];
+            if (c >= 2) fg = fmaxf(fg, l[c]);
+        }
+    float best = e[1] / sum;
+    int arg = 0;
+#pragma unroll
+    for (int c = 2; c < kMaxClasses; ++c)
+        if (c < n_cls) {
+            const float p = e[c] / sum;
+            if (p > best) { best = p; arg = c - 1; }
+        }
+    score = best;
+    type = arg;
+    nms = fg;
+}
+
+__global__ void __launch_bounds__(256)
+class_scores_kernel(const float* __restrict__ logits, int n_cls, int n, const int* __restrict__ d_n,
+                    float* __restrict__ scores, int* __restrict__ types) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lim = d_n ? min(*d_n, n) : n;
+    if (i >= lim) return;
+    float score, nms;
+    int type;
+    class_scores_elem(logits + (size_t)i * n_cls, n_cls, score, type, nms);
+    scores[i] = score;
+    types[i] = type;
+}
+
 // dt_evaluator.py:1166-1212 (box_rep 'box_4ca'): the box decoded from four corners knows its
 // heading modulo 90 / 180 degrees only; the regressed angle decides.  float32, unfused, the
 // thresholds as float32(k * pi) like numpy's scalar-with-array comparisons.
@@ -330,7 +378,8 @@ __global__ void __launch_bounds__(256)
 pack_detections_kernel(const float* __restrict__ boxes_3d, const float* __restrict__ scores,
                        const float* __restrict__ orientations, const float* __restrict__ corr,
                        const int* __restrict__ sel, const int* __restrict__ d_count, int max_det,
-                       float frame_mark, float* __restrict__ rec, int* __restrict__ count_out, int corr_compact) {
+                       float frame_mark, float* __restrict__ rec, int* __restrict__ count_out, int corr_compact,
+                       const int* __restrict__ types) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int cnt = min(*d_count, max_det);
     if (t == 0) *count_out = cnt;
@@ -340,6 +389,7 @@ pack_detections_kernel(const float* __restrict__ boxes_3d, const float* __restri
     if (row < cnt) {
         const int src = sel[row];
         if (col == 7) v = scores[src];
+        else if (col == 8) v = types ? (float)types[src] : 0.0f;      // (one class: type 0)
         else if (col == 16) v = frame_mark;
         else if (col < 7 || (col >= 9 && corr)) {
             float b[7];
@@ -498,6 +548,27 @@ final_decode_kernel(const float* __restrict__ top_anchors, const float* __restri
     if (orientations) orientations[i] = atan2f(angle_vec[2 * i + 1], angle_vec[2 * i]);
 }
 
+// ... with n_cls logits per row: the same box arithmetic, the scores of class_scores_elem and the record's type
+__global__ void __launch_bounds__(256)
+final_decode_classes_kernel(const float* __restrict__ top_anchors, const float* __restrict__ offsets,
+                            const float* __restrict__ cls_logits, int n_cls, const float* __restrict__ angle_vec, int n,
+                            const int* __restrict__ d_n, const DecodeParams P, float* __restrict__ boxes_3d,
+                            float* __restrict__ pred_anchors, float* __restrict__ bev_tf, float* __restrict__ nms_scores,
+                            float* __restrict__ det_scores, int* __restrict__ det_types,
+                            float* __restrict__ orientations) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lim = d_n ? min(*d_n, n) : n;
+    if (i >= lim) return;
+    box_4c_decode_elem(i, top_anchors, offsets, P, boxes_3d, pred_anchors, bev_tf);
+    float score, nms;
+    int type;
+    class_scores_elem(cls_logits + (size_t)i * n_cls, n_cls, score, type, nms);
+    nms_scores[i] = nms;
+    det_scores[i] = score;
+    det_types[i] = type;
+    if (orientations) orientations[i] = atan2f(angle_vec[2 * i + 1], angle_vec[2 * i]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -618,6 +689,41 @@ int dodt_final_decode(dodt_ctx* ctx, const float* d_top_anchors, const float* d_
     return DODT_OK;
 }
 
+int dodt_final_decode_classes(dodt_ctx* ctx, const float* d_top_anchors, const float* d_offsets,
+                              const float* d_cls_logits, int n_cls, const float* d_angle_vectors, int n,
+                              const int32_t* d_n, const float plane[4], const float bev_extents[4],
+                              float* d_boxes_3d_out, float* d_pred_anchors_out, float* d_bev_tf_out,
+                              float* d_nms_scores_out, float* d_det_scores_out, int32_t* d_det_types_out,
+                              float* d_orientations_out) {
+    DODT_REQUIRE(ctx && d_top_anchors && d_offsets && d_cls_logits && plane && bev_extents && d_nms_scores_out &&
+                     d_det_scores_out && d_det_types_out &&
+                     (d_angle_vectors != nullptr) == (d_orientations_out != nullptr),
+                 "dodt_final_decode_classes: bad argument");
+    DODT_REQUIRE(n_cls >= 2 && n_cls <= kMaxClasses, "dodt_final_decode_classes: n_cls must be 2..8");
+    if (n <= 0) return DODT_OK;
+    DecodeParams P;
+    P.a = plane[0]; P.b = plane[1]; P.c = plane[2]; P.d = plane[3];
+    P.x_min = bev_extents[0]; P.x_max = bev_extents[1];
+    P.z_min = bev_extents[2]; P.z_max = bev_extents[3];
+    hipLaunchKernelGGL(final_decode_classes_kernel, dim3(dodt::ceil_div(n, 256)), dim3(256), 0, ctx->stream,
+                       d_top_anchors, d_offsets, d_cls_logits, n_cls, d_angle_vectors, n, d_n, P, d_boxes_3d_out,
+                       d_pred_anchors_out, d_bev_tf_out, d_nms_scores_out, d_det_scores_out, d_det_types_out,
+                       d_orientations_out);
+    DODT_LAUNCH_CHECK();
+    return DODT_OK;
+}
+
+int dodt_class_scores(dodt_ctx* ctx, const float* d_logits, int n_cls, int n, const int32_t* d_n,
+                      float* d_scores_out, int32_t* d_types_out) {
+    DODT_REQUIRE(ctx && d_logits && d_scores_out && d_types_out, "dodt_class_scores: NULL argument");
+    DODT_REQUIRE(n_cls >= 2 && n_cls <= kMaxClasses, "dodt_class_scores: n_cls must be 2..8");
+    if (n <= 0) return DODT_OK;
+    hipLaunchKernelGGL(class_scores_kernel, dim3(dodt::ceil_div(n, 256)), dim3(256), 0, ctx->stream, d_logits, n_cls,
+                       n, d_n, d_scores_out, d_types_out);
+    DODT_LAUNCH_CHECK();
+    return DODT_OK;
+}
+
 int dodt_offset_to_anchor(dodt_ctx* ctx, const float* d_anchors, const float* d_offsets, int n,
                           const int32_t* d_n, float* d_out) {
     DODT_REQUIRE(ctx && d_anchors && d_offsets && d_out, "dodt_offset_to_anchor: NULL argument");
@@ -662,13 +768,13 @@ namespace {
 int launch_pack_detections(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores,
                            const float* d_orientations, const float* d_corr_offsets, int corr_compact,
                            const int32_t* d_sel, const int32_t* d_count, int max_det,
-                           float frame_mark, float* d_rec_out, int32_t* d_count_out) {
+                           float frame_mark, float* d_rec_out, int32_t* d_count_out, const int32_t* d_types) {
     DODT_REQUIRE(ctx && d_boxes_3d && d_scores && d_sel && d_count && d_rec_out && d_count_out &&
                      max_det > 0,
                  "dodt_pack_detections: bad argument");
     hipLaunchKernelGGL(pack_detections_kernel, dim3(dodt::ceil_div(max_det * 17, 256)), dim3(256),
                        0, ctx->stream, d_boxes_3d, d_scores, d_orientations, d_corr_offsets, d_sel,
-                       d_count, max_det, frame_mark, d_rec_out, d_count_out, corr_compact);
+                       d_count, max_det, frame_mark, d_rec_out, d_count_out, corr_compact, d_types);
     DODT_LAUNCH_CHECK();
     return DODT_OK;
 }
@@ -679,7 +785,7 @@ int dodt_pack_detections(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_
                          const int32_t* d_sel, const int32_t* d_count, int max_det,
                          float frame_mark, float* d_rec_out, int32_t* d_count_out) {
     return launch_pack_detections(ctx, d_boxes_3d, d_scores, d_orientations, d_corr_offsets, 0, d_sel, d_count,
-                                  max_det, frame_mark, d_rec_out, d_count_out);
+                                  max_det, frame_mark, d_rec_out, d_count_out, nullptr);
 }
 
 int dodt_pack_detections_compact(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores,
@@ -687,7 +793,23 @@ int dodt_pack_detections_compact(dodt_ctx* ctx, const float* d_boxes_3d, const f
                                  const int32_t* d_sel, const int32_t* d_count, int max_det,
                                  float frame_mark, float* d_rec_out, int32_t* d_count_out) {
     return launch_pack_detections(ctx, d_boxes_3d, d_scores, d_orientations, d_det_offsets, 1, d_sel, d_count,
-                                  max_det, frame_mark, d_rec_out, d_count_out);
+                                  max_det, frame_mark, d_rec_out, d_count_out, nullptr);
+}
+
+int dodt_pack_detections_classes(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores, const int32_t* d_types,
+                                 const float* d_orientations, const float* d_corr_offsets, const int32_t* d_sel,
+                                 const int32_t* d_count, int max_det, float frame_mark, float* d_rec_out,
+                                 int32_t* d_count_out) {
+    return launch_pack_detections(ctx, d_boxes_3d, d_scores, d_orientations, d_corr_offsets, 0, d_sel, d_count,
+                                  max_det, frame_mark, d_rec_out, d_count_out, d_types);
+}
+
+int dodt_pack_detections_compact_classes(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores,
+                                         const int32_t* d_types, const float* d_orientations,
+                                         const float* d_det_offsets, const int32_t* d_sel, const int32_t* d_count,
+                                         int max_det, float frame_mark, float* d_rec_out, int32_t* d_count_out) {
+    return launch_pack_detections(ctx, d_boxes_3d, d_scores, d_orientations, d_det_offsets, 1, d_sel, d_count,
+                                  max_det, frame_mark, d_rec_out, d_count_out, d_types);
 }
 
 int dodt_angle_vector_to_orientation(dodt_ctx* ctx, const float* d_angle_vectors, int n,

@@ -274,6 +274,43 @@ def pack_detections_compact(ctx, d_boxes_3d, d_scores, d_sel, d_count, max_det, 
         'dodt_pack_detections_compact')
 
 
+def class_scores(ctx, d_logits, n_cls, n, d_n, d_scores, d_types):
+    """Record score (largest non-background softmax value) and type (its index among the non-background columns, the
+    first maximum; int32) of n rows of (n, n_cls) logits (dodt_class_scores)."""
+    _lib.check(ctx.lib.dodt_class_scores(
+        ctx.handle, _p(d_logits), int(n_cls), int(n), _p(d_n), _p(d_scores), _p(d_types)), 'dodt_class_scores')
+
+
+def final_decode_classes(ctx, d_top_anchors, d_offsets, d_cls_logits, n_cls, d_angle_vectors, n, d_n, plane,
+                         bev_extents, d_boxes_3d, d_pred_anchors, d_bev_tf, d_nms_scores, d_det_scores, d_det_types,
+                         d_orientations):
+    """final_decode for (n, n_cls) logits: box_4c_decode + max_fg_logit + class_scores [+ angle_vector_to_orientation]
+    in one launch."""
+    _lib.check(ctx.lib.dodt_final_decode_classes(
+        ctx.handle, _p(d_top_anchors), _p(d_offsets), _p(d_cls_logits), int(n_cls), _p(d_angle_vectors), int(n),
+        _p(d_n), _arr(C.c_float, plane), _arr(C.c_float, bev_extents), _p(d_boxes_3d), _p(d_pred_anchors),
+        _p(d_bev_tf), _p(d_nms_scores), _p(d_det_scores), _p(d_det_types), _p(d_orientations)),
+        'dodt_final_decode_classes')
+
+
+def pack_detections_classes(ctx, d_boxes_3d, d_scores, d_types, d_sel, d_count, max_det, frame_mark,
+                            d_rec, d_count_out, d_corr_offsets=None, d_orientations=None):
+    """pack_detections with record column 8 = d_types[d_sel[row]] (d_types None: 0)."""
+    _lib.check(ctx.lib.dodt_pack_detections_classes(
+        ctx.handle, _p(d_boxes_3d), _p(d_scores), _p(d_types), _p(d_orientations), _p(d_corr_offsets),
+        _p(d_sel), _p(d_count), int(max_det), float(frame_mark), _p(d_rec), _p(d_count_out)),
+        'dodt_pack_detections_classes')
+
+
+def pack_detections_compact_classes(ctx, d_boxes_3d, d_scores, d_types, d_sel, d_count, max_det, frame_mark,
+                                    d_rec, d_count_out, d_det_offsets=None, d_orientations=None):
+    """pack_detections_compact with record column 8 = d_types[d_sel[row]] (d_types None: 0)."""
+    _lib.check(ctx.lib.dodt_pack_detections_compact_classes(
+        ctx.handle, _p(d_boxes_3d), _p(d_scores), _p(d_types), _p(d_orientations), _p(d_det_offsets),
+        _p(d_sel), _p(d_count), int(max_det), float(frame_mark), _p(d_rec), _p(d_count_out)),
+        'dodt_pack_detections_compact_classes')
+
+
 def fetch_i32_begin(ctx, d_src, n, slot):
     _lib.check(ctx.lib.dodt_fetch_i32_begin(ctx.handle, _p(d_src), int(n), int(slot)),
                'dodt_fetch_i32_begin')

@@ -130,9 +130,9 @@ class FramePairPipeline(object):
                  bev_input_skip=True, bev_frame_tables=True, t_branch_rows=None):
         """temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
         module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it.
-        tracker: None, or dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3, classes=('Car',),
-        max_sequence_dets=65536) -- the IoU tracker on the device after every step: the pairs of the steps, in order,
-        are one sequence until end_sequence() (see _tracker_step, tracks_so_far()); None enqueues and allocates nothing
+        tracker: None, or dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3,
+        classes=cfg['classes'], max_sequence_dets=65536) -- the IoU tracker on the device after every step: the pairs of
+        the steps, in order, are one sequence until end_sequence() (see _tracker_step, tracks_so_far()); None enqueues and allocates nothing
         for it.
         bev_input_skip: the fp32 BEV net skips the tiles that no BEV cell inside the camera's frustum reaches (their
         values depend on the weights alone, dodt_extractor_set_input_support); False: full tables.
@@ -163,6 +163,12 @@ class FramePairPipeline(object):
         self.n_points_max = int(n_points_max)
         self.pairs = int(pairs_per_step)               # samples per step
         self.fps = int(cfg.get('frames_per_sample', 2))
+        # stage-2 classification columns: the background and one per class.  Two (one class) take the two-way kernels;
+        # more take the *_classes entries, which also give every record its type (_decode_nms2, _records)
+        self.classes = tuple(cfg.get('classes', ('Car',)))
+        self.n_cls = len(self.classes) + 1
+        if not 2 <= self.n_cls <= 8:
+            raise ValueError('1 to 7 classes')
         if self.fps not in (1, 2):
             raise ValueError('frames_per_sample must be 1 or 2')
         self.temporal = self._temporal_args(temporal)
@@ -188,8 +194,10 @@ class FramePairPipeline(object):
         self.sched = resolve_schedule(None, head_params is not None, self.fps, len(self.sides))
         self.placement = self.alternate = None      # (of the T branch: the first run() fixes them with its form)
         # ---- constants of the configuration, resident on the device ----------------
-        boxes = gen.tile_anchors_3d(cfg['area_extents'], cfg['anchor_sizes'],
-                                    cfg['anchor_stride'], cfg['ground_plane'])
+        # (one grid per class, concatenated class-major: dt_rpn_model.py:894-909; the filter, the compaction and the RPN
+        #  take the rows as they come)
+        sizes, strides = _config.class_anchor_params(cfg)
+        boxes = gen.tile_anchors_3d_classes(cfg['area_extents'], sizes, strides, cfg['ground_plane'])
         self.anchors_all = gen.box_3d_to_anchor(boxes)            # (N,6) float64
         cells, self.nx, self.nz = gen.anchor_grid_cells(
             self.anchors_all, cfg['area_extents'], cfg['voxel_size'])
@@ -290,9 +298,11 @@ class FramePairPipeline(object):
                 nms2_boxes=ctx.empty((P, 4), f32), nms2_scores=ctx.empty((P,), f32),
                 det_idx=ctx.empty((MAX_DET,), i32), det_count=ctx.zeros((1,), i32),
                 det_scores=ctx.empty((P,), f32), orientations=ctx.empty((P,), f32))
+            if self.n_cls > 2:
+                b.update(det_types=ctx.zeros((P,), i32))
             if head_params is not None:
                 b.update(rpn_logits=ctx.empty((N, 2), f32), rpn_offsets=ctx.empty((N, 6), f32),
-                         cls_logits=ctx.empty((P, 2), f32), offsets_4c=ctx.empty((P, 10), f32))
+                         cls_logits=ctx.empty((P, self.n_cls), f32), offsets_4c=ctx.empty((P, 10), f32))
                 if self.box_4ca:
                     b.update(angle_vectors=ctx.empty((P, 2), f32))
                 if self.fps == 2 and f % 2 == 0:
@@ -355,7 +365,7 @@ class FramePairPipeline(object):
         tk = dict(score_threshold=float(t.pop('score_threshold', 0.1)),
                   high_threshold=float(t.pop('high_threshold', 0.5)),
                   iou_threshold=float(t.pop('iou_threshold', 0.005)), t_min=int(t.pop('t_min', 3)),
-                  classes=tuple(t.pop('classes', ('Car',))), max_sequence_dets=int(t.pop('max_sequence_dets', 65536)))
+                  classes=tuple(t.pop('classes', self.classes)), max_sequence_dets=int(t.pop('max_sequence_dets', 65536)))
         if t:
             raise ValueError('tracker: unknown keys %s' % sorted(t))
         if tk['max_sequence_dets'] < 1:
@@ -530,7 +540,7 @@ class FramePairPipeline(object):
         """Enqueue one step.  Lists of length 2 * pairs_per_step, frame order
         [pair0 f0, pair0 f1, pair1 f0, ...]: d_points[f] (n,4) float32 velodyne xyzi;
         d_images[f] (H,W,3) uint8; heads[f] dict of device arrays rpn_logits (N,2),
-        rpn_offsets (N,6), cls_logits (P,2), offsets_4c (P,10), angle_vectors (P,2) (box_4ca)
+        rpn_offsets (N,6), cls_logits (P,n_cls), offsets_4c (P,10), angle_vectors (P,2) (box_4ca)
         [, corr_offsets (P,3) on frame 0 of a pair]; None when the pipeline computes the heads
         itself (head_params).
         ego_motion: None, or one (trans (3,), matrix (3,3)) per pair of the step -- the
@@ -698,7 +708,7 @@ class FramePairPipeline(object):
             if self.tracker is None or self.last_sequence_tracks is None:
                 raise ValueError('kitti_tracking_rows: no sequence has ended')
             tracks = self.last_sequence_tracks
-        return convert_trajectory_to_kitti_format(tracks)
+        return convert_trajectory_to_kitti_format(tracks)           # (a track's type is its name in cfg['classes'])
 
     def frames(self):
         """Every frame's detections of the last finished step (as d_records: after finish(), or of the previous step
@@ -882,6 +892,8 @@ class FramePairPipeline(object):
         # box_4ca: all_orientations = atan2 of the angle vectors (dt_avod_model.py:547-548),
         # gathered with the boxes by NMS #2's indices (:631-634) inside the record kernel,
         # which applies the evaluator's heading correction (dt_evaluator.py:1166-1212)
+        if self.n_cls > 2:
+            return self._decode_nms2_classes(c, b, h, plane)
         if self.sched.fused_tail:
             ops.final_decode(c, b['top_anchors'], h['offsets_4c'], h['cls_logits'],
                              h['angle_vectors'] if self.box_4ca else None, self.P, b['top_count'], plane,
@@ -899,6 +911,27 @@ class FramePairPipeline(object):
             if self.box_4ca:
                 ops.angle_vector_to_orientation(c, h['angle_vectors'], self.P, b['top_count'], b['orientations'])
 
+    def _decode_nms2_classes(self, c, b, h, plane):
+        """_decode_nms2 for several classes: NMS #2 stays class-agnostic on the largest non-background logit
+        (dt_avod_model.py:606); score and type come from the n_cls-way softmax (dt_evaluator.py:1226-1255)."""
+        if self.sched.fused_tail:
+            ops.final_decode_classes(c, b['top_anchors'], h['offsets_4c'], h['cls_logits'], self.n_cls,
+                                     h['angle_vectors'] if self.box_4ca else None, self.P, b['top_count'], plane,
+                                     self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'],
+                                     b['nms2_scores'], b['det_scores'], b['det_types'],
+                                     b['orientations'] if self.box_4ca else None)
+            ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
+                    self.cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
+        else:
+            ops.box_4c_decode(c, b['top_anchors'], h['offsets_4c'], self.P, b['top_count'],
+                              plane, self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'])
+            ops.max_fg_logit(c, h['cls_logits'], self.n_cls, self.P, b['top_count'], b['nms2_scores'])
+            ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
+                    self.cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
+            ops.class_scores(c, h['cls_logits'], self.n_cls, self.P, b['top_count'], b['det_scores'], b['det_types'])
+            if self.box_4ca:
+                ops.angle_vector_to_orientation(c, h['angle_vectors'], self.P, b['top_count'], b['orientations'])
+
     def _records(self, t, f):
         """Frame f's detection records; in the 'detections' form, behind the T branch of its pair on frame 0."""
         c, b = self.sides[f % len(self.sides)], t.fr[f]
@@ -906,18 +939,21 @@ class FramePairPipeline(object):
         d_rec = self.d_records.offset(4 * MAX_DET * REC_COLS * f, (MAX_DET, REC_COLS))
         d_cnt = self.d_rec_counts.offset(4 * f, (1,), np.int32)
         d_orient = b['orientations'] if self.box_4ca else None
+        # (one class: the two-way entries, column 8 is 0; several: the same kernel with every box's type)
+        if self.n_cls > 2:
+            types, pack, pack_compact = (b['det_types'],), ops.pack_detections_classes, ops.pack_detections_compact_classes
+        else:
+            types, pack, pack_compact = (), ops.pack_detections, ops.pack_detections_compact
         if frame0 and self._t_detections():
             if self.placement == 'detections':
                 self._t_detection_rows(t, f)
             # (placement 'none', DODT_PIPE_NO_CORR: the offsets stay the zeros they were made as)
-            ops.pack_detections_compact(c, b['boxes_3d'], b['det_scores'], b['det_idx'], b['det_count'], MAX_DET,
-                                        float(f % self.fps), d_rec, d_cnt, d_det_offsets=b['det_corr_offsets'],
-                                        d_orientations=d_orient)
+            pack_compact(c, b['boxes_3d'], b['det_scores'], *types, b['det_idx'], b['det_count'], MAX_DET,
+                         float(f % self.fps), d_rec, d_cnt, d_det_offsets=b['det_corr_offsets'], d_orientations=d_orient)
         else:
-            ops.pack_detections(c, b['boxes_3d'], b['det_scores'], b['det_idx'], b['det_count'], MAX_DET,
-                                float(f % self.fps), d_rec, d_cnt,
-                                d_corr_offsets=t.heads[f].get('corr_offsets') if frame0 else None,
-                                d_orientations=d_orient)
+            pack(c, b['boxes_3d'], b['det_scores'], *types, b['det_idx'], b['det_count'], MAX_DET,
+                 float(f % self.fps), d_rec, d_cnt,
+                 d_corr_offsets=t.heads[f].get('corr_offsets') if frame0 else None, d_orientations=d_orient)
         self._mark(c, t.step, 'tail%d_end' % f)
 
     def _t_detection_rows(self, t, f):

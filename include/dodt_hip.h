@@ -548,6 +548,37 @@ int dodt_pack_detections_compact(dodt_ctx* ctx, const float* d_boxes_3d, const f
                                  const float* d_orientations, const float* d_det_offsets,
                                  const int32_t* d_sel, const int32_t* d_count, int max_det,
                                  float frame_mark, float* d_rec_out, int32_t* d_count_out);
+/* ---- several classes (n_cls = number of classes + 1, column 0 the background; 2 <= n_cls <= 8, anything else is
+ * DODT_ERR_INVALID).  A model for classes ['Pedestrian', 'Cyclist'] has n_cls == 3
+ * (avod/configs/pyramid_people_example.config).  The entries above are the n_cls == 2 forms and stay as they are. ----
+ * Record score and type of n rows of d_logits (n, n_cls) as the evaluator takes them from the softmax
+ * (avod/core/dt_evaluator.py:1226-1255): per row a float32 tf.nn.softmax -- the row's maximum subtracted, the
+ * exponentials summed in column order 0..n_cls-1, each divided by that sum --, d_scores_out (n) its largest
+ * non-background value and d_types_out (n) int32 that value's index among the non-background columns: np.argmax of
+ * softmax[:, 1:], so the FIRST maximum, taken over the float32 softmax values and not over the logits.  Rows at and
+ * past min(n, *d_n) are left untouched. */
+int dodt_class_scores(dodt_ctx* ctx, const float* d_logits, int n_cls, int n, const int32_t* d_n,
+                      float* d_scores_out, int32_t* d_types_out);
+/* dodt_final_decode for d_cls_logits (n, n_cls): one launch gives the box_4c decode (the same device functions), the
+ * NMS #2 score -- the largest non-background LOGIT, NMS #2 is class-agnostic (models/dt_avod_model.py:606) --, the
+ * score and type of dodt_class_scores (-> d_det_scores_out (n), d_det_types_out (n) int32) and the orientation.  At
+ * n_cls == 2 every float output is byte-equal to dodt_final_decode's and the types are 0. */
+int dodt_final_decode_classes(dodt_ctx* ctx, const float* d_top_anchors, const float* d_offsets,
+                              const float* d_cls_logits, int n_cls, const float* d_angle_vectors, int n,
+                              const int32_t* d_n, const float plane[4], const float bev_extents[4],
+                              float* d_boxes_3d_out, float* d_pred_anchors_out, float* d_bev_tf_out,
+                              float* d_nms_scores_out, float* d_det_scores_out, int32_t* d_det_types_out,
+                              float* d_orientations_out);
+/* dodt_pack_detections / dodt_pack_detections_compact with the record's class index, column 8: (float)d_types[d_sel[row]],
+ * d_types (n,) int32 as dodt_class_scores writes them.  d_types NULL: column 8 is 0, the result of the entries above. */
+int dodt_pack_detections_classes(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores, const int32_t* d_types,
+                                 const float* d_orientations, const float* d_corr_offsets, const int32_t* d_sel,
+                                 const int32_t* d_count, int max_det, float frame_mark, float* d_rec_out,
+                                 int32_t* d_count_out);
+int dodt_pack_detections_compact_classes(dodt_ctx* ctx, const float* d_boxes_3d, const float* d_scores,
+                                         const int32_t* d_types, const float* d_orientations,
+                                         const float* d_det_offsets, const int32_t* d_sel, const int32_t* d_count,
+                                         int max_det, float frame_mark, float* d_rec_out, int32_t* d_count_out);
 /* Stage-2 decode (models/dt_avod_model.py:464-469,575-603):
  *   anchors_to_box_3d(fix_lw) -> tf_box_3d_to_box_4c -> + offsets ->
  *   tf_box_4c_to_box_3d -> tf_box_3d_to_anchor -> project_to_bev (metres) ->
