@@ -29,6 +29,10 @@ environment's switches by resolve_schedule() when the pipeline is built.
 Everything stays on the device; the only host round trip per step is the kept-anchor count
 of each frame, fetched one step after it was produced (the host runs one step ahead of the
 GPU and otherwise waits in that read).
+Sequence mode (FramePairPipeline(sequence=True), push_frame()): the steps are the overlapping keyframe pairs of one
+sequence, a step takes ONE new frame, and what does not depend on a keyframe's role in a pair -- its image stack, image
+preprocessing, anchor filter and projections -- is computed once and read by both steps it belongs to (sequence_slots(),
+DESIGN section 8d).
 """
 import os
 from collections import namedtuple
@@ -66,6 +70,30 @@ CONV_DONE_MARK = 250    # 251, by parity: the main and the image stream behind a
                         # the main stream's also -> the image stream in front of the correlation maps (run)
 PROPOSALS_MARK = 252    # frame 0's side stream where its proposals stand -> frame 1's in front of the T branch's crops
 CORR_ROIS_MARK = 253    # frame 1's side stream behind its share of the T branch -> frame 0's in front of what reads it
+
+
+# Sequence mode (FramePairPipeline(sequence=True)): what a keyframe leaves for the two steps it
+# belongs to lives in rings of single-frame slots, keyframe j (frame f of step k: j = k + f) in slot j % depth
+IMG_RING = 3       # the image net's maps: forward j + 3 is the first writer enqueued behind the last tail that reads j
+PREP_RING = 4      # occ / keep / count / projections / anchors: one more than pair mode's three, see sequence_slots()
+POINT_RING = 3     # the pipeline's copy of a keyframe's points, read by its plain voxelisation one step later
+
+SeqSlots = namedtuple('SeqSlots', 'img prep points')
+
+
+def sequence_slots(step, img_ring=IMG_RING, prep_ring=PREP_RING, point_ring=POINT_RING):
+    """The ring slots of sequence step `step`, whose frames are keyframes step and step + 1: per ring a pair
+    (slot frame 0 reads, slot frame 1 reads).  The second of each is also what the step's NEW frame writes: its image
+    forward, its prep and the copy of its points.  Pure arithmetic; the depths are arguments only so that
+    tests/test_sequence_slots.py can show what a shallower ring collides with:
+    - image ring: the tail of step k is enqueued in the call for step k + 1, behind that call's image forward, which
+      writes keyframe k + 2 -- with two slots the slot of keyframe k, frame 0 of that tail;
+    - prep ring: a look-ahead prep is enqueued one call early, in front of the tail of that call.  The one in the call
+      for step k + 2 writes keyframe k + 4; the tail behind it, of step k + 1, reads keyframes k + 1 and k + 2, and with
+      four slots the last reader of the written one -- the tail of step k, frame 0 -- was enqueued a call before."""
+    return SeqSlots(img=(step % img_ring, (step + 1) % img_ring),
+                    prep=(step % prep_ring, (step + 1) % prep_ring),
+                    points=(step % point_ring, (step + 1) % point_ring))
 
 
 class Schedule(namedtuple('Schedule', 'fused_tail no_tail no_corr no_rpn t_branch two_streams corr_map_img')):
@@ -127,7 +155,7 @@ class FramePairPipeline(object):
                  image_wh=_config.KITTI_IMAGE_WH, n_points_max=120000, rpn_nms_size=1024,
                  pairs_per_step=1, side_streams=None, head_params=None, conv_dtype='f32',
                  head_dtype='f32', reuse_streams_of=None, temporal=None, tracker=None,
-                 bev_input_skip=True, bev_frame_tables=True, t_branch_rows=None):
+                 bev_input_skip=True, bev_frame_tables=True, t_branch_rows=None, sequence=False):
         """temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
         module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it.
         tracker: None, or dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3,
@@ -149,7 +177,14 @@ class FramePairPipeline(object):
         'proposals' otherwise.  The tile list of 'detections' is built in one workgroup's LDS, which holds a map of up to
         ops.CORR_TILE_LIST_MAX 16 x 16 tiles (the 700 x 800 map has 2200): on a larger map None means 'proposals' and
         'detections' is refused here.  t_branch_form() gives the form in use; the first run() fixes it.  Injected heads
-        keep their per-proposal offsets array whatever the argument."""
+        keep their per-proposal offsets array whatever the argument.
+        sequence: the steps are the overlapping keyframe pairs of one sequence (the reference's evaluation order,
+        kitti_tracking_dataset.py:266-272): push_frame() takes ONE new frame per step and pairs it with the previous one,
+        whose image maps, anchor filter and projections are kept from the step before.  Needs frame
+        pairs, one per step; run() / run_from_host() are refused on such a pipeline, push_frame() on any other."""
+        self.sequence = bool(sequence)
+        if self.sequence and (int(cfg.get('frames_per_sample', 2)) != 2 or int(pairs_per_step) != 1):
+            raise ValueError('sequence: needs frames_per_sample == 2 and pairs_per_step == 1')
         if t_branch_rows not in (None, 'proposals', 'detections'):
             raise ValueError("t_branch_rows must be None, 'proposals' or 'detections'")
         self.t_branch_rows = t_branch_rows
@@ -218,7 +253,8 @@ class FramePairPipeline(object):
                 ops.bev_support_mask(self.bp, self.bev_net.PAD_TOP, ctx.lib), frame_tables=bev_frame_tables)
         self.img_net = img_cls(ctx=self.img_ctx, shared_gpu=True, conv_dtype=conv_dtype)
         self.img_net.load_params(img_params)
-        self.img_net._ensure(self.nf, self.img_h, self.img_w, 4)
+        n_img = 1 if self.sequence else self.nf        # (sequence mode: one forward per NEW frame)
+        self.img_net._ensure(n_img, self.img_h, self.img_w, 4)
         # feature maps the crops read: (700,800,32) / (360,1200,32) for the pyramid,
         # (350,400,256) / (240,795,256) for the plain VGG
         self.bev_fh, self.bev_fw, self.feat_c = self.bev_net.output_shape()
@@ -231,11 +267,11 @@ class FramePairPipeline(object):
         self.bev_pad = self.bev_net.PAD_TOP
         self.in_bev = [ctx.zeros((self.nf, self.bev_pad + self.bev_h, self.bev_w, cfg['bev_depth']), np.float32)
                        for _ in range(2)]
-        self.in_img = [ctx.zeros((self.nf, self.img_net.PAD_TOP + self.img_h, self.img_w, 4), np.float32)
+        self.in_img = [ctx.zeros((n_img, self.img_net.PAD_TOP + self.img_h, self.img_w, 4), np.float32)
                        for _ in range(2)]
         # per-frame views of them, by parity
         self.bev_in = [self._views(a, (self.bev_h, self.bev_w, cfg['bev_depth']), self.bev_pad) for a in self.in_bev]
-        self.img_in = [self._views(a, (self.img_h, self.img_w, 4), self.img_net.PAD_TOP) for a in self.in_img]
+        self.img_in = [self._views(a, (self.img_h, self.img_w, 4), self.img_net.PAD_TOP, n_img) for a in self.in_img]
         self.d_bev_in = self.bev_in[0]             # (of the most recently finished step)
 
         # ---- dense heads (weights shared, scratch per side stream) ------------------------
@@ -266,21 +302,43 @@ class FramePairPipeline(object):
 
         # ---- work buffers ----------------------------------------------------------------
         FC = self.feat_c
-        self.feat = [dict(
-            bev_feat=ctx.empty((self.nf, self.bev_fh, self.bev_fw, FC), f32),
-            bev_bneck=ctx.empty((self.nf, self.bev_fh, self.bev_fw, 1), f32),
-            img_feat=ctx.empty((self.nf, self.img_fh, self.img_fw, FC), f32),
-            img_bneck=ctx.empty((self.nf, self.img_fh, self.img_fw, 1), f32)) for _ in range(2)]
+        # (sequence mode: the image net's maps of a keyframe serve two steps and live in img_ring instead)
+        self.feat = []
+        for _ in range(2):
+            d = dict(bev_feat=ctx.empty((self.nf, self.bev_fh, self.bev_fw, FC), f32),
+                     bev_bneck=ctx.empty((self.nf, self.bev_fh, self.bev_fw, 1), f32))
+            if not self.sequence:
+                d.update(img_feat=ctx.empty((self.nf, self.img_fh, self.img_fw, FC), f32),
+                         img_bneck=ctx.empty((self.nf, self.img_fh, self.img_fw, 1), f32))
+            self.feat.append(d)
+        if self.sequence:
+            # a ring of single-frame slots, keyframe j in slot j % IMG_RING (sequence_slots)
+            self.img_ring = [dict(img_feat=ctx.empty((1, self.img_fh, self.img_fw, FC), f32),
+                                  img_bneck=ctx.empty((1, self.img_fh, self.img_fw, 1), f32)) for _ in range(IMG_RING)]
         # per-frame views of them: feat_views[parity][frame][name]
         self.feat_views = [[{name: a.offset(a.nbytes // self.nf * f, a.shape[1:]) for name, a in d.items()}
                             for f in range(self.nf)] for d in self.feat]
         # what a step's prep leaves for its tail, THREE deep (step k: set k % 3): with look-ahead (run(...,
         # lookahead=)) the prep of step k + 1 is enqueued in front of the tail of step k - 1, which still reads
         # the set of its own step
-        self.prep3 = [[dict(occ=ctx.empty((self.nz, (self.nx + 31) // 32), np.uint32),
-                            keep=ctx.empty((N,), i32), count=ctx.zeros((1,), i32),
-                            bev_norm=ctx.empty((N, 4), f32), img_norm=ctx.empty((N, 4), f32),
-                            anchors=ctx.empty((N, 6), f32)) for _ in range(self.nf)] for _ in range(3)]
+        def prep_set():
+            return dict(occ=ctx.empty((self.nz, (self.nx + 31) // 32), np.uint32),
+                        keep=ctx.empty((N,), i32), count=ctx.zeros((1,), i32),
+                        bev_norm=ctx.empty((N, 4), f32), img_norm=ctx.empty((N, 4), f32),
+                        anchors=ctx.empty((N, 6), f32))
+        if self.sequence:
+            # ... one set per KEYFRAME, shared by the two steps it belongs to, PREP_RING deep (sequence_slots); the
+            # kept-anchor count of a set once its fetch has been read; and the pipeline's own copy of each keyframe's
+            # points for its plain voxelisation as frame 0, one step after the caller handed them over
+            self.prep_sets = [prep_set() for _ in range(PREP_RING)]
+            self.seq_counts = [None] * PREP_RING
+            self.pts_ring = [ctx.empty((self.n_points_max, 4), f32) for _ in range(POINT_RING)]
+            self.pts_n = [0] * POINT_RING
+            self.d_row_ids = ctx.array(np.arange(self.n_points_max, dtype=i32))     # (the copy is a gather of all rows)
+            self.seq_primed = False        # a keyframe stands ready to be frame 0 of the next step
+            self.seq_prime_parity = None   # parity of the image input a priming push's forward read (_seq_prep_new)
+        else:
+            self.prep3 = [[prep_set() for _ in range(self.nf)] for _ in range(3)]
         if 3 * self.nf > 32:
             raise ValueError('at most 10 frames per step (count fetch slots)')
         self.fr2 = [[], []]
@@ -310,7 +368,8 @@ class FramePairPipeline(object):
                     b.update(corr_rois=ctx.zeros((P, self.corr_head.in_ld), f32),
                              corr_offsets=ctx.empty((P, 3), f32))
             self.fr2[f // self.nf].append(b)
-        self.fr = [dict(b, **p) for b, p in zip(self.fr2[0], self.prep3[0])]   # buffers of the most recently finished step
+        # buffers of the most recently finished step
+        self.fr = [dict(b, **p) for b, p in zip(self.fr2[0], self.prep_sets if self.sequence else self.prep3[0])]
         self.prepped = -1              # step whose prep a look-ahead has already enqueued
         self.step_idx = 0
         self.pending = None            # step whose tail has not been enqueued yet
@@ -380,11 +439,11 @@ class FramePairPipeline(object):
                 c.mark(slot)
                 self.marks['%d:%s' % (step, name)] = (c, slot)
 
-    def _views(self, arr, shape, pad_top=0):
+    def _views(self, arr, shape, pad_top=0, n=None):
         """Per-frame views of a batch buffer whose frames are pad_top + shape[0] rows tall: the rows behind the pad."""
         row = int(np.prod(shape[1:])) * 4
         frame = (pad_top + shape[0]) * row
-        return [arr.offset(frame * f + pad_top * row, shape) for f in range(self.nf)]
+        return [arr.offset(frame * f + pad_top * row, shape) for f in range(self.nf if n is None else n)]
 
     def _tile_list_fits(self):
         return ops.correlation_tile_capacity((self.bev_fh, self.bev_fw)) <= ops.CORR_TILE_LIST_MAX
@@ -491,6 +550,8 @@ class FramePairPipeline(object):
         they travel under the kernels of the previous step; the host does not wait for them
         (the caller keeps the pinned buffers untouched until that step's prep has run, e.g.
         by alternating two sets)."""
+        if self.sequence:
+            raise ValueError('run_from_host: a sequence pipeline takes push_frame_from_host()')
         if self.prepped == self.step_idx:       # staged and prepared by the previous call's look-ahead
             d_pts = d_imgs = None
         else:
@@ -559,18 +620,13 @@ class FramePairPipeline(object):
         detections of the PREVIOUS step are complete on the main stream when this returns
         (self.d_records / self.fr / self.last_anchor_counts then describe that step);
         call finish() after the last step (run(); finish() is the unpipelined form)."""
+        if self.sequence:
+            raise ValueError('run: a sequence pipeline takes push_frame()')
         main, img = self.ctx, self.img_ctx
         if (heads is None) != (self.rpn_head is not None):
             raise ValueError('pass `heads` exactly when the pipeline has no head_params')
         self._resolve_t_branch()
-        if recover is not None:
-            if self.temporal is None:
-                raise ValueError('recover: the pipeline has no temporal module')
-            if len(recover) != self.pairs:
-                raise ValueError('recover: one entry per pair of the step')
-            n = self.temporal['n_frames']
-            # slot k % R was last read by M of step k - R, enqueued on `main` before this copy
-            self.ego2[self.step_idx % len(self.rec2)].upload(np.stack([ops.temporal_ego(e, n) for e in recover]))
+        self._upload_recover(recover)
         k = self.step_idx
         cur = k & 1
         feat = self.feat[cur]
@@ -604,6 +660,191 @@ class FramePairPipeline(object):
             la = tuple(lookahead) + (None,) * (4 - len(lookahead))
             self._prep(k + 1, la[0], la[1], la[2], la[3], ahead=True)
         # -- the previous step's tail runs under this step's convs --------------------------
+        self._pending_tail()
+        self.pending = dict(cur=cur, heads=heads, step=k, rslot=k % len(self.rec2), recover=recover is not None)
+        self.step_idx += 1
+        return cur
+
+    # ---- sequence mode ------------------------------------------------------------------------
+    def _seq_streams(self):
+        """(stream of a step's frame 0: the carried keyframe's plain voxelisation and its tail, stream of its frame 1:
+        every NEW keyframe's prep and its tail)."""
+        return self.sides[0], self.sides[1 % len(self.sides)]
+
+    def _seq_prep_new(self, k, d_points, n_points, d_image, ego_motion, host):
+        """The full prep of a NEW keyframe, as frame 1 of step k, on frame 1's side stream: _prep's chain for one frame,
+        into the ring slots sequence_slots(k) gives it -- its BEV maps (registered by ego_motion) are the only output
+        that is this step's alone; occ / keep / count / the projections / anchors and the preprocessed image also serve
+        step k + 1, where the frame is frame 0.  host: the frame is in pinned host memory; its points are copied
+        straight into the pipeline's point ring, which otherwise gets a device copy of the caller's array."""
+        c0, c = self._seq_streams()
+        cur, slots = k & 1, sequence_slots(k)
+        q, ps = slots.prep[1], slots.points[1]
+        if n_points > self.n_points_max:
+            raise ValueError('the frame has more than n_points_max points')
+        # The set and the point slot were last read on frame 0's stream: by the tail of step k + 1 - PREP_RING and by the
+        # plain voxelisation of step k + 1 - POINT_RING, both enqueued there a call or more ago (sequence_slots)
+        c.wait_for(c0)
+        if self.seq_prime_parity == cur:
+            # in_img[cur] was last read by a priming push's image forward, which no tail in front of this prep waited for
+            c.wait_mark(self.img_ctx, CONV_DONE_MARK + cur)
+            self.seq_prime_parity = None
+        b, d_pts = self.prep_sets[q], self.pts_ring[ps]
+        self._mark(c, k, 'prep1_start')
+        if host:
+            if not hasattr(self, 'seq_img_stage'):       # (read by this stream's own preprocessing only: one buffer)
+                self.seq_img_stage = self.ctx.empty((self.image_wh[1], self.image_wh[0], 3), np.uint8)
+            d_pts.upload_async(d_points, ctx=c, nbytes=16 * int(n_points))
+            d_image = self.seq_img_stage.upload_async(d_image, ctx=c)
+            d_points = d_pts
+        bp = self.bp if ego_motion is None else ops.with_ego_motion(self.bp, *ego_motion)
+        ops.bev_slices(c, d_points, n_points, bp, self.bev_in[cur][1], b['occ'])
+        ops.anchor_filter(c, b['occ'], self.nx, self.nz, self.d_cells, self.n_all, b['keep'], b['count'])
+        ops.fetch_i32_begin(c, b['count'], 1, PREP_RING * (1 % len(self.sides)) + q)
+        self.seq_counts[q] = None
+        ops.project_anchors_f64(c, self.d_anchor_table, b['keep'], self.n_all, b['count'], self.bev_extents_flat,
+                                self.p2, self.image_wh, b['bev_norm'], b['img_norm'], b['anchors'])
+        mean = (self.img_net._R_MEAN, self.img_net._G_MEAN, self.img_net._B_MEAN)
+        ops.img_preprocess(c, d_image, (self.image_wh[1], self.image_wh[0]), (self.img_h, self.img_w), 4, mean,
+                           self.img_in[cur][0])
+        if not host and n_points > 0:
+            ops.gather_rows(c, d_points, 4, self.d_row_ids, n_points, None, d_pts)
+        self.pts_n[ps] = int(n_points)
+        self._mark(c, k, 'prep1_end')
+        c.mark(PREP_DONE_MARK + k % 3)
+
+    def _seq_prep(self, k, d_points, n_points, d_image, ego_motion, ahead, host):
+        """The prep of sequence step k: on frame 0's stream what is left to do for the carried keyframe -- the plain,
+        un-registered voxelisation of the pipeline's copy of its points into in_bev[k & 1][0]; as frame 1 of step
+        k - 1 its maps were registered, everything else stands in its ring slots --, beside it on frame 1's stream the new
+        frame's full prep.  `ahead`: as for _prep."""
+        cur, slots = k & 1, sequence_slots(k)
+        c0, c1 = self._seq_streams()
+        if ahead and k >= 2:
+            for c in self.sides:
+                c.wait_mark(self.ctx, CONV_DONE_MARK + cur)
+                c.wait_mark(self.img_ctx, CONV_DONE_MARK + cur)
+        # the copy of the carried frame's points was made at the end of its prep as a new frame, on frame 1's stream
+        # (as frame 1 of step k - 1; that mark's next recording is the prep of step k + 2, not enqueued yet)
+        self._mark(c0, k, 'prep0_start')
+        if c0 is not c1:
+            c0.wait_mark(c1, PREP_DONE_MARK + (k - 1) % 3)
+        ps = slots.points[0]
+        # (no occupancy output: the frame's grid, from the same un-registered cloud, is in its prep set)
+        ops.bev_slices(c0, self.pts_ring[ps], self.pts_n[ps], self.bp, self.bev_in[cur][0], None)
+        self._mark(c0, k, 'prep0_end')
+        if c0 is not c1:
+            c0.mark(PREP_DONE_MARK + k % 3)
+        self._seq_prep_new(k, d_points, n_points, d_image, ego_motion, host)
+        self.prepped = k
+
+    def _seq_image_forward(self, k):
+        """The image net over the new frame of step k (batch 1) into its slot of the image ring, on the image stream.
+        The slot's last reader is the tail of step k - 2 (its frame 0), enqueued in the call before this one, whose end
+        the image stream has been told to wait for (TAIL_DONE_MARK, _pending_tail); a tail finish() enqueued stands in
+        front of this step's preps on both side streams, which the caller makes the stream wait for.  Marked as the
+        step's image stack (CONV_DONE_MARK)."""
+        img, cur = self.img_ctx, k & 1
+        slot = self.img_ring[sequence_slots(k).img[1]]
+        self._mark(img, k, 'img_start')
+        self.img_net.forward_device_padded(self.in_img[cur], slot['img_feat'], slot['img_bneck'])
+        self._mark(img, k, 'img_end')
+        img.mark(CONV_DONE_MARK + cur)
+
+    def push_frame(self, d_points, n_points, d_image, heads=None, ego_motion=None, lookahead=None, recover=None):
+        """Sequence mode's run(): ONE new keyframe -- d_points (n,4) float32 velodyne xyzi of which n_points rows are
+        valid, d_image (H,W,3) uint8.  The first push of a sequence (after construction or end_sequence()) only primes:
+        the frame is prepared, its image forward enqueued, and None returned.  Every later push enqueues the step of
+        the pair (previous frame, new frame), as run() enqueues a pair, and returns the parity of its record buffers;
+        the previous step's detections are then complete on the main stream, and finish() drains the last step.
+        heads: as for run(), the two frames' dicts in the pair's order (injected logits are inputs: nothing of them is
+        carried); ignored by a priming push.  ego_motion: None, or the (trans, matrix) that registers the new frame into
+        the previous one; lookahead: None, or (d_points, n_points, d_image[, ego_motion]) of the NEXT frame, which the
+        next push must then bring; recover: as for run().  The arrays may be reused once this call's work has run: the
+        pipeline voxelises the frame a second time one step later, from a copy of its own."""
+        return self._push(d_points, n_points, d_image, heads, ego_motion, lookahead, recover, host=False)
+
+    def push_frame_from_host(self, h_points, n_points, h_image, heads=None, ego_motion=None, lookahead=None,
+                             recover=None):
+        """push_frame() for a frame still in (page-locked) host memory, PinnedArrays as for run_from_host(): the points
+        are copied straight into the pipeline's point ring and the image into a staging buffer, on the new frame's side
+        stream in front of its prep; the host does not wait.  A look-ahead's frame is in pinned memory too."""
+        return self._push(h_points, n_points, h_image, heads, ego_motion, lookahead, recover, host=True)
+
+    def _push(self, d_points, n_points, d_image, heads, ego_motion, lookahead, recover, host):
+        if not self.sequence:
+            raise ValueError('push_frame: the pipeline was built without sequence=True')
+        main, img = self.ctx, self.img_ctx
+        c0, c1 = self._seq_streams()
+        la = None if lookahead is None else tuple(lookahead) + (None,) * (4 - len(lookahead))
+        k = self.step_idx
+        if not self.seq_primed:
+            # the frame is prepared as if it were frame 1 of step k - 1: every buffer it writes is that step's, whose
+            # readers a finished sequence has left behind (end_sequence() follows finish())
+            self._seq_prep_new(k - 1, d_points, n_points, d_image, None, host)
+            img.wait_mark(c1, PREP_DONE_MARK + (k - 1) % 3)
+            img.wait_for(c0)                            # (the last sequence's tails, frame 0's, read the image ring too)
+            self._seq_image_forward(k - 1)
+            self.seq_primed, self.seq_prime_parity = True, (k - 1) & 1
+            if la is not None:
+                self._seq_prep(k, la[0], la[1], la[2], la[3], ahead=True, host=host)
+            return None
+        if (heads is None) != (self.rpn_head is not None):
+            raise ValueError('pass `heads` exactly when the pipeline has no head_params')
+        self._resolve_t_branch()
+        self._upload_recover(recover)
+        cur = k & 1
+        feat = self.feat[cur]
+        if self.prepped != k:      # (else: enqueued by the previous call's look-ahead)
+            self._seq_prep(k, d_points, n_points, d_image, ego_motion, ahead=False, host=host)
+        for c in self.sides:
+            main.wait_mark(c, PREP_DONE_MARK + k % 3)
+            img.wait_mark(c, PREP_DONE_MARK + k % 3)
+        # -- the BEV stack over both frames, beside it the image stack over the new one --------
+        self._mark(main, k, 'bev_start')
+        self.bev_net.forward_device_padded(self.in_bev[cur], feat['bev_feat'], feat['bev_bneck'])
+        self._mark(main, k, 'bev_end')
+        main.mark(CONV_DONE_MARK + cur)
+        self._seq_image_forward(k)
+        if self.placement == 'img':                     # (as in run())
+            img.wait_mark(main, CONV_DONE_MARK + cur)
+            self._correlation_map(img, cur, 0, self.corr_maps[cur][0])
+            img.mark(CORR_MAP_MARK + cur)
+        if la is not None:
+            self._seq_prep(k + 1, la[0], la[1], la[2], la[3], ahead=True, host=host)
+        self._pending_tail()
+        self.pending = dict(cur=cur, heads=heads, step=k, rslot=k % len(self.rec2), recover=recover is not None)
+        self.step_idx += 1
+        return cur
+
+    def _seq_tail_inputs(self, st):
+        """What _tail composes a sequence step's frames from: per frame its kept-anchor count (the carried frame's is
+        known from the step before), its keyframe's prep set, and views of the step's BEV maps and the keyframe's slot
+        of the image ring."""
+        slots, (_, c1) = sequence_slots(st['step']), self._seq_streams()
+        for q in slots.prep:
+            if self.seq_counts[q] is None:
+                self.seq_counts[q] = ops.fetch_i32_end(c1, PREP_RING * (1 % len(self.sides)) + q, 1)[0]
+        feat = [dict(self.feat_views[st['cur']][f],
+                     **{name: a.offset(0, a.shape[1:]) for name, a in self.img_ring[slots.img[f]].items()})
+                for f in range(2)]
+        return [self.seq_counts[q] for q in slots.prep], [self.prep_sets[q] for q in slots.prep], feat
+
+    def _upload_recover(self, recover):
+        """The step's recovery parameters for M (run()'s `recover`), into the slot of the step about to be enqueued."""
+        if recover is None:
+            return
+        if self.temporal is None:
+            raise ValueError('recover: the pipeline has no temporal module')
+        if len(recover) != self.pairs:
+            raise ValueError('recover: one entry per pair of the step')
+        n = self.temporal['n_frames']
+        # slot k % R was last read by M of step k - R, enqueued on `main` before this copy
+        self.ego2[self.step_idx % len(self.rec2)].upload(np.stack([ops.temporal_ego(e, n) for e in recover]))
+
+    def _pending_tail(self):
+        """Enqueue the tail of the step before the one just enqueued, then M and the tracker over its records."""
+        main, img = self.ctx, self.img_ctx
         if self.pending is not None:
             self._wait_convs(self.pending)
             self._tail(self.pending)
@@ -620,9 +861,6 @@ class FramePairPipeline(object):
                 img.wait_mark(s, TAIL_DONE_MARK)
             self._temporal_step(self.pending)
             self._tracker_step(self.pending)
-        self.pending = dict(cur=cur, heads=heads, step=k, rslot=k % len(self.rec2), recover=recover is not None)
-        self.step_idx += 1
-        return cur
 
     def finish(self):
         """Enqueue the tail of the last step; afterwards self.fr / d_records hold it."""
@@ -689,11 +927,17 @@ class FramePairPipeline(object):
 
     def end_sequence(self, frame_ids=None):
         """End the sequence after finish(): finish the remaining active tracks, download, and start a new sequence.
-        Returns the host function's tracks_finished (kept as last_sequence_tracks for kitti_tracking_rows())."""
-        if self.tracker is None:
+        Returns the host function's tracks_finished (kept as last_sequence_tracks for kitti_tracking_rows()).
+        Sequence mode: the next push_frame() primes again, and a look-ahead that no push followed is dropped; without a
+        tracker that is all (returns None)."""
+        if self.tracker is None and not self.sequence:
             raise ValueError('end_sequence: the pipeline has no tracker')
         if self.pending is not None:
             raise ValueError('end_sequence: call finish() first (the last step is not tracked yet)')
+        if self.sequence:
+            self.seq_primed, self.prepped = False, -1
+            if self.tracker is None:
+                return None
         self.track_state.flush(ctx=self.img_ctx)
         tracks = self.tracks_so_far(frame_ids)
         self.track_state.reset(ctx=self.img_ctx)
@@ -731,17 +975,21 @@ class FramePairPipeline(object):
         """Stages after the extractors for every frame of step `st` (a11-a14): the per-step state, then the stages of
         its frames in the order of the T branch's placement (Schedule.t_placement)."""
         cur, k3, nf, ns = st['cur'], st['step'] % 3, self.nf, len(self.sides)
-        # kept-anchor counts of that step: fetched by its side streams, long complete
-        counts = [ops.fetch_i32_end(self.sides[f % ns], 3 * f + k3, 1)[0] for f in range(nf)]
+        if self.sequence:
+            counts, preps, feat = self._seq_tail_inputs(st)
+        else:
+            # kept-anchor counts of that step: fetched by its side streams, long complete
+            counts = [ops.fetch_i32_end(self.sides[f % ns], 3 * f + k3, 1)[0] for f in range(nf)]
+            preps, feat = self.prep3[k3], self.feat_views[cur]
         self.last_anchor_counts = counts
-        self.fr = [dict(b, **p) for b, p in zip(self.fr2[cur], self.prep3[k3])]   # the tail's buffers + what its prep left
+        self.fr = [dict(b, **p) for b, p in zip(self.fr2[cur], preps)]   # the tail's buffers + what its prep left
         self.d_records, self.d_rec_counts = self.rec2[st['rslot']], self.cnt2[st['rslot']]
         self.d_bev_in = self.bev_in[cur]
         if self.sched.no_tail:      # (tools/: the step without its tail)
             return
         if self.on_records_reuse is not None:
             self.on_records_reuse(st['rslot'], self.sides)
-        t = _TailState(step=st['step'], cur=cur, fr=self.fr, feat=self.feat_views[cur], counts=counts,
+        t = _TailState(step=st['step'], cur=cur, fr=self.fr, feat=feat, counts=counts,
                        heads=self.fr if st['heads'] is None else st['heads'], scratch=self.head_scratch)
         if self.placement == 'img':
             for f0 in range(0, nf, 2):
