@@ -56,6 +56,24 @@ class LayerInfo(C.Structure):
                 ('bytes', C.c_double), ('ms', C.c_float), ('reserved_', C.c_int32)]
 
 
+VARIANT_DECONV, VARIANT_SMALL_CIN, VARIANT_TAIL_ONLY, VARIANT_BF16, VARIANT_SPLIT, VARIANT_WINO = 1, 2, 4, 8, 0x10, 0x20
+VARIANT_WINO43, VARIANT_DMA, VARIANT_DECONV_DMA, VARIANT_FIRST2, VARIANT_STREAM = 0x40, 0x80, 0x100, 0x200, 0x400
+VARIANT_XCD_QUEUE, VARIANT_CAN_POOL = 0x800, 0x1000
+
+
+class ConvVariant(C.Structure):
+    _fields_ = [('tw', C.c_int32), ('th', C.c_int32), ('bn', C.c_int32), ('ck', C.c_int32), ('flags', C.c_int32),
+                ('blocks_per_cu', C.c_int32), ('lds_bytes', C.c_int32), ('reserved_', C.c_int32),
+                ('kernel', C.c_char * 48)]
+
+
+class ConvLayerPlan(C.Structure):
+    _fields_ = [('name', C.c_char * 32), ('h', C.c_int32), ('w', C.c_int32), ('cin', C.c_int32), ('cout', C.c_int32),
+                ('variant', C.c_int32 * 2), ('items', C.c_int32 * 2),
+                ('grid', C.c_int32 * 2), ('pool_fused', C.c_int32), ('bneck_fused', C.c_int32),
+                ('folded', C.c_int32), ('reserved_', C.c_int32)]
+
+
 _vp = C.c_void_p
 _i = C.c_int
 _f = C.c_float
@@ -75,6 +93,7 @@ SIGNATURES = {
     'dodt_ctx_create_high_priority': (_i, [_i, C.POINTER(_vp)]),
     'dodt_ctx_create_on_stream': (_i, [_i, _vp, C.POINTER(_vp)]),
     'dodt_ctx_destroy': (_i, [_vp]),
+    'dodt_ctx_set_plan_cus': (_i, [_vp, _i]),
     'dodt_ctx_sync': (_i, [_vp]),
     'dodt_ctx_wait_for': (_i, [_vp, _vp]),
     'dodt_malloc': (_i, [_vp, C.c_size_t, C.POINTER(_vp)]),
@@ -127,6 +146,10 @@ SIGNATURES = {
     'dodt_extractor_mfma_flops': (_d, [_vp]),
     'dodt_extractor_bytes': (_d, [_vp]),
     'dodt_extractor_layer_count': (_i, [_vp]),
+    'dodt_conv_variant_count': (_i, []),
+    'dodt_conv_variant_info': (_i, [_i, C.POINTER(ConvVariant)]),
+    'dodt_conv_plan_host': (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(ConvLayerPlan), _i, C.POINTER(_i)]),
+    'dodt_extractor_layer_plan': (_i, [_vp, C.POINTER(ConvLayerPlan), _i, C.POINTER(_i)]),
     'dodt_extractor_forward_timed': (_i, [_vp, _pf, _pf, _pf, C.POINTER(LayerInfo), _i]),
     'dodt_crop_and_resize': (_i, [_vp, _pf, _i, _i, _i, _pf, _i, _pi32, _i, _i,
                                   _pf]),

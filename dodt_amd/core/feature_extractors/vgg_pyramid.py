@@ -11,6 +11,37 @@ import numpy as np
 from dodt_amd import _lib, device
 
 
+def conv_variants():
+    """The kernel-variant table (dodt_conv_variant_info): a list of dicts tw, th, bn, ck, flags (_lib.VARIANT_*),
+    blocks_per_cu, lds_bytes, kernel.  Host only."""
+    lib = _lib.load()
+    out = []
+    for i in range(lib.dodt_conv_variant_count()):
+        v = _lib.ConvVariant()
+        _lib.check(lib.dodt_conv_variant_info(i, C.byref(v)), 'dodt_conv_variant_info')
+        out.append(dict(tw=v.tw, th=v.th, bn=v.bn, ck=v.ck, flags=v.flags, blocks_per_cu=v.blocks_per_cu,
+                        lds_bytes=v.lds_bytes, kernel=v.kernel.decode()))
+    return out
+
+
+def _plan_records(recs):
+    return [dict(name=r.name.decode(), h=r.h, w=r.w, cin=r.cin, cout=r.cout, variant=list(r.variant),
+                 items=list(r.items), grid=list(r.grid), pool_fused=bool(r.pool_fused),
+                 bneck_fused=bool(r.bneck_fused), folded=bool(r.folded)) for r in recs]
+
+
+def conv_plan_host(kind, in_h, in_w, in_c, pad_top, batch, num_cus):
+    """What dodt_extractor_create would plan for these arguments on a device of num_cus CUs, layer by layer in launch
+    order (dodt_conv_plan_host; kind with its _lib.EXTRACTOR_* flag bits).  Host only: needs no GPU."""
+    lib = _lib.load()
+    n = C.c_int()
+    args = (int(kind), int(in_h), int(in_w), int(in_c), int(pad_top), int(batch), int(num_cus))
+    _lib.check(lib.dodt_conv_plan_host(*(args + (None, 0, C.byref(n)))), 'dodt_conv_plan_host')
+    recs = (_lib.ConvLayerPlan * n.value)()
+    _lib.check(lib.dodt_conv_plan_host(*(args + (recs, n.value, None))), 'dodt_conv_plan_host')
+    return _plan_records(recs)
+
+
 class _VggPyr(object):
     PAD_TOP = 0
     KIND = _lib.EXTRACTOR_VGG_PYR
@@ -44,11 +75,7 @@ class _VggPyr(object):
         self._ctx = self._ctx or device.default_context()
         hnd = C.c_void_p()
         _lib.check(self._ctx.lib.dodt_extractor_create(
-            self._ctx.handle,
-            self.KIND | (_lib.EXTRACTOR_SHARED_GPU if self._shared_gpu else 0)
-            | (_lib.EXTRACTOR_BF16 if self._bf16 else 0)
-            | (_lib.EXTRACTOR_SPLIT if self._split else 0),
-            h, w, c, self.PAD_TOP,
+            self._ctx.handle, self.kind_flags(), h, w, c, self.PAD_TOP,
             batch, C.byref(hnd)), 'dodt_extractor_create')
         self._handle = hnd
         self._shape = shape
@@ -166,6 +193,19 @@ class _VggPyr(object):
         return [dict(name=i.name.decode(), kernel=i.kernel.decode(), launches=i.launches,
                      items=i.items, flops_direct=i.flops_direct, flops_executed=i.flops_executed,
                      bytes=i.bytes, ms=i.ms) for i in info]
+
+    def kind_flags(self):
+        """The `kind` argument this extractor is created with (conv_plan_host takes the same)."""
+        return (self.KIND | (_lib.EXTRACTOR_SHARED_GPU if self._shared_gpu else 0)
+                | (_lib.EXTRACTOR_BF16 if self._bf16 else 0) | (_lib.EXTRACTOR_SPLIT if self._split else 0))
+
+    def plan(self):
+        """The built extractor's plan, the records of conv_plan_host (dodt_extractor_layer_plan)."""
+        lib = self._ctx.lib
+        n = lib.dodt_extractor_layer_count(self._handle)
+        recs = (_lib.ConvLayerPlan * n)()
+        _lib.check(lib.dodt_extractor_layer_plan(self._handle, recs, n, None), 'dodt_extractor_layer_plan')
+        return _plan_records(recs)
 
     def input_view(self):
         """DeviceArray aliasing the extractor's own input buffer (zero copy)."""

@@ -77,6 +77,7 @@ struct dodt_ctx {
     dodt::Scratch tracking_ws;   // tracker: the IoU tables of a batch of pairs
     dodt::Scratch tracking_enc;  // tracker: a batch's encoded label rows
     int num_cus = 256;
+    int plan_cus = 0;        // > 0: the CU count extractors created from now on plan with (dodt_ctx_set_plan_cus)
     int32_t* pinned = nullptr;       // kFetchSlots x 16 int32, hipHostMalloc
     hipEvent_t fetch_ev[kFetchSlots] = {};
     hipEvent_t mark_ev[kMarkSlots] = {};     // timing marks for tools/ (created on first use)

@@ -400,6 +400,16 @@ void report_launch(const dodt_extractor* ex, const Layer& l, const KernelVariant
     }
 }
 
+// persistent workgroups: as many as stay resident on num_cus CUs, each walks items with that stride
+int launch_grid(const KernelVariant& v, int n_items, int num_cus) {
+    static const int bpc_env = getenv("DODT_CONV_BPC") ? atoi(getenv("DODT_CONV_BPC")) : 0;
+    // (the first-layer kernel is persistent since round 4: three workgroups per CU by its registers)
+    static const int small_bpc = getenv("DODT_CONV_SMALL_BPC") ? atoi(getenv("DODT_CONV_SMALL_BPC")) : 3;
+    const int vb = v.small_cin ? small_bpc : v.blocks_per_cu;
+    const int bpc = (bpc_env > 0 && bpc_env < vb) ? bpc_env : vb;
+    return std::min(n_items, num_cus * bpc);
+}
+
 // which: 0 the layer's main launch, 1 its tail
 int run_launch(const dodt_extractor* ex, const Pass& p, const Layer& l, int which,
                float* override_out, int out_y0, int out_h, float* bneck_out, int pool_dst, const Layer* folded = nullptr) {
@@ -463,17 +473,7 @@ int run_launch(const dodt_extractor* ex, const Pass& p, const Layer& l, int whic
     a.first_w = folded ? folded->d_first_w : nullptr;
     a.first_scale = folded ? folded->d_scale : nullptr;
     a.first_shift = folded ? folded->d_shift : nullptr;
-    // persistent workgroups: as many as stay resident, each walks items with that stride
-    int grid_x = a.n_items;
-    {
-        static const int bpc_env = getenv("DODT_CONV_BPC") ? atoi(getenv("DODT_CONV_BPC")) : 0;
-        // (the first-layer kernel is persistent since round 4: three workgroups per CU by its registers)
-        static const int small_bpc = getenv("DODT_CONV_SMALL_BPC") ? atoi(getenv("DODT_CONV_SMALL_BPC")) : 3;
-        const int vb = v.small_cin ? small_bpc : v.blocks_per_cu;
-        const int bpc = (bpc_env > 0 && bpc_env < vb) ? bpc_env : vb;
-        const int resident = ex->ctx->num_cus * bpc;
-        if (grid_x > resident) grid_x = resident;
-    }
+    const int grid_x = launch_grid(v, a.n_items, ex->num_cus);
     dim3 grid(grid_x, 1);
     v.launch(a, grid, ex->ctx->stream);
     DODT_LAUNCH_CHECK();
@@ -703,11 +703,7 @@ int dodt::run_layers(const dodt_extractor* ex, const Pass& p, float* d_feat_out,
     return DODT_OK;
 }
 
-extern "C" {
-
-int dodt_extractor_create(dodt_ctx* ctx, int kind, int in_h, int in_w, int in_c, int pad_top,
-                          int batch, dodt_extractor** out) {
-    DODT_REQUIRE(ctx && out, "dodt_extractor_create: NULL argument");
+int dodt::plan_convs(int kind, int in_h, int in_w, int in_c, int pad_top, int batch, int num_cus, ConvPlan& plan) {
     const bool split = (kind & DODT_EXTRACTOR_SPLIT) != 0;
     const bool bf16 = (kind & DODT_EXTRACTOR_BF16) != 0 || split;
     // (the bf16 kernels have no quarter-size instantiations: single launches)
@@ -728,15 +724,174 @@ int dodt_extractor_create(dodt_ctx* ctx, int kind, int in_h, int in_w, int in_c,
                      "dodt_extractor_create: padded input %dx%d must be divisible by 8 "
                      "(three 2x2 pools, three stride-2 upconvs)", H, W);
     }
+    DODT_REQUIRE(num_cus >= 1, "dodt_extractor_create: bad CU count %d", num_cus);
+    plan = ConvPlan();
+    plan.kind = kind;
+    plan.bf16 = bf16;
+    plan.parts = split ? 2 : 1;
+    plan.H = H; plan.W = W;
+    // VALID 2x2 pools floor odd sizes (plain VGG: 175 -> 87, 795 -> 397 -> 198)
+    const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2, H8 = H4 / 2, W8 = W4 / 2;
+
+    // (LayerId names the layers by their place in this order)
+    bool in_order = true;
+    auto add = [&](LayerId id, const char* name, bool deconv, int h, int w, int cin, int cout, int src,
+                   int src_coff, int dst, int dst_coff, int pool = -1) {
+        in_order = in_order && id == (int)plan.layers.size() && deconv == ft::transposed(id);
+        Layer l;
+        l.pool = pool;
+        l.name = name; l.deconv = deconv; l.H = h; l.W = w; l.Cin = cin; l.Cout = cout;
+        l.src = src; l.src_coff = src_coff; l.dst = dst; l.dst_coff = dst_coff;
+        l.variant = pick_variant(deconv, h, w, cin, cout, bf16, plan.parts, batch, num_cus);
+        l.real_cin = cin;
+        plan.layers.push_back(l);
+    };
+    add(CONV1_1, "conv1_1", false, H, W, in_c, 32, X0, 0, C1A, 0);
+    add(CONV1_2, "conv1_2", false, H, W, 32, 32, C1A, 0, CAT1, 0, P1);
+    add(CONV2_1, "conv2_1", false, H2, W2, 32, 64, P1, 0, C2A, 0);
+    add(CONV2_2, "conv2_2", false, H2, W2, 64, 64, C2A, 0, CAT2, 0, P2);
+    add(CONV3_1, "conv3_1", false, H4, W4, 64, 128, P2, 0, C3A, 0);
+    add(CONV3_2, "conv3_2", false, H4, W4, 128, 128, C3A, 0, C3B, 0);
+    add(CONV3_3, "conv3_3", false, H4, W4, 128, 128, C3B, 0, CAT3, 0, P3);
+    add(CONV4_1, "conv4_1", false, H8, W8, 128, 256, P3, 0, C4A, 0);
+    add(CONV4_2, "conv4_2", false, H8, W8, 256, 256, C4A, 0, C4B, 0);
+    add(CONV4_3, "conv4_3", false, H8, W8, 256, 256, C4B, 0, C4C, 0);
+    if (!plain) {
+        add(UPCONV3, "upconv3", true, H8, W8, 256, 128, C4C, 0, CAT3, 128);
+        add(FUSION3, "pyramid_fusion3", false, H4, W4, 256, 64, CAT3, 0, F3, 0);
+        add(UPCONV2, "upconv2", true, H4, W4, 64, 64, F3, 0, CAT2, 64);
+        add(FUSION2, "pyramid_fusion2", false, H2, W2, 128, 32, CAT2, 0, F2, 0);
+        add(UPCONV1, "upconv1", true, H2, W2, 32, 32, F2, 0, CAT1, 32);
+        add(FUSION1, "pyramid_fusion1", false, H, W, 64, 32, CAT1, 0, F1, 0);
+    }
+    if (!in_order) {
+        dodt::set_error("dodt_extractor_create: the layers are not in LayerId's order");
+        return DODT_ERR_INVALID;
+    }
+    for (const Layer& l : plan.layers) {
+        if (l.variant < 0) {
+            dodt::set_error("dodt_extractor_create: no kernel variant for layer %s (%dx%d %d->%d)",
+                            l.name.c_str(), l.H, l.W, l.Cin, l.Cout);
+            return DODT_ERR_UNSUPPORTED;
+        }
+    }
+    for (Layer& l : plan.layers) {
+        plan_layer(l, batch, num_cus, !shared_gpu, l.main.h_items, l.tail.h_items);
+        l.main.n_items = (int)l.main.h_items.size();
+        l.tail.n_items = (int)l.tail.h_items.size();
+    }
+    {
+        // bf16 conv path: conv1_1 folded into conv1_2's launch when conv1_2 runs on the streaming kernel (same tiles, same
+        // weight blocking) and the input rows are whole 16-byte slots (DODT_CONV_BF16_FIRST2=0: two launches)
+        static const bool first2 = !(getenv("DODT_CONV_BF16_FIRST2") && atoi(getenv("DODT_CONV_BF16_FIRST2")) == 0);
+        const Layer& c11 = plan.layers[CONV1_1];
+        const Layer& c12 = plan.layers[CONV1_2];
+        const auto& vs = variants();
+        // (the input buffer holds exactly conv1_1's in_c channels)
+        if (first2 && bf16 && plan.parts == 1 && vs[c12.variant].stream_nch == 2 && c12.tail.n_items == 0 &&
+            c11.Cout == 32 && c11.src_coff == 0 && (W * c11.Cin * 4) % 16 == 0 &&
+            variant_can_pool(vs[c12.variant]))
+            for (size_t i = 0; i < vs.size() && plan.first2_variant < 0; ++i)
+                if (vs[i].first2 == c11.Cin && vs[i].TH == vs[c12.variant].TH && vs[i].TW == vs[c12.variant].TW &&
+                    vs[i].lds_bytes <= (getenv("DODT_CONV_BF16_STREAM_LDS") ? atoi(getenv("DODT_CONV_BF16_STREAM_LDS")) * 1024 : 1 << 30))
+                    plan.first2_variant = (int)i;
+    }
+    return DODT_OK;
+}
+
+namespace {
+
+// one layer of a plan as the C ABI reports it (dodt_conv_plan_host, dodt_extractor_layer_plan)
+void report_layer(const std::vector<Layer>& layers, int first2_variant, int num_cus, size_t i, dodt_conv_layer_plan* o) {
+    const Layer& l = layers[i];
+    const bool folding = first2_variant >= 0;
+    memset(o, 0, sizeof(*o));
+    snprintf(o->name, sizeof(o->name), "%s", l.name.c_str());
+    o->h = l.H; o->w = l.W; o->cin = l.Cin; o->cout = l.Cout;
+    o->variant[0] = l.main.variant;
+    o->variant[1] = l.tail.n_items > 0 ? l.tail.variant : -1;
+    o->items[0] = l.main.n_items;
+    o->items[1] = l.tail.n_items;
+    if (folding && i == CONV1_1) {          // no launch of its own
+        o->variant[0] = -1;
+        o->items[0] = 0;
+        o->folded = 1;
+    }
+    if (folding && i == CONV1_2) o->variant[0] = first2_variant;   // conv1_2's items, the folding kernel
+    for (int j = 0; j < 2; ++j)
+        o->grid[j] = o->variant[j] >= 0 ? launch_grid(variants()[o->variant[j]], o->items[j], num_cus) : 0;
+    o->pool_fused = l.pool >= 0 && ((folding && i == CONV1_2) || fused_pool_buffer(l) >= 0);
+    o->bneck_fused = i == FUSION1 && bneck_fused(l);
+}
+
+int report_plan(const std::vector<Layer>& layers, int first2_variant, int num_cus, dodt_conv_layer_plan* out, int n_out,
+                int* n_layers) {
+    if (n_layers) *n_layers = (int)layers.size();
+    if (!out) return DODT_OK;
+    DODT_REQUIRE(n_out >= (int)layers.size(), "conv plan: room for %d layers, the net has %d", n_out, (int)layers.size());
+    for (size_t i = 0; i < layers.size(); ++i) report_layer(layers, first2_variant, num_cus, i, out + i);
+    return DODT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dodt_conv_plan_host(int kind, int in_h, int in_w, int in_c, int pad_top, int batch, int num_cus,
+                        dodt_conv_layer_plan* out, int n_out, int* n_layers) {
+    ConvPlan plan;
+    const int rc = plan_convs(kind, in_h, in_w, in_c, pad_top, batch, num_cus, plan);
+    return rc ? rc : report_plan(plan.layers, plan.first2_variant, num_cus, out, n_out, n_layers);
+}
+
+int dodt_extractor_layer_plan(const dodt_extractor* ex, dodt_conv_layer_plan* out, int n_out, int* n_layers) {
+    DODT_REQUIRE(ex, "dodt_extractor_layer_plan: extractor is NULL");
+    return report_plan(ex->layers, ex->first2_variant, ex->num_cus, out, n_out, n_layers);
+}
+
+int dodt_conv_variant_count(void) { return (int)variants().size(); }
+
+int dodt_conv_variant_info(int i, dodt_conv_variant* out) {
+    DODT_REQUIRE(out && i >= 0 && i < (int)variants().size(), "dodt_conv_variant_info: bad argument");
+    const KernelVariant& v = variants()[i];
+    memset(out, 0, sizeof(*out));
+    out->tw = v.TW; out->th = v.TH; out->bn = v.BN; out->ck = v.CK;
+    out->blocks_per_cu = v.blocks_per_cu;
+    out->flags = (v.deconv ? DODT_VARIANT_DECONV : 0) | (v.small_cin ? DODT_VARIANT_SMALL_CIN : 0) |
+                 (v.tail_only ? DODT_VARIANT_TAIL_ONLY : 0) | (v.bf16 ? DODT_VARIANT_BF16 : 0) |
+                 (v.parts == 2 ? DODT_VARIANT_SPLIT : 0) | (v.wino ? DODT_VARIANT_WINO : 0) |
+                 (v.wino && v.wino_m == 4 ? DODT_VARIANT_WINO43 : 0) | (v.dma ? DODT_VARIANT_DMA : 0) |
+                 (v.deconv_dma ? DODT_VARIANT_DECONV_DMA : 0) | (v.first2 ? DODT_VARIANT_FIRST2 : 0) |
+                 (v.stream_nch ? DODT_VARIANT_STREAM : 0) | (variant_xcd_queue(v) ? DODT_VARIANT_XCD_QUEUE : 0) |
+                 (variant_can_pool(v) ? DODT_VARIANT_CAN_POOL : 0);
+    out->lds_bytes = v.lds_bytes;
+    snprintf(out->kernel, sizeof(out->kernel), "%s", kernel_name(v));
+    return DODT_OK;
+}
+
+int dodt_extractor_create(dodt_ctx* ctx, int kind, int in_h, int in_w, int in_c, int pad_top,
+                          int batch, dodt_extractor** out) {
+    DODT_REQUIRE(ctx && out, "dodt_extractor_create: NULL argument");
+    const int num_cus = ctx->plan_cus > 0 ? ctx->plan_cus : ctx->num_cus;
+    ConvPlan plan;
+    {
+        const int rc = plan_convs(kind, in_h, in_w, in_c, pad_top, batch, num_cus, plan);
+        if (rc) return rc;
+    }
+    kind = plan.kind;
+    const bool plain = kind == DODT_EXTRACTOR_VGG;
+    const bool bf16 = plan.bf16;
+    const int H = plan.H, W = plan.W;
     for (const KernelVariant& v : variants()) DODT_HIP_CHECK(v.prepare());
 
     dodt_extractor* ex = new dodt_extractor();
+    ex->num_cus = num_cus;
     ex->ctx = ctx;
     ex->kind = kind;
     ex->in_h = in_h; ex->in_w = in_w; ex->in_c = in_c; ex->pad_top = pad_top; ex->batch = batch;
     ex->H = H; ex->W = W;
     ex->bf16 = bf16;
-    ex->parts = split ? 2 : 1;
+    ex->parts = plan.parts;
     auto setb = [&](int id, int h, int w, int c) { ex->buf[id].H = h; ex->buf[id].W = w; ex->buf[id].C = c; };
     // VALID 2x2 pools floor odd sizes (plain VGG: 175 -> 87, 795 -> 397 -> 198)
     const int H2 = H / 2, W2 = W / 2, H4 = H2 / 2, W4 = W2 / 2, H8 = H4 / 2, W8 = W4 / 2;
@@ -779,79 +934,18 @@ int dodt_extractor_create(dodt_ctx* ctx, int kind, int in_h, int in_w, int in_c,
     DODT_HIP_CHECK(hipMemsetAsync(ex->buf[X0].ptr, 0,
                                   ex->buf[X0].frame_floats() * batch * sizeof(float), ctx->stream));
 
-    // (LayerId names the layers by their place in this order)
-    bool in_order = true;
-    auto add = [&](LayerId id, const char* name, bool deconv, int h, int w, int cin, int cout, int src,
-                   int src_coff, int dst, int dst_coff, int pool = -1) {
-        in_order = in_order && id == (int)ex->layers.size() && deconv == ft::transposed(id);
-        Layer l;
-        l.pool = pool;
-        l.name = name; l.deconv = deconv; l.H = h; l.W = w; l.Cin = cin; l.Cout = cout;
-        l.src = src; l.src_coff = src_coff; l.dst = dst; l.dst_coff = dst_coff;
-        l.variant = pick_variant(deconv, h, w, cin, cout, bf16, ex->parts, batch, ctx->num_cus);
-        l.real_cin = cin;
-        ex->layers.push_back(l);
-    };
-    add(CONV1_1, "conv1_1", false, H, W, in_c, 32, X0, 0, C1A, 0);
-    add(CONV1_2, "conv1_2", false, H, W, 32, 32, C1A, 0, CAT1, 0, P1);
-    add(CONV2_1, "conv2_1", false, H2, W2, 32, 64, P1, 0, C2A, 0);
-    add(CONV2_2, "conv2_2", false, H2, W2, 64, 64, C2A, 0, CAT2, 0, P2);
-    add(CONV3_1, "conv3_1", false, H4, W4, 64, 128, P2, 0, C3A, 0);
-    add(CONV3_2, "conv3_2", false, H4, W4, 128, 128, C3A, 0, C3B, 0);
-    add(CONV3_3, "conv3_3", false, H4, W4, 128, 128, C3B, 0, CAT3, 0, P3);
-    add(CONV4_1, "conv4_1", false, H8, W8, 128, 256, P3, 0, C4A, 0);
-    add(CONV4_2, "conv4_2", false, H8, W8, 256, 256, C4A, 0, C4B, 0);
-    add(CONV4_3, "conv4_3", false, H8, W8, 256, 256, C4B, 0, C4C, 0);
-    if (!plain) {
-        add(UPCONV3, "upconv3", true, H8, W8, 256, 128, C4C, 0, CAT3, 128);
-        add(FUSION3, "pyramid_fusion3", false, H4, W4, 256, 64, CAT3, 0, F3, 0);
-        add(UPCONV2, "upconv2", true, H4, W4, 64, 64, F3, 0, CAT2, 64);
-        add(FUSION2, "pyramid_fusion2", false, H2, W2, 128, 32, CAT2, 0, F2, 0);
-        add(UPCONV1, "upconv1", true, H2, W2, 32, 32, F2, 0, CAT1, 32);
-        add(FUSION1, "pyramid_fusion1", false, H, W, 64, 32, CAT1, 0, F1, 0);
-    }
-    if (!in_order) {
-        dodt::set_error("dodt_extractor_create: the layers are not in LayerId's order");
-        dodt_extractor_destroy(ex);
-        return DODT_ERR_INVALID;
-    }
-    for (const Layer& l : ex->layers) {
-        if (l.variant < 0) {
-            dodt::set_error("dodt_extractor_create: no kernel variant for layer %s (%dx%d %d->%d)",
-                            l.name.c_str(), l.H, l.W, l.Cin, l.Cout);
-            dodt_extractor_destroy(ex);
-            return DODT_ERR_UNSUPPORTED;
-        }
-    }
+    // the plan's layers; their item tables go to the device
+    ex->layers = std::move(plan.layers);
+    ex->first2_variant = plan.first2_variant;
     for (Layer& l : ex->layers) {
-        std::vector<int4> mi, ti;
-        plan_layer(l, batch, ctx->num_cus, !shared_gpu, mi, ti);
-        for (auto pr : {std::make_pair(&l.main, &mi), std::make_pair(&l.tail, &ti)}) {
-            pr.first->n_items = (int)pr.second->size();
-            pr.first->h_items = *pr.second;
-            if (pr.second->empty()) continue;
-            DODT_HIP_CHECK(hipMalloc(&pr.first->d_items, pr.second->size() * sizeof(int4)));
-            DODT_HIP_CHECK(hipMemcpyAsync(pr.first->d_items, pr.second->data(),
-                                          pr.second->size() * sizeof(int4), hipMemcpyHostToDevice,
-                                          ctx->stream));
+        for (Launch* ln : {&l.main, &l.tail}) {
+            if (ln->h_items.empty()) continue;
+            DODT_HIP_CHECK(hipMalloc(&ln->d_items, ln->h_items.size() * sizeof(int4)));
+            DODT_HIP_CHECK(hipMemcpyAsync(ln->d_items, ln->h_items.data(), ln->h_items.size() * sizeof(int4),
+                                          hipMemcpyHostToDevice, ctx->stream));
         }
-        DODT_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // the vectors go out of scope
     }
-    {
-        // bf16 conv path: conv1_1 folded into conv1_2's launch when conv1_2 runs on the streaming kernel (same tiles, same
-        // weight blocking) and the input rows are whole 16-byte slots (DODT_CONV_BF16_FIRST2=0: two launches)
-        static const bool first2 = !(getenv("DODT_CONV_BF16_FIRST2") && atoi(getenv("DODT_CONV_BF16_FIRST2")) == 0);
-        const Layer& c11 = ex->layers[CONV1_1];
-        const Layer& c12 = ex->layers[CONV1_2];
-        const auto& vs = variants();
-        if (first2 && bf16 && ex->parts == 1 && vs[c12.variant].stream_nch == 2 && c12.tail.n_items == 0 &&
-            c11.Cout == 32 && c11.src_coff == 0 && ex->buf[X0].C == c11.Cin && (W * c11.Cin * 4) % 16 == 0 &&
-            variant_can_pool(vs[c12.variant]))
-            for (size_t i = 0; i < vs.size() && ex->first2_variant < 0; ++i)
-                if (vs[i].first2 == c11.Cin && vs[i].TH == vs[c12.variant].TH && vs[i].TW == vs[c12.variant].TW &&
-                    vs[i].lds_bytes <= (getenv("DODT_CONV_BF16_STREAM_LDS") ? atoi(getenv("DODT_CONV_BF16_STREAM_LDS")) * 1024 : 1 << 30))
-                    ex->first2_variant = (int)i;
-    }
+    DODT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (getenv("DODT_DEBUG_PLAN")) {
         if (ex->first2_variant >= 0) fprintf(stderr, "[dodt] conv1_1 runs folded into conv1_2's launch\n");
         for (const Layer& l : ex->layers) {

@@ -117,6 +117,19 @@ int dodt_ctx_destroy(dodt_ctx* ctx) {
     return DODT_OK;
 }
 
+// Multiples of 8 only: the grouped work queues of the conv kernels give block b the queue b & 7, each queue an
+// eighth of the items.  A grid of fewer than 8 blocks with more than 8 items would leave queues that hold items
+// without a block drawing from them; every grid is a CU count times a variant's workgroups per CU, so a multiple
+// of 8 CUs keeps every grid with more items than blocks a multiple of 8.  Never above the device's own count:
+// the grids only shrink, and the workgroups stay resident.
+int dodt_ctx_set_plan_cus(dodt_ctx* ctx, int n) {
+    DODT_REQUIRE(ctx, "dodt_ctx_set_plan_cus: ctx is NULL");
+    DODT_REQUIRE(n >= 8 && n % 8 == 0 && n <= ctx->num_cus,
+                 "dodt_ctx_set_plan_cus: %d is not a multiple of 8 from 8 to the device's %d CUs", n, ctx->num_cus);
+    ctx->plan_cus = n;
+    return DODT_OK;
+}
+
 int dodt_ctx_sync(dodt_ctx* ctx) {
     DODT_REQUIRE(ctx, "dodt_ctx_sync: ctx is NULL");
     DODT_HIP_CHECK(hipStreamSynchronize(ctx->stream));

@@ -90,6 +90,17 @@ struct OutPair {
 };
 constexpr int kOutPairs = 8;
 
+// What the host decides about an extractor before it touches the device (plan_convs): the layers in launch order,
+// each with its variants and the item tables of its launches (Launch::h_items), and the first layers' folding.
+struct ConvPlan {
+    int kind = DODT_EXTRACTOR_VGG_PYR;   // without the flag bits
+    bool bf16 = false;
+    int parts = 1;
+    int H = 0, W = 0;            // padded input size
+    std::vector<Layer> layers;
+    int first2_variant = -1;     // dodt_extractor::first2_variant
+};
+
 }  // namespace dodt
 
 struct dodt_extractor {
@@ -100,6 +111,7 @@ struct dodt_extractor {
     bool bf16 = false;  // conv path on bf16 MFMA (fp32 accumulate, fp32 BN/ReLU, bf16 maps)
     int parts = 1;      // 2: split mode (hi + lo bf16 maps and weights, three MFMAs per term)
     int H = 0, W = 0;  // padded input size
+    int num_cus = 0;   // CUs the layers were planned for and the grids are sized by (dodt_ctx_set_plan_cus, or the device's)
     dodt::Buffer buf[dodt::NBUF];
     std::vector<dodt::Layer> layers;
     float* d_bneck_w = nullptr;
@@ -150,6 +162,9 @@ const std::vector<KernelVariant>& variants();
 int fused_pool_buffer(const Layer& l);
 // pyramid_fusion1 computes the 1x1 bottleneck in its epilogue (32-channel tiles)
 bool bneck_fused(const Layer& last);
+// The layer list of an extractor of `kind` (flag bits included) for num_cus CUs: each layer's variant, its main and
+// tail launch with their item tables, the folded first layers.  Host only: reads no device and allocates nothing on one.
+int plan_convs(int kind, int in_h, int in_w, int in_c, int pad_top, int batch, int num_cus, ConvPlan& plan);
 // the layers of one walk on the extractor's stream; writes nothing in the extractor
 int run_layers(const dodt_extractor* ex, const Pass& p, float* d_feat_out, float* d_bottleneck_out);
 

@@ -105,7 +105,9 @@ class PinnedArray(object):
 class Context(object):
     """One per GPU per process (include/dodt_hip.h conventions)."""
 
-    def __init__(self, device_id=0, stream=None, high_priority=False):
+    def __init__(self, device_id=0, stream=None, high_priority=False, plan_cus=None):
+        """plan_cus: extractors created on this context plan their layers and size their grids as on a device
+        of that many CUs (dodt_ctx_set_plan_cus: a multiple of 8, at most the device's own count)."""
         self.lib = _lib.load()
         h = C.c_void_p()
         if stream is None and high_priority:
@@ -119,6 +121,12 @@ class Context(object):
         _lib.check(rc, 'dodt_ctx_create')
         self.handle = h
         self.device_id = int(device_id)
+        if plan_cus is not None:
+            try:
+                _lib.check(self.lib.dodt_ctx_set_plan_cus(h, int(plan_cus)), 'dodt_ctx_set_plan_cus')
+            except Exception:
+                self.close()
+                raise
 
     def empty(self, shape, dtype=np.float32):
         return DeviceArray(self, shape, dtype)

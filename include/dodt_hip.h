@@ -51,6 +51,12 @@ int dodt_ctx_create_high_priority(int device_id, dodt_ctx** out);
 /* Use an existing hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) */
 int dodt_ctx_create_on_stream(int device_id, void* hip_stream, dodt_ctx** out);
 int dodt_ctx_destroy(dodt_ctx* ctx);
+/* The CU count that extractors created on ctx AFTER this call plan their layers with and size their grids by (by
+ * default the device's).  Lets a small input walk the code a full-size one walks: several work items per persistent
+ * workgroup, tail launches, the wide tiles.  n: a multiple of 8 from 8 to the device's count, anything else is
+ * DODT_ERR_INVALID (the grouped work queues hand block b the queue b & 7: a grid of fewer than 8 blocks with more
+ * than 8 items would leave queues without a block).  It never raises the count: grids only shrink. */
+int dodt_ctx_set_plan_cus(dodt_ctx* ctx, int n);
 int dodt_ctx_sync(dodt_ctx* ctx);
 /* Timing marks (256 per context) for stream-level timelines: record one on ctx's stream;
  * elapsed GPU time between two marks, possibly of different contexts (waits for `to`). */
@@ -372,6 +378,50 @@ typedef struct dodt_layer_info {
     int32_t reserved_;
 } dodt_layer_info;
 int dodt_extractor_layer_count(const dodt_extractor* ex);
+/* The kernel-variant table the layers choose from. */
+#define DODT_VARIANT_DECONV 0x1       /* transposed conv */
+#define DODT_VARIANT_SMALL_CIN 0x2    /* first-layer kernel (4 / 6 input channels) */
+#define DODT_VARIANT_TAIL_ONLY 0x4    /* quarter tiles: never a layer's main variant */
+#define DODT_VARIANT_BF16 0x8
+#define DODT_VARIANT_SPLIT 0x10       /* hi + lo bf16 pairs */
+#define DODT_VARIANT_WINO 0x20        /* Winograd, F(2x2,3x3) unless ... */
+#define DODT_VARIANT_WINO43 0x40      /* ... F(4x4,3x3) */
+#define DODT_VARIANT_DMA 0x80         /* bf16 3x3 kernels with LDS-DMA staging */
+#define DODT_VARIANT_DECONV_DMA 0x100 /* transposed conv, LDS-DMA staged */
+#define DODT_VARIANT_FIRST2 0x200     /* conv1_1 folded into conv1_2 */
+#define DODT_VARIANT_STREAM 0x400     /* producer wave, weights in registers */
+#define DODT_VARIANT_XCD_QUEUE 0x800  /* walks one work queue per group of blocks that share an XCD (in this process) */
+#define DODT_VARIANT_CAN_POOL 0x1000  /* its epilogue can write the 2x2 max pool behind the layer */
+typedef struct dodt_conv_variant {
+    int32_t tw, th, bn, ck;  /* output tile (transposed convs: input pixels), channels per tile, channels per chunk */
+    int32_t flags;           /* DODT_VARIANT_* */
+    int32_t blocks_per_cu;   /* resident workgroups per CU its grids are sized by */
+    int32_t lds_bytes;
+    int32_t reserved_;
+    char kernel[48];         /* the __global__ function */
+} dodt_conv_variant;
+int dodt_conv_variant_count(void);
+int dodt_conv_variant_info(int i, dodt_conv_variant* out);
+/* What the host decides about one layer before anything runs: [0] its main launch, [1] its tail launch. */
+typedef struct dodt_conv_layer_plan {
+    char name[32];
+    int32_t h, w, cin, cout; /* the layer's GEMM grid (transposed convs: the input's size) and channels */
+    int32_t variant[2];   /* index into the variant table; -1: no such launch */
+    int32_t items[2];     /* work items of the full tables */
+    int32_t grid[2];      /* workgroups launched for them */
+    int32_t pool_fused;   /* the 2x2 max pool behind the layer runs in its epilogue */
+    int32_t bneck_fused;  /* pyramid_fusion1: the 1x1 bottleneck runs in its epilogue */
+    int32_t folded;       /* conv1_1: computed inside conv1_2's launch (no launch of its own; conv1_2's main variant is then
+                           * the folding kernel) */
+    int32_t reserved_;
+} dodt_conv_layer_plan;
+/* Host only: the plan dodt_extractor_create makes for these arguments (kind with its flag bits) on a device of num_cus
+ * CUs, in launch order; *n_layers (may be NULL) receives the layer count, out (may be NULL) has room for n_out records.
+ * The environment switches of the conv path apply as they do to an extractor of this process. */
+int dodt_conv_plan_host(int kind, int in_h, int in_w, int in_c, int pad_top, int batch, int num_cus,
+                        dodt_conv_layer_plan* out, int n_out, int* n_layers);
+/* The same records from a live extractor. */
+int dodt_extractor_layer_plan(const dodt_extractor* ex, dodt_conv_layer_plan* out, int n_out, int* n_layers);
 int dodt_extractor_forward_timed(dodt_extractor* ex, const float* d_in, float* d_feat_out,
                                  float* d_bottleneck_out, dodt_layer_info* info, int n_info);
 

@@ -33,13 +33,10 @@ def _check_all_layers(ex, params, x, pad_top):
         _close(ex.activation(name), np.stack(collect[name]), name)
 
 
-@pytest.mark.parametrize('h,w', [(60, 96), (28, 40), (44, 72), (12, 136)])
-def test_bev_pyramid_small_all_layers(h, w):
-    """(h + 4) x w must be divisible by 8; every layer is compared."""
+def _bev_small_all_layers(h, w, params):
     rng = np.random.default_rng(h * w)
     x = rng.uniform(0, 1, size=(2, h, w, 6)).astype(np.float32)
     x[x < 0.7] = 0                                   # BEV maps are sparse
-    params = synth.pyramid_params(6, seed=42)
     ex = BevVggPyr()
     ex.load_params(params)
     feat, ends = ex.build(x, with_bottleneck=True)
@@ -51,14 +48,34 @@ def test_bev_pyramid_small_all_layers(h, w):
     ex.close()
 
 
+@pytest.mark.parametrize('h,w', [(60, 96), (28, 40), (44, 72), (12, 136)])
+def test_bev_pyramid_small_all_layers(h, w):
+    """(h + 4) x w must be divisible by 8; every layer is compared."""
+    _bev_small_all_layers(h, w, synth.pyramid_params(6, seed=42))
+
+
+@pytest.mark.parametrize('net', ['bev', 'img'])
+def test_small_all_layers_with_varied_batch_norm(net):
+    """The same checks, once, with batch-norm statistics that differ per layer and channel
+    (tests/_conv_cases.py varied_bn): synth.pyramid_params' mean 0 / var 1 give every channel one scale."""
+    import _conv_cases as cc
+    if net == 'bev':
+        _bev_small_all_layers(60, 96, cc.net_params('bev'))
+    else:
+        _img_small_all_layers(cc.net_params('img'))
+
+
 def test_img_pyramid_small_all_layers():
+    _img_small_all_layers(synth.pyramid_params(3, seed=142))
+
+
+def _img_small_all_layers(params):
     rng = np.random.default_rng(77)
     img = rng.integers(0, 256, size=(53, 170, 3), dtype=np.uint8)
     ex = ImgVggPyr()
     pre = ex.preprocess_input(img[None], (48, 160))
     want_pre = tfops.img_preprocess(img, 48, 160)
     assert np.array_equal(pre[0], want_pre)           # unfused fp32: bit exact
-    params = synth.pyramid_params(3, seed=142)
     ex.load_params(params)
     x = np.stack([pre[0], pre[0][::-1].copy()])
     feat, _ = ex.build(x)

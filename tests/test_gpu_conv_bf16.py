@@ -76,6 +76,22 @@ def test_img_pyramid_bf16_all_layers():
     _run(ImgVggPyr, x, synth.pyramid_params(3, seed=142), 0)
 
 
+@pytest.mark.parametrize('net', ['bev', 'img'])
+def test_pyramid_bf16_all_layers_with_varied_batch_norm(net):
+    """The same all-layers checks against the same bars, once, with batch-norm statistics that differ per layer and
+    channel (tests/_conv_cases.py varied_bn; synth.pyramid_params gives every channel of every layer one scale)."""
+    import _conv_cases as cc
+    if net == 'bev':
+        rng = np.random.default_rng(60 * 96 + 1)
+        x = rng.uniform(0, 1, size=(2, 60, 96, 6)).astype(np.float32)
+        x[x < 0.7] = 0
+        _run(BevVggPyr, x, cc.net_params('bev'), 4)
+    else:
+        rng = np.random.default_rng(78)
+        x = rng.normal(0, 60, size=(2, 48, 160, 3)).astype(np.float32)
+        _run(ImgVggPyr, x, cc.net_params('img'), 0)
+
+
 def test_bf16_is_opt_in_and_checked():
     with pytest.raises(ValueError):
         BevVggPyr(conv_dtype='fp8')

@@ -45,6 +45,23 @@ def test_bev_pyramid_split_all_layers_at_fp32_tolerance(h, w):
     print('worst layer error / scale: %.2e' % worst)
 
 
+@pytest.mark.parametrize('net', ['bev', 'img'])
+def test_pyramid_split_all_layers_with_varied_batch_norm(net):
+    """The same checks at the same tolerance, once, with batch-norm statistics that differ per layer and channel
+    (tests/_conv_cases.py varied_bn; synth.pyramid_params gives every channel of every layer one scale)."""
+    import _conv_cases as cc
+    if net == 'bev':
+        rng = np.random.default_rng(60 * 96 + 2)
+        x = rng.uniform(0, 1, size=(2, 60, 96, 6)).astype(np.float32)
+        x[x < 0.7] = 0
+        worst = _run(BevVggPyr, x, cc.net_params('bev'), 4)
+    else:
+        rng = np.random.default_rng(79)
+        x = rng.normal(0, 60, size=(2, 48, 160, 3)).astype(np.float32)
+        worst = _run(ImgVggPyr, x, cc.net_params('img'), 0)
+    print('worst layer error / scale: %.2e' % worst)
+
+
 def test_img_pyramid_split_all_layers_at_fp32_tolerance():
     rng = np.random.default_rng(79)
     x = rng.normal(0, 60, size=(2, 48, 160, 3)).astype(np.float32)

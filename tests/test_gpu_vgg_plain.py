@@ -26,9 +26,22 @@ def _close(got, want, name, rel=1e-4):
                                        (BevVgg, 56, 64, 6),
                                        (ImgVgg, 60, 198, 3)])     # 198 -> 99 -> 49 -> 24
 def test_plain_vgg_small_all_layers(cls, h, w, c):
+    _small_all_layers(cls, h, w, c, synth.pyramid_params(c, seed=42, plain=True))
+
+
+@pytest.mark.parametrize('cls,h,w,c,net', [(BevVgg, 44, 52, 6, 'bev_plain'), (ImgVgg, 60, 198, 3, 'img_plain')])
+def test_plain_vgg_small_all_layers_with_varied_batch_norm(cls, h, w, c, net):
+    """The same checks, once per net, with batch-norm statistics that differ per layer and channel
+    (tests/_conv_cases.py varied_bn; synth.pyramid_params gives every channel of every layer one scale).  The inputs
+    here are uniform in [-1, 1): the statistics are in that unit."""
+    import _conv_cases as cc
+    p = synth.pyramid_params(c, seed=42, plain=True)
+    _small_all_layers(cls, h, w, c, cc.varied_bn(p, seed=1000 + c))
+
+
+def _small_all_layers(cls, h, w, c, params):
     rng = np.random.default_rng(h * w + c)
     x = rng.uniform(-1, 1, size=(2, h, w, c)).astype(np.float32)
-    params = synth.pyramid_params(c, seed=42, plain=True)
     ex = cls()
     ex.load_params(params)
     feat, ends = ex.build(x, with_bottleneck=True)
