@@ -74,6 +74,13 @@ class ConvLayerPlan(C.Structure):
                 ('folded', C.c_int32), ('reserved_', C.c_int32)]
 
 
+class NmsPlan(C.Structure):
+    _fields_ = [('n_pad', C.c_int32), ('nb', C.c_int32), ('n_rows', C.c_int32), ('ranked', C.c_int32),
+                ('sort_tiles', C.c_int32), ('first_rows', C.c_int32), ('later_rows', C.c_int32),
+                ('chunk_rows', C.c_int32), ('n_chunks', C.c_int32), ('scan_lds_bytes', C.c_int32),
+                ('scratch_bytes', C.c_int64)]
+
+
 _vp = C.c_void_p
 _i = C.c_int
 _f = C.c_float
@@ -172,6 +179,8 @@ SIGNATURES = {
     'dodt_fc_forward_split_bf16': (_i, [_vp, _vp, _vp, _i, _i, _pi32, _i, C.POINTER(_i), C.POINTER(_vp)]),
     'dodt_rows_to_bf16': (_i, [_vp, _pf, _pf, _i, _pi32, _i, _i, _vp, _i]),
     'dodt_nms': (_i, [_vp, _pf, _pf, _i, _pi32, _i, _f, _pi32, _pi32]),
+    'dodt_nms_plan_host': (_i, [_i, _i, C.POINTER(NmsPlan), C.POINTER(C.c_int32), _i]),
+    'dodt_nms_scratch_bytes': (C.c_longlong, [_vp]),
     'dodt_offset_to_anchor': (_i, [_vp, _pf, _pf, _i, _pi32, _pf]),
     'dodt_softmax_fg': (_i, [_vp, _pf, _i, _pi32, _pf]),
     'dodt_rpn_decode': (_i, [_vp, _pf, _pf, _pf, _i, _pi32, C.POINTER(_f), _pf, _pf, _pf]),

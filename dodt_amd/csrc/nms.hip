@@ -60,7 +60,11 @@ nms_keys_kernel(const float* __restrict__ scores, int n, const int* __restrict__
     if (i >= n_pad) return;
     if (rank) rank[i] = 0;
     unsigned long long k = ~0ull;
-    if (i < n_eff) k = ((unsigned long long)(~ordered_bits(scores[i])) << 32) | (uint32_t)i;
+    if (i < n_eff) {
+        uint32_t b = __float_as_uint(scores[i]);
+        if (b == 0x80000000u) b = 0u;   // -0.0 == +0.0 under float comparison: the two tie, index order decides
+        k = ((unsigned long long)(~ordered_bits(__uint_as_float(b))) << 32) | (uint32_t)i;
+    }
     keys[i] = k;
 }
 
@@ -396,7 +400,83 @@ int next_pow2(int v) {
     return p;
 }
 
+// Everything dodt_nms decides on the host for (n, max_out), n > 0 and max_out > 0: sizes, the order's path, the
+// row chunks and the scratch layout.  Touches no device; dodt_nms launches from it and dodt_nms_plan_host exports it.
+struct NmsPlan {
+    int n_pad, nb, n_rows;
+    bool ranked;
+    int sort_tiles;                 // bitonic path: kTile-key tiles of the sort; 0 on the counted-rank path
+    int first_rows, later_rows, chunk_rows, n_chunks;
+    size_t o_state, o_keys, o_rank, o_sb, o_idx, o_removed, o_diag, o_mask, scratch_bytes;
+    size_t scan_lds;                // dynamic LDS of nms_scan_kernel
+    // rows of the chunk that starts at row0
+    int rows_at(int row0) const {
+        const int want = row0 == 0 ? first_rows : later_rows;
+        return (n_rows - row0) < want ? (n_rows - row0) : want;
+    }
+};
+
+NmsPlan plan_nms(int n, int max_out) {
+    NmsPlan p;
+    p.n_pad = next_pow2(n < 2 ? 2 : n);
+    p.nb = dodt::ceil_div(n, 64);
+    p.n_rows = p.nb * 64;
+    p.ranked = n <= kRankMax;
+    p.sort_tiles = p.ranked ? 0 : p.n_pad / (p.n_pad < kTile ? p.n_pad : kTile);
+    // chunks of candidate rows: the first just over max_out (all of them up to 2048 rows: one mask + scan pair
+    // then), the others as large as a 32 MB matrix allows, at most 4096 (the scan's 64 in-chunk column blocks)
+    p.later_rows = p.nb <= 1024 ? 2 * kChunkRows : kChunkRows;
+    p.first_rows = (int)dodt::align_up((size_t)max_out + (size_t)max_out / 8, 64) + 64;
+    if (p.first_rows > p.later_rows) p.first_rows = p.later_rows;
+    if (p.first_rows > p.n_rows || p.n_rows <= kChunkRows) p.first_rows = p.n_rows;
+    // two chunks instead of three where a somewhat longer first one does it (the RPN's 5 760 rows: 1 664 + 4 096)
+    if (p.n_rows - p.first_rows > p.later_rows && p.n_rows - p.later_rows <= p.later_rows)
+        p.first_rows = p.n_rows - p.later_rows;
+    p.chunk_rows = p.n_rows < p.later_rows ? p.n_rows : p.later_rows;    // the largest chunk
+    p.n_chunks = 0;
+    for (int row0 = 0; row0 < p.n_rows; row0 += p.rows_at(row0)) ++p.n_chunks;
+    // scratch layout
+    size_t off = 0;
+    p.o_state = off; off += 256;
+    p.o_keys = off; off += dodt::align_up((size_t)p.n_pad * 8, 256);
+    p.o_rank = off; off += dodt::align_up((size_t)p.n_pad * 4, 256);
+    p.o_sb = off; off += dodt::align_up((size_t)p.n_rows * 5 * 4, 256);
+    p.o_idx = off; off += dodt::align_up((size_t)p.n_rows * 4, 256);
+    p.o_removed = off; off += dodt::align_up((size_t)p.nb * 8, 256);
+    p.o_diag = off; off += dodt::align_up((size_t)p.n_rows * 8, 256);
+    p.o_mask = off; off += (size_t)p.chunk_rows * p.nb * 8;
+    p.scratch_bytes = off;
+    p.scan_lds = ((size_t)p.nb + p.chunk_rows + p.chunk_rows / 64) * 8;      // <= 84 KB at n = 400000
+    return p;
+}
+
+constexpr int kNmsMaxN = 400000;
+
 }  // namespace
+
+extern "C" int dodt_nms_plan_host(int n, int max_out, dodt_nms_plan* plan, int32_t* chunks, int n_chunks_out) {
+    DODT_REQUIRE(plan, "dodt_nms_plan_host: NULL argument");
+    DODT_REQUIRE(n >= 0 && max_out >= 0, "dodt_nms_plan_host: negative size");
+    DODT_REQUIRE(n <= kNmsMaxN, "dodt_nms_plan_host: n = %d exceeds %d", n, kNmsMaxN);
+    DODT_REQUIRE(n_chunks_out >= 0 && (chunks || n_chunks_out == 0), "dodt_nms_plan_host: bad chunk buffer");
+    *plan = dodt_nms_plan{};
+    if (n == 0 || max_out == 0) return DODT_OK;     // dodt_nms launches nothing: count = 0
+    const NmsPlan p = plan_nms(n, max_out);
+    plan->n_pad = p.n_pad; plan->nb = p.nb; plan->n_rows = p.n_rows;
+    plan->ranked = p.ranked ? 1 : 0; plan->sort_tiles = p.sort_tiles;
+    plan->first_rows = p.first_rows; plan->later_rows = p.later_rows; plan->chunk_rows = p.chunk_rows;
+    plan->n_chunks = p.n_chunks;
+    plan->scan_lds_bytes = (int32_t)p.scan_lds;
+    plan->scratch_bytes = (int64_t)p.scratch_bytes;
+    int c = 0;
+    for (int row0 = 0; row0 < p.n_rows && c < n_chunks_out; row0 += p.rows_at(row0), ++c) {
+        chunks[2 * c] = row0;
+        chunks[2 * c + 1] = p.rows_at(row0);
+    }
+    return DODT_OK;
+}
+
+extern "C" long long dodt_nms_scratch_bytes(const dodt_ctx* ctx) { return ctx ? (long long)ctx->nms_ws.bytes : -1; }
 
 extern "C" int dodt_nms(dodt_ctx* ctx, const float* d_boxes, const float* d_scores, int n,
                         const int32_t* d_n, int max_out, float iou_threshold, int32_t* d_sel_out,
@@ -404,45 +484,25 @@ extern "C" int dodt_nms(dodt_ctx* ctx, const float* d_boxes, const float* d_scor
     DODT_REQUIRE(ctx && d_sel_out && d_count_out && (n == 0 || (d_boxes && d_scores)),
                  "dodt_nms: NULL argument");
     DODT_REQUIRE(n >= 0 && max_out >= 0, "dodt_nms: negative size");
-    DODT_REQUIRE(n <= 400000, "dodt_nms: n = %d exceeds 400000", n);
+    DODT_REQUIRE(n <= kNmsMaxN, "dodt_nms: n = %d exceeds %d", n, kNmsMaxN);
     if (n == 0 || max_out == 0) {
         DODT_HIP_CHECK(hipMemsetAsync(d_count_out, 0, sizeof(int32_t), ctx->stream));
         return DODT_OK;
     }
-    const int n_pad = next_pow2(n < 2 ? 2 : n);
-    const int nb = dodt::ceil_div(n, 64);
-    const int n_rows = nb * 64;
-    const bool ranked = n <= kRankMax;
-    // chunks of candidate rows: the first just over max_out (all of them up to 2048 rows: one mask + scan pair
-    // then), the others as large as a 32 MB matrix allows, at most 4096 (the scan's 64 in-chunk column blocks)
-    const int later_rows = nb <= 1024 ? 2 * kChunkRows : kChunkRows;
-    int first_rows = (int)dodt::align_up((size_t)max_out + (size_t)max_out / 8, 64) + 64;
-    if (first_rows > later_rows) first_rows = later_rows;
-    if (first_rows > n_rows || n_rows <= kChunkRows) first_rows = n_rows;
-    // two chunks instead of three where a somewhat longer first one does it (the RPN's 5 760 rows: 1 664 + 4 096)
-    if (n_rows - first_rows > later_rows && n_rows - later_rows <= later_rows) first_rows = n_rows - later_rows;
-    const int chunk_rows = n_rows < later_rows ? n_rows : later_rows;    // the largest chunk
-    // scratch layout
-    size_t off = 0;
-    const size_t o_state = off; off += 256;
-    const size_t o_keys = off; off += dodt::align_up((size_t)n_pad * 8, 256);
-    const size_t o_rank = off; off += dodt::align_up((size_t)n_pad * 4, 256);
-    const size_t o_sb = off; off += dodt::align_up((size_t)n_rows * 5 * 4, 256);
-    const size_t o_idx = off; off += dodt::align_up((size_t)n_rows * 4, 256);
-    const size_t o_removed = off; off += dodt::align_up((size_t)nb * 8, 256);
-    const size_t o_diag = off; off += dodt::align_up((size_t)n_rows * 8, 256);
-    const size_t o_mask = off; off += (size_t)chunk_rows * nb * 8;
-    int rc = ctx->nms_ws.reserve(off);
+    const NmsPlan p = plan_nms(n, max_out);
+    const int n_pad = p.n_pad, nb = p.nb, n_rows = p.n_rows;
+    const bool ranked = p.ranked;
+    int rc = ctx->nms_ws.reserve(p.scratch_bytes);
     if (rc) return rc;
     char* ws = reinterpret_cast<char*>(ctx->nms_ws.ptr);
-    NmsState* st = reinterpret_cast<NmsState*>(ws + o_state);
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + o_keys);
-    int* rank = reinterpret_cast<int*>(ws + o_rank);
-    float* sb = reinterpret_cast<float*>(ws + o_sb);
-    int* sorted_idx = reinterpret_cast<int*>(ws + o_idx);
-    unsigned long long* removed = reinterpret_cast<unsigned long long*>(ws + o_removed);
-    unsigned long long* diag_cols = reinterpret_cast<unsigned long long*>(ws + o_diag);
-    unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + o_mask);
+    NmsState* st = reinterpret_cast<NmsState*>(ws + p.o_state);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + p.o_keys);
+    int* rank = reinterpret_cast<int*>(ws + p.o_rank);
+    float* sb = reinterpret_cast<float*>(ws + p.o_sb);
+    int* sorted_idx = reinterpret_cast<int*>(ws + p.o_idx);
+    unsigned long long* removed = reinterpret_cast<unsigned long long*>(ws + p.o_removed);
+    unsigned long long* diag_cols = reinterpret_cast<unsigned long long*>(ws + p.o_diag);
+    unsigned long long* mask = reinterpret_cast<unsigned long long*>(ws + p.o_mask);
     hipStream_t s = ctx->stream;
 
     const int init_n = n_pad > nb ? n_pad : nb;
@@ -457,8 +517,8 @@ extern "C" int dodt_nms(dodt_ctx* ctx, const float* d_boxes, const float* d_scor
                            d_boxes, rank, st, n_rows, sb, sorted_idx);
         DODT_LAUNCH_CHECK();
     } else {
-        const int tile = n_pad < kTile ? n_pad : kTile;
-        hipLaunchKernelGGL(nms_sort_local, dim3(n_pad / tile), dim3(kSortThreads), (size_t)tile * 8, s,
+        const int tile = n_pad / p.sort_tiles;
+        hipLaunchKernelGGL(nms_sort_local, dim3(p.sort_tiles), dim3(kSortThreads), (size_t)tile * 8, s,
                            keys, n_pad);
         DODT_LAUNCH_CHECK();
         for (int k = 2 * kTile; k <= n_pad; k <<= 1) {
@@ -476,18 +536,16 @@ extern "C" int dodt_nms(dodt_ctx* ctx, const float* d_boxes, const float* d_scor
         DODT_LAUNCH_CHECK();
     }
     const int col_groups = dodt::ceil_div(nb, kColGroup);
-    const size_t scan_lds = ((size_t)nb + chunk_rows + chunk_rows / 64) * 8;      // <= 84 KB at n = 400000
     static const hipError_t lds_attr = hipFuncSetAttribute(
         reinterpret_cast<const void*>(nms_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     DODT_HIP_CHECK(lds_attr);
     for (int row0 = 0; row0 < n_rows;) {
-        const int want = row0 == 0 ? first_rows : later_rows;
-        const int rows = (n_rows - row0) < want ? (n_rows - row0) : want;
+        const int rows = p.rows_at(row0);
         hipLaunchKernelGGL(nms_mask_kernel, dim3(col_groups, dodt::ceil_div(rows / 64, 4)),
                            dim3(256), 0, s, sb, st, row0, rows, nb, iou_threshold, mask, diag_cols);
         DODT_LAUNCH_CHECK();
         const int last = (row0 + rows >= n_rows);
-        hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(1024), scan_lds, s, mask, diag_cols,
+        hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(1024), p.scan_lds, s, mask, diag_cols,
                            sorted_idx, st, removed, row0, rows, nb, max_out, d_sel_out,
                            d_count_out, last);
         DODT_LAUNCH_CHECK();

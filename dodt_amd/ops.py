@@ -191,6 +191,26 @@ def crop_and_resize_indexed(ctx, d_image, hwc, d_boxes, n_boxes, d_box_idx, n, d
         'dodt_crop_and_resize_indexed')
 
 
+def nms_plan(n, max_out):
+    """What dodt_nms decides on the host for (n, max_out): the fields of dodt_nms_plan plus 'chunks', the
+    (row0, rows) of its mask + scan launch pairs in order (dodt_nms_plan_host).  Host only: needs no GPU."""
+    lib = _lib.load()
+    p = _lib.NmsPlan()
+    _lib.check(lib.dodt_nms_plan_host(int(n), int(max_out), C.byref(p), None, 0), 'dodt_nms_plan_host')
+    chunks = (C.c_int32 * (2 * p.n_chunks))()
+    _lib.check(lib.dodt_nms_plan_host(int(n), int(max_out), C.byref(p), chunks, p.n_chunks), 'dodt_nms_plan_host')
+    plan = dict((name, int(getattr(p, name))) for name, _ in p._fields_)
+    plan['ranked'] = bool(p.ranked)
+    plan['chunks'] = [(int(chunks[2 * c]), int(chunks[2 * c + 1])) for c in range(p.n_chunks)]
+    return plan
+
+
+def nms_scratch_bytes(ctx):
+    """Bytes of the context's NMS scratch (dodt_nms_scratch_bytes): grown, with a quarter to spare, whenever a call's
+    plan needs more than there is."""
+    return int(ctx.lib.dodt_nms_scratch_bytes(ctx.handle))
+
+
 def nms(ctx, d_boxes, d_scores, n, d_n, max_out, iou_threshold, d_sel, d_count):
     _lib.check(ctx.lib.dodt_nms(
         ctx.handle, _p(d_boxes), _p(d_scores), int(n), _p(d_n), int(max_out),

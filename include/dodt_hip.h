@@ -531,10 +531,30 @@ double dodt_fc_flops(const dodt_fc* fc, int M);
  * call sites models/dt_rpn_model.py:587-591 and models/dt_avod_model.py:606-613.
  * Candidate order is (score descending, index ascending) -- TF leaves ties
  * unspecified.  d_sel_out: (max_out) int32 selected ORIGINAL indices in score
- * order; d_count_out: (1) int32.  *d_n (may be NULL) overrides n. */
+ * order; d_count_out: (1) int32.  *d_n (may be NULL) overrides n.
+ * Scores of rows below *d_n must not be NaN (TF's comparator is undefined there); rows from *d_n on are never read. */
 int dodt_nms(dodt_ctx* ctx, const float* d_boxes, const float* d_scores, int n,
              const int32_t* d_n, int max_out, float iou_threshold, int32_t* d_sel_out,
              int32_t* d_count_out);
+/* What dodt_nms decides on the host for (n, max_out) before anything runs; all zero where it launches nothing
+ * (n == 0 or max_out == 0). */
+typedef struct dodt_nms_plan {
+    int32_t n_pad;          /* keys: n rounded up to a power of two */
+    int32_t nb, n_rows;     /* 64-box blocks, and the rows they hold */
+    int32_t ranked;         /* 1: the order comes from counted ranks, 0: from the bitonic sort */
+    int32_t sort_tiles;     /* bitonic sort: LDS tiles (workgroups of its local launches); 0 if ranked */
+    int32_t first_rows, later_rows;     /* rows of the first chunk and of the chunks behind it (the last may be shorter) */
+    int32_t chunk_rows;     /* the largest chunk: rows of the suppression matrix in the scratch */
+    int32_t n_chunks;       /* mask + scan launch pairs */
+    int32_t scan_lds_bytes; /* dynamic LDS of the scan */
+    int64_t scratch_bytes;  /* what the call reserves in the context's NMS scratch */
+} dodt_nms_plan;
+/* Host only, touches no device: the plan dodt_nms launches from.  chunks (may be NULL with n_chunks_out 0) receives
+ * (row0, rows) of the first n_chunks_out chunks, in launch order. */
+int dodt_nms_plan_host(int n, int max_out, dodt_nms_plan* plan, int32_t* chunks, int n_chunks_out);
+/* Bytes of the context's NMS scratch: 0 before the first call; a call whose plan needs more than there is replaces it
+ * by one of scratch_bytes and a quarter more, rounded up to 256. */
+long long dodt_nms_scratch_bytes(const dodt_ctx* ctx);
 
 /* ---- a12/a14: box encoders (TF branch, float32) ------------------------------------------ */
 /* anchor_encoder.offset_to_anchor (avod/core/anchor_encoder.py:99-150) */
