@@ -33,6 +33,11 @@ Sequence mode (FramePairPipeline(sequence=True), push_frame()): the steps are th
 sequence, a step takes ONE new frame, and what does not depend on a keyframe's role in a pair -- its image stack, image
 preprocessing, anchor filter and projections -- is computed once and read by both steps it belongs to (sequence_slots(),
 DESIGN section 8d).
+Both modes enqueue a step through one body, _step(), behind the checks of run() / push_frame().  A mode is three things:
+its prep (_prep, _seq_prep: both run the one per-frame chain, _prep_frame), where the image stack writes (_image_forward),
+and which buffers frame f of step k uses -- its prep set, the slot of its count's fetch, its feature views
+(_frame_buffers, asked by the preps and by _tail alike).  A step's record (_Step) is made by the call that enqueues it,
+waits in `pending`, and is completed by its tail.
 """
 import os
 from collections import namedtuple
@@ -58,16 +63,21 @@ CORR_MAX_DISP, CORR_STRIDE2, CORR_PAD = 5, 2, 5     # correlation_config; correl
 CORR_CH = (2 * (CORR_MAX_DISP // CORR_STRIDE2) + 1) ** 2
 
 # Mark slots (Context.mark / wait_mark; slots below 64 are the timing marks of _mark):    recorded by -> waited for by
-PREP_DONE_MARK = 244    # .. 246, by step % 3: every side stream at the end of a step's prep (_prep) -> the main and the
-                        # image stream in front of that step's conv stacks (run)
-TAIL_DONE_MARK = 247    # every side stream at the end of a step's tail (run) -> the main stream (the step's records are
-                        # complete there; the next BEV stack of that parity overwrites maps the tail reads) and the image
-                        # stream (the same for the image net's maps; the temporal module and the tracker read the records)
-CORR_MAP_MARK = 248     # 249, by parity: the image stream behind a step's correlation maps (run, placement 'img')
+PREP_DONE_MARK = 244    # .. 246, by step % 3: every side stream at the end of a step's prep (_prep; _seq_prep and
+                        # _seq_prep_new) -> the main and the image stream in front of that step's conv stacks (_step);
+                        # sequence mode: frame 1's stream also -> frame 0's in front of the next step's plain
+                        # voxelisation (_seq_prep), and -> the image stream in front of a priming forward (_push)
+TAIL_DONE_MARK = 247    # every side stream at the end of a step's tail (_pending_tail) -> the main stream (the step's
+                        # records are complete there; the next BEV stack of that parity overwrites maps the tail reads) and
+                        # the image stream (the same for the image net's maps; the temporal module and the tracker read the
+                        # records)
+CORR_MAP_MARK = 248     # 249, by parity: the image stream behind a step's correlation maps (_step, placement 'img')
                         # -> frame 1's side stream in front of the T branch's crops (_pair_img)
-CONV_DONE_MARK = 250    # 251, by parity: the main and the image stream behind a step's stacks (run) -> the side streams in
-                        # front of that step's tail (_wait_convs) and of the look-ahead prep of the step after next (_prep);
-                        # the main stream's also -> the image stream in front of the correlation maps (run)
+CONV_DONE_MARK = 250    # 251, by parity: the main and the image stream behind a step's stacks (_step; the image stream
+                        # also behind a priming forward, _push) -> the side streams (_wait_convs) in front of that step's
+                        # tail (_tail) and of the look-ahead prep of the step after next (_prep, _seq_prep); the main
+                        # stream's also -> the image stream in front of the correlation maps (_step); a priming forward's
+                        # -> frame 1's stream in front of the next prep of that parity (_seq_prep_new)
 PROPOSALS_MARK = 252    # frame 0's side stream where its proposals stand -> frame 1's in front of the T branch's crops
 CORR_ROIS_MARK = 253    # frame 1's side stream behind its share of the T branch -> frame 0's in front of what reads it
 
@@ -136,10 +146,16 @@ def resolve_schedule(environ, computed_heads, frames_per_sample, n_side_streams)
                     corr_map_img=environ.get('DODT_PIPE_CORR_MAP', 'img') == 'img')
 
 
-# One tail's state (FramePairPipeline._tail): the step and its parity, every frame's buffers (its own + what its prep
-# left), feature-map views, kept-anchor count and head outputs (its own buffers when the pipeline computes them), and the
-# side streams' head scratch
-_TailState = namedtuple('_TailState', 'step cur fr feat counts heads scratch')
+# One step from the call that enqueues it (FramePairPipeline._step_record: the step, its parity, its record slot, the
+# injected heads or None, whether `recover` came with it) to its tail, which adds (_tail) every frame's buffers (its own +
+# what its prep left), feature-map views and kept-anchor count, resolves `heads` to those buffers when the pipeline
+# computes them, and adds the side streams' head scratch
+_Step = namedtuple('_Step', 'step cur rslot heads recover fr feat counts scratch', defaults=(None,) * 4)
+
+
+def _pad_lookahead(lookahead):
+    """A call's `lookahead` with its optional ego-motion entry: None, or (points, n_points, image(s), ego_motion)."""
+    return None if lookahead is None else tuple(lookahead) + (None,) * (4 - len(lookahead))
 
 
 class FramePairPipeline(object):
@@ -293,7 +309,7 @@ class FramePairPipeline(object):
             self.head_scratch = [dict(rpn=self.rpn_head.make_scratch(N), fc=self.avod_head.make_scratch(P),
                                       corr_map=ctx.empty((self.bev_fh, self.bev_fw, CORR_CH), f32)
                                       if self.fps == 2 else None) for _ in self.sides]
-            # the pairs' correlation maps, by step parity (written behind the image stack on its stream, see run();
+            # the pairs' correlation maps, by step parity (written behind the image stack on its stream, see _step();
             # 'proposals' form only: made by _resolve_t_branch at the first run())
             self.corr_maps = None
             if t_branch_rows == 'detections' and self.corr_head is not None and not self._tile_list_fits():
@@ -315,6 +331,7 @@ class FramePairPipeline(object):
             # a ring of single-frame slots, keyframe j in slot j % IMG_RING (sequence_slots)
             self.img_ring = [dict(img_feat=ctx.empty((1, self.img_fh, self.img_fw, FC), f32),
                                   img_bneck=ctx.empty((1, self.img_fh, self.img_fw, 1), f32)) for _ in range(IMG_RING)]
+            self.img_ring_views = [{name: a.offset(0, a.shape[1:]) for name, a in d.items()} for d in self.img_ring]
         # per-frame views of them: feat_views[parity][frame][name]
         self.feat_views = [[{name: a.offset(a.nbytes // self.nf * f, a.shape[1:]) for name, a in d.items()}
                             for f in range(self.nf)] for d in self.feat]
@@ -327,11 +344,10 @@ class FramePairPipeline(object):
                         bev_norm=ctx.empty((N, 4), f32), img_norm=ctx.empty((N, 4), f32),
                         anchors=ctx.empty((N, 6), f32))
         if self.sequence:
-            # ... one set per KEYFRAME, shared by the two steps it belongs to, PREP_RING deep (sequence_slots); the
-            # kept-anchor count of a set once its fetch has been read; and the pipeline's own copy of each keyframe's
-            # points for its plain voxelisation as frame 0, one step after the caller handed them over
+            # ... one set per KEYFRAME, shared by the two steps it belongs to, PREP_RING deep (sequence_slots); and the
+            # pipeline's own copy of each keyframe's points for its plain voxelisation as frame 0, one step after the
+            # caller handed them over
             self.prep_sets = [prep_set() for _ in range(PREP_RING)]
-            self.seq_counts = [None] * PREP_RING
             self.pts_ring = [ctx.empty((self.n_points_max, 4), f32) for _ in range(POINT_RING)]
             self.pts_n = [0] * POINT_RING
             self.d_row_ids = ctx.array(np.arange(self.n_points_max, dtype=i32))     # (the copy is a gather of all rows)
@@ -341,6 +357,9 @@ class FramePairPipeline(object):
             self.prep3 = [[prep_set() for _ in range(self.nf)] for _ in range(3)]
         if 3 * self.nf > 32:
             raise ValueError('at most 10 frames per step (count fetch slots)')
+        # fetch slot -> the kept-anchor count read from it; None between a prep's fetch_i32_begin and the first tail that
+        # reads it (a sequence's keyframe has two tails and one fetch)
+        self.kept_counts = {}
         self.fr2 = [[], []]
         for f in range(2 * self.nf):
             b = dict(
@@ -558,7 +577,7 @@ class FramePairPipeline(object):
             d_pts, d_imgs = self._stage_from_host(self.step_idx, h_points, n_points, h_images)
         if lookahead is not None:
             # (the copies of step k + 1 go behind what its side streams hold now, i.e. behind step k's prep)
-            la = tuple(lookahead) + (None,) * (4 - len(lookahead))
+            la = _pad_lookahead(lookahead)
             nd_pts, nd_imgs = self._stage_from_host(self.step_idx + 1, la[0], la[1], la[2])
             lookahead = (nd_pts, la[1], nd_imgs, la[3])
         return self.run(d_pts, n_points, d_imgs, heads, ego_motion, lookahead)
@@ -568,34 +587,46 @@ class FramePairPipeline(object):
         is marked on those streams (PREP_DONE_MARK + k % 3).  `ahead`: enqueued by the previous step's run()
         (look-ahead): the conv inputs of this parity were last read by the convs of step k - 2, which the side
         streams are told to wait for (with the usual order, behind the tail of step k - 2, that is implied)."""
-        mean = (self.img_net._R_MEAN, self.img_net._G_MEAN, self.img_net._B_MEAN)
         cur = k & 1
-        ns = len(self.sides)
-        bev_in, img_in = self.bev_in[cur], self.img_in[cur]
         if ahead and k >= 2:
-            for c in self.sides:
-                c.wait_mark(self.ctx, CONV_DONE_MARK + cur)
-                c.wait_mark(self.img_ctx, CONV_DONE_MARK + cur)
+            self._wait_convs(cur)
         for f in range(self.nf):
-            c, b = self.sides[f % ns], self.prep3[k % 3][f]
+            b, c, slot, _ = self._frame_buffers(k, f)
             self._mark(c, k, 'prep%d_start' % f)
-            bp = self.bp
-            if ego_motion is not None and self.fps == 2 and f % 2 == 1 \
-                    and ego_motion[f // 2] is not None:
-                bp = ops.with_ego_motion(self.bp, *ego_motion[f // 2])
-            ops.bev_slices(c, d_points[f], n_points[f], bp, bev_in[f], b['occ'])
-            ops.anchor_filter(c, b['occ'], self.nx, self.nz, self.d_cells, self.n_all,
-                              b['keep'], b['count'])
-            ops.fetch_i32_begin(c, b['count'], 1, 3 * f + k % 3)
-            ops.project_anchors_f64(c, self.d_anchor_table, b['keep'], self.n_all, b['count'],
-                                    self.bev_extents_flat, self.p2, self.image_wh,
-                                    b['bev_norm'], b['img_norm'], b['anchors'])
-            ops.img_preprocess(c, d_images[f], (self.image_wh[1], self.image_wh[0]),
-                               (self.img_h, self.img_w), 4, mean, img_in[f])
+            ego = ego_motion[f // 2] if ego_motion is not None and self.fps == 2 and f % 2 == 1 else None
+            self._prep_frame(c, d_points[f], n_points[f], d_images[f], ego, self.bev_in[cur][f], self.img_in[cur][f],
+                             b, slot)
             self._mark(c, k, 'prep%d_end' % f)
         for c in self.sides:
             c.mark(PREP_DONE_MARK + k % 3)
         self.prepped = k
+
+    def _frame_buffers(self, k, f):
+        """Which buffers frame f of step k uses, for its prep and its tail alike: (what the prep leaves the tail -- occ /
+        keep / count / projections / anchors --, the stream and the slot of the kept-anchor count's fetch, the frame's
+        views of the feature maps).  Pair mode: the step's own, three deep (set k % 3) and by parity.  Sequence mode: the
+        frame is keyframe k + f, whose set and image maps lie in the ring slots sequence_slots(k) gives it -- fetched on
+        frame 1's stream, where every keyframe is prepared --, beside the step's own BEV maps."""
+        ns, views = len(self.sides), self.feat_views[k & 1][f]
+        if not self.sequence:
+            return self.prep3[k % 3][f], self.sides[f % ns], 3 * f + k % 3, views
+        slots = sequence_slots(k)
+        views = dict(views, **self.img_ring_views[slots.img[f]])
+        return self.prep_sets[slots.prep[f]], self.sides[1 % ns], PREP_RING * (1 % ns) + slots.prep[f], views
+
+    def _prep_frame(self, c, d_points, n_points, d_image, ego_motion, d_bev, d_img, b, slot):
+        """One frame's prep chain on stream c (a0-a7): BEV maps (registered by `ego_motion`, a pair's (trans, matrix), or
+        None) into d_bev, the anchor filter on the un-registered grid, the fetch of its count into `slot`, the kept
+        anchors' projections -- all into the set b --, and the preprocessed image into d_img."""
+        bp = self.bp if ego_motion is None else ops.with_ego_motion(self.bp, *ego_motion)
+        ops.bev_slices(c, d_points, n_points, bp, d_bev, b['occ'])
+        ops.anchor_filter(c, b['occ'], self.nx, self.nz, self.d_cells, self.n_all, b['keep'], b['count'])
+        ops.fetch_i32_begin(c, b['count'], 1, slot)
+        self.kept_counts[slot] = None
+        ops.project_anchors_f64(c, self.d_anchor_table, b['keep'], self.n_all, b['count'], self.bev_extents_flat,
+                                self.p2, self.image_wh, b['bev_norm'], b['img_norm'], b['anchors'])
+        ops.img_preprocess(c, d_image, (self.image_wh[1], self.image_wh[0]), (self.img_h, self.img_w), 4,
+                           (self.img_net._R_MEAN, self.img_net._G_MEAN, self.img_net._B_MEAN), d_img)
 
     def run(self, d_points, n_points, d_images, heads=None, ego_motion=None, lookahead=None, recover=None):
         """Enqueue one step.  Lists of length 2 * pairs_per_step, frame order
@@ -622,24 +653,31 @@ class FramePairPipeline(object):
         call finish() after the last step (run(); finish() is the unpipelined form)."""
         if self.sequence:
             raise ValueError('run: a sequence pipeline takes push_frame()')
-        main, img = self.ctx, self.img_ctx
         if (heads is None) != (self.rpn_head is not None):
             raise ValueError('pass `heads` exactly when the pipeline has no head_params')
+        return self._step(self._prep, (d_points, n_points, d_images, ego_motion), heads, _pad_lookahead(lookahead),
+                          recover)
+
+    def _step(self, prep, inputs, heads, lookahead, recover):
+        """The step body of run() and push_frame(): `prep`(k, points, n_points, image(s), ego_motion, ahead=) is the
+        mode's prep (_prep, _seq_prep), `inputs` and the padded `lookahead` its arguments for this step and the next."""
+        main, img = self.ctx, self.img_ctx
         self._resolve_t_branch()
         self._upload_recover(recover)
         k = self.step_idx
         cur = k & 1
         feat = self.feat[cur]
         if self.prepped != k:      # (else: enqueued by the previous call's look-ahead)
-            self._prep(k, d_points, n_points, d_images, ego_motion, ahead=False)
+            prep(k, *inputs, ahead=False)
         for c in self.sides:
             main.wait_mark(c, PREP_DONE_MARK + k % 3)
             img.wait_mark(c, PREP_DONE_MARK + k % 3)
-        # -- a8-a10: conv stacks, all frames per launch, the two nets side by side --------
+        # -- a8-a10: conv stacks, all frames per launch, the two nets side by side (sequence mode: the BEV stack over both
+        # frames, the image stack over the new one) --------
         self._mark(main, k, 'bev_start')
         self._mark(img, k, 'img_start')
         self.bev_net.forward_device_padded(self.in_bev[cur], feat['bev_feat'], feat['bev_bneck'])
-        self.img_net.forward_device_padded(self.in_img[cur], feat['img_feat'], feat['img_bneck'])
+        self._image_forward(k)
         self._mark(main, k, 'bev_end')
         self._mark(img, k, 'img_end')
         # The tail of THIS step (next call) starts when these convs are done.  The point is marked now and waited
@@ -657,13 +695,26 @@ class FramePairPipeline(object):
             img.mark(CORR_MAP_MARK + cur)
         # -- the next step's prep, when the caller has given its inputs: in front of the previous step's tail ----
         if lookahead is not None:
-            la = tuple(lookahead) + (None,) * (4 - len(lookahead))
-            self._prep(k + 1, la[0], la[1], la[2], la[3], ahead=True)
+            prep(k + 1, *lookahead, ahead=True)
         # -- the previous step's tail runs under this step's convs --------------------------
         self._pending_tail()
-        self.pending = dict(cur=cur, heads=heads, step=k, rslot=k % len(self.rec2), recover=recover is not None)
+        self.pending = self._step_record(k, heads, recover is not None)
         self.step_idx += 1
         return cur
+
+    def _step_record(self, k, heads=None, recover=False):
+        """The record of step k as the call that enqueues it leaves it in `pending` (_Step)."""
+        return _Step(step=k, cur=k & 1, rslot=k % len(self.rec2), heads=heads, recover=recover)
+
+    def _image_forward(self, k):
+        """The image stack of step k on the image stream: over every frame of the step into feat[k & 1]; in sequence
+        mode over the step's new frame (batch 1) into its slot of the image ring.  That slot's last reader is the tail of
+        step k - 2 (its frame 0), enqueued in the call before this one, whose end the image stream has been told to wait
+        for (TAIL_DONE_MARK, _pending_tail); a tail finish() enqueued stands in front of this step's preps on both side
+        streams, which the stream waits for in front of its stack."""
+        cur = k & 1
+        dst = self.img_ring[sequence_slots(k).img[1]] if self.sequence else self.feat[cur]
+        self.img_net.forward_device_padded(self.in_img[cur], dst['img_feat'], dst['img_bneck'])
 
     # ---- sequence mode (DESIGN section 8d) ------------------------------------------------------------------------
     def _seq_streams(self):
@@ -672,14 +723,14 @@ class FramePairPipeline(object):
         return self.sides[0], self.sides[1 % len(self.sides)]
 
     def _seq_prep_new(self, k, d_points, n_points, d_image, ego_motion, host):
-        """The full prep of a NEW keyframe, as frame 1 of step k, on frame 1's side stream: _prep's chain for one frame,
+        """The full prep of a NEW keyframe, as frame 1 of step k, on frame 1's side stream: the chain of _prep_frame
         into the ring slots sequence_slots(k) gives it -- its BEV maps (registered by ego_motion) are the only output
         that is this step's alone; occ / keep / count / the projections / anchors and the preprocessed image also serve
         step k + 1, where the frame is frame 0.  host: the frame is in pinned host memory; its points are copied
         straight into the pipeline's point ring, which otherwise gets a device copy of the caller's array."""
-        c0, c = self._seq_streams()
-        cur, slots = k & 1, sequence_slots(k)
-        q, ps = slots.prep[1], slots.points[1]
+        cur, ps = k & 1, sequence_slots(k).points[1]
+        c0 = self._seq_streams()[0]
+        b, c, slot, _ = self._frame_buffers(k, 1)
         if n_points > self.n_points_max:
             raise ValueError('the frame has more than n_points_max points')
         # The set and the point slot were last read on frame 0's stream: by the tail of step k + 1 - PREP_RING and by the
@@ -689,7 +740,7 @@ class FramePairPipeline(object):
             # in_img[cur] was last read by a priming push's image forward, which no tail in front of this prep waited for
             c.wait_mark(self.img_ctx, CONV_DONE_MARK + cur)
             self.seq_prime_parity = None
-        b, d_pts = self.prep_sets[q], self.pts_ring[ps]
+        d_pts = self.pts_ring[ps]
         self._mark(c, k, 'prep1_start')
         if host:
             if not hasattr(self, 'seq_img_stage'):       # (read by this stream's own preprocessing only: one buffer)
@@ -697,16 +748,7 @@ class FramePairPipeline(object):
             d_pts.upload_async(d_points, ctx=c, nbytes=16 * int(n_points))
             d_image = self.seq_img_stage.upload_async(d_image, ctx=c)
             d_points = d_pts
-        bp = self.bp if ego_motion is None else ops.with_ego_motion(self.bp, *ego_motion)
-        ops.bev_slices(c, d_points, n_points, bp, self.bev_in[cur][1], b['occ'])
-        ops.anchor_filter(c, b['occ'], self.nx, self.nz, self.d_cells, self.n_all, b['keep'], b['count'])
-        ops.fetch_i32_begin(c, b['count'], 1, PREP_RING * (1 % len(self.sides)) + q)
-        self.seq_counts[q] = None
-        ops.project_anchors_f64(c, self.d_anchor_table, b['keep'], self.n_all, b['count'], self.bev_extents_flat,
-                                self.p2, self.image_wh, b['bev_norm'], b['img_norm'], b['anchors'])
-        mean = (self.img_net._R_MEAN, self.img_net._G_MEAN, self.img_net._B_MEAN)
-        ops.img_preprocess(c, d_image, (self.image_wh[1], self.image_wh[0]), (self.img_h, self.img_w), 4, mean,
-                           self.img_in[cur][0])
+        self._prep_frame(c, d_points, n_points, d_image, ego_motion, self.bev_in[cur][1], self.img_in[cur][0], b, slot)
         if not host and n_points > 0:
             ops.gather_rows(c, d_points, 4, self.d_row_ids, n_points, None, d_pts)
         self.pts_n[ps] = int(n_points)
@@ -721,9 +763,7 @@ class FramePairPipeline(object):
         cur, slots = k & 1, sequence_slots(k)
         c0, c1 = self._seq_streams()
         if ahead and k >= 2:
-            for c in self.sides:
-                c.wait_mark(self.ctx, CONV_DONE_MARK + cur)
-                c.wait_mark(self.img_ctx, CONV_DONE_MARK + cur)
+            self._wait_convs(cur)
         # the copy of the carried frame's points was made at the end of its prep as a new frame, on frame 1's stream
         # (as frame 1 of step k - 1; that mark's next recording is the prep of step k + 2, not enqueued yet)
         self._mark(c0, k, 'prep0_start')
@@ -737,19 +777,6 @@ class FramePairPipeline(object):
             c0.mark(PREP_DONE_MARK + k % 3)
         self._seq_prep_new(k, d_points, n_points, d_image, ego_motion, host)
         self.prepped = k
-
-    def _seq_image_forward(self, k):
-        """The image net over the new frame of step k (batch 1) into its slot of the image ring, on the image stream.
-        The slot's last reader is the tail of step k - 2 (its frame 0), enqueued in the call before this one, whose end
-        the image stream has been told to wait for (TAIL_DONE_MARK, _pending_tail); a tail finish() enqueued stands in
-        front of this step's preps on both side streams, which the caller makes the stream wait for.  Marked as the
-        step's image stack (CONV_DONE_MARK)."""
-        img, cur = self.img_ctx, k & 1
-        slot = self.img_ring[sequence_slots(k).img[1]]
-        self._mark(img, k, 'img_start')
-        self.img_net.forward_device_padded(self.in_img[cur], slot['img_feat'], slot['img_bneck'])
-        self._mark(img, k, 'img_end')
-        img.mark(CONV_DONE_MARK + cur)
 
     def push_frame(self, d_points, n_points, d_image, heads=None, ego_motion=None, lookahead=None, recover=None):
         """Sequence mode's run(): ONE new keyframe -- d_points (n,4) float32 velodyne xyzi of which n_points rows are
@@ -774,61 +801,31 @@ class FramePairPipeline(object):
     def _push(self, d_points, n_points, d_image, heads, ego_motion, lookahead, recover, host):
         if not self.sequence:
             raise ValueError('push_frame: the pipeline was built without sequence=True')
-        main, img = self.ctx, self.img_ctx
+        img = self.img_ctx
         c0, c1 = self._seq_streams()
-        la = None if lookahead is None else tuple(lookahead) + (None,) * (4 - len(lookahead))
+        la = _pad_lookahead(lookahead)
         k = self.step_idx
+
+        def prep(k, *inputs, ahead):
+            self._seq_prep(k, *inputs, ahead=ahead, host=host)
         if not self.seq_primed:
             # the frame is prepared as if it were frame 1 of step k - 1: every buffer it writes is that step's, whose
-            # readers a finished sequence has left behind (end_sequence() follows finish())
+            # readers a finished sequence has left behind (end_sequence() follows finish()); its image forward is marked
+            # as that step's image stack
             self._seq_prep_new(k - 1, d_points, n_points, d_image, None, host)
             img.wait_mark(c1, PREP_DONE_MARK + (k - 1) % 3)
             img.wait_for(c0)                            # (the last sequence's tails, frame 0's, read the image ring too)
-            self._seq_image_forward(k - 1)
+            self._mark(img, k - 1, 'img_start')
+            self._image_forward(k - 1)
+            self._mark(img, k - 1, 'img_end')
+            img.mark(CONV_DONE_MARK + ((k - 1) & 1))
             self.seq_primed, self.seq_prime_parity = True, (k - 1) & 1
             if la is not None:
-                self._seq_prep(k, la[0], la[1], la[2], la[3], ahead=True, host=host)
+                prep(k, *la, ahead=True)
             return None
         if (heads is None) != (self.rpn_head is not None):
             raise ValueError('pass `heads` exactly when the pipeline has no head_params')
-        self._resolve_t_branch()
-        self._upload_recover(recover)
-        cur = k & 1
-        feat = self.feat[cur]
-        if self.prepped != k:      # (else: enqueued by the previous call's look-ahead)
-            self._seq_prep(k, d_points, n_points, d_image, ego_motion, ahead=False, host=host)
-        for c in self.sides:
-            main.wait_mark(c, PREP_DONE_MARK + k % 3)
-            img.wait_mark(c, PREP_DONE_MARK + k % 3)
-        # -- the BEV stack over both frames, beside it the image stack over the new one --------
-        self._mark(main, k, 'bev_start')
-        self.bev_net.forward_device_padded(self.in_bev[cur], feat['bev_feat'], feat['bev_bneck'])
-        self._mark(main, k, 'bev_end')
-        main.mark(CONV_DONE_MARK + cur)
-        self._seq_image_forward(k)
-        if self.placement == 'img':                     # (as in run())
-            img.wait_mark(main, CONV_DONE_MARK + cur)
-            self._correlation_map(img, cur, 0, self.corr_maps[cur][0])
-            img.mark(CORR_MAP_MARK + cur)
-        if la is not None:
-            self._seq_prep(k + 1, la[0], la[1], la[2], la[3], ahead=True, host=host)
-        self._pending_tail()
-        self.pending = dict(cur=cur, heads=heads, step=k, rslot=k % len(self.rec2), recover=recover is not None)
-        self.step_idx += 1
-        return cur
-
-    def _seq_tail_inputs(self, st):
-        """What _tail composes a sequence step's frames from: per frame its kept-anchor count (the carried frame's is
-        known from the step before), its keyframe's prep set, and views of the step's BEV maps and the keyframe's slot
-        of the image ring."""
-        slots, (_, c1) = sequence_slots(st['step']), self._seq_streams()
-        for q in slots.prep:
-            if self.seq_counts[q] is None:
-                self.seq_counts[q] = ops.fetch_i32_end(c1, PREP_RING * (1 % len(self.sides)) + q, 1)[0]
-        feat = [dict(self.feat_views[st['cur']][f],
-                     **{name: a.offset(0, a.shape[1:]) for name, a in self.img_ring[slots.img[f]].items()})
-                for f in range(2)]
-        return [self.seq_counts[q] for q in slots.prep], [self.prep_sets[q] for q in slots.prep], feat
+        return self._step(prep, (d_points, n_points, d_image, ego_motion), heads, la, recover)
 
     def _upload_recover(self, recover):
         """The step's recovery parameters for M (run()'s `recover`), into the slot of the step about to be enqueued."""
@@ -846,7 +843,6 @@ class FramePairPipeline(object):
         """Enqueue the tail of the step before the one just enqueued, then M and the tracker over its records."""
         main, img = self.ctx, self.img_ctx
         if self.pending is not None:
-            self._wait_convs(self.pending)
             self._tail(self.pending)
             for s in self.sides:
                 # one event at the tail's end, two waiters: `main` (the previous step's records are complete there, and
@@ -859,14 +855,12 @@ class FramePairPipeline(object):
                 s.mark(TAIL_DONE_MARK)
                 main.wait_mark(s, TAIL_DONE_MARK)
                 img.wait_mark(s, TAIL_DONE_MARK)
-            self._temporal_step(self.pending)
-            self._tracker_step(self.pending)
+            self._after_tail(self.pending)
 
     def finish(self):
         """Enqueue the tail of the last step; afterwards self.fr / d_records hold it."""
         st = self.pending
         if st is not None:
-            self._wait_convs(st)
             self._tail(st)
             self.pending = None
         for s in self.sides:
@@ -874,26 +868,30 @@ class FramePairPipeline(object):
         self.ctx.wait_for(self.img_ctx)
         if st is not None and (self.temporal is not None or self.tracker is not None):
             self.img_ctx.wait_for(self.ctx)         # (the main stream has joined every stream, the last tails included)
-            self._temporal_step(st)
-            self._tracker_step(st)
+            self._after_tail(st)
             self.ctx.wait_for(self.img_ctx)
+
+    def _after_tail(self, st):
+        """What reads the records of step `st` on the image stream: M, then the tracker."""
+        self._temporal_step(st)
+        self._tracker_step(st)
 
     def _temporal_step(self, st):
         """M of step `st` (pipelines built with `temporal`): one launch for all its pairs on the IMAGE stream, behind the
         next step's image stack (the shorter of the two; on the main stream, behind the BEV stack, M's 0.1 ms lengthened
-        the step by 3 %).  That stream already waits for the step's tails (TAIL_DONE_MARK, run()) -- its records are
+        the step by 3 %).  That stream already waits for the step's tails (TAIL_DONE_MARK, _pending_tail) -- its records are
         complete there; the next writer of the record slot, the tail of step st + R, waits for the conv stacks of step
         st + R on both conv streams (CONV_DONE_MARK), i.e. behind this launch: no marks of its own.  The outputs go to
         slot st % R of the frames ring (d_frames, frames()); finish() makes the main stream wait for them."""
         if self.temporal is None:
             return
-        T, r, c = self.temporal, st['rslot'], self.img_ctx
-        self._mark(c, st['step'], 'temporal_start')
+        T, r, c = self.temporal, st.rslot, self.img_ctx
+        self._mark(c, st.step, 'temporal_start')
         ops.interpolate_pairs(c, self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, T['n_frames'], T['threshold'],
                               T['on_conflict'], self.frames2[r], self.fcnt2[r], self.fst2[r],
-                              d_recover=self.ego2[r] if st['recover'] else None,
-                              calib=self.temporal_calib if st['recover'] else None, max_out=2 * MAX_DET)
-        self._mark(c, st['step'], 'temporal_end')
+                              d_recover=self.ego2[r] if st.recover else None,
+                              calib=self.temporal_calib if st.recover else None, max_out=2 * MAX_DET)
+        self._mark(c, st.step, 'temporal_end')
         self.d_frames, self.d_frame_counts, self.d_frame_status = self.frames2[r], self.fcnt2[r], self.fst2[r]
 
     def _tracker_step(self, st):
@@ -903,10 +901,10 @@ class FramePairPipeline(object):
         launches.  The state carries over to the next step; nothing is downloaded."""
         if self.tracker is None:
             return
-        r, c = st['rslot'], self.img_ctx
-        self._mark(c, st['step'], 'tracker_start')
+        r, c = st.rslot, self.img_ctx
+        self._mark(c, st.step, 'tracker_start')
         self.track_state.track_records(self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, self.p2, self.image_wh, ctx=c)
-        self._mark(c, st['step'], 'tracker_end')
+        self._mark(c, st.step, 'tracker_end')
 
     def _frame_ids(self, frame_ids):
         if frame_ids is not None:
@@ -965,32 +963,38 @@ class FramePairPipeline(object):
         return unpack_frames(self.d_frames.download(), self.d_frame_counts.download(),
                              self.d_frame_status.download(), self.temporal['on_conflict'])
 
-    def _wait_convs(self, st):
-        """The side streams wait for the conv stacks of step `st` (marked at the end of its run())."""
+    def _wait_convs(self, cur):
+        """The side streams wait for both conv stacks of the last step of parity `cur` (marked behind them, _step): in
+        front of that step's tail, and of a look-ahead prep, which overwrites the conv inputs that step read."""
         for s in self.sides:
-            s.wait_mark(self.ctx, CONV_DONE_MARK + st['cur'])
-            s.wait_mark(self.img_ctx, CONV_DONE_MARK + st['cur'])
+            s.wait_mark(self.ctx, CONV_DONE_MARK + cur)
+            s.wait_mark(self.img_ctx, CONV_DONE_MARK + cur)
 
     def _tail(self, st):
-        """Stages after the extractors for every frame of step `st` (a11-a14): the per-step state, then the stages of
-        its frames in the order of the T branch's placement (Schedule.t_placement)."""
-        cur, k3, nf, ns = st['cur'], st['step'] % 3, self.nf, len(self.sides)
-        if self.sequence:
-            counts, preps, feat = self._seq_tail_inputs(st)
-        else:
-            # kept-anchor counts of that step: fetched by its side streams, long complete
-            counts = [ops.fetch_i32_end(self.sides[f % ns], 3 * f + k3, 1)[0] for f in range(nf)]
-            preps, feat = self.prep3[k3], self.feat_views[cur]
+        """Stages after the extractors for every frame of step `st` (a11-a14), behind its conv stacks: the per-step
+        state, then the stages of its frames in the order of the T branch's placement (Schedule.t_placement)."""
+        cur, nf, ns = st.cur, self.nf, len(self.sides)
+        self._wait_convs(cur)
+        counts, preps, feat = [], [], []
+        for f in range(nf):
+            b, c, slot, views = self._frame_buffers(st.step, f)
+            # the frame's kept-anchor count: fetched by its prep, long complete (sequence mode: a carried frame's was
+            # read by the tail of the step before)
+            if self.kept_counts[slot] is None:
+                self.kept_counts[slot] = ops.fetch_i32_end(c, slot, 1)[0]
+            counts.append(self.kept_counts[slot])
+            preps.append(b)
+            feat.append(views)
         self.last_anchor_counts = counts
         self.fr = [dict(b, **p) for b, p in zip(self.fr2[cur], preps)]   # the tail's buffers + what its prep left
-        self.d_records, self.d_rec_counts = self.rec2[st['rslot']], self.cnt2[st['rslot']]
+        self.d_records, self.d_rec_counts = self.rec2[st.rslot], self.cnt2[st.rslot]
         self.d_bev_in = self.bev_in[cur]
         if self.sched.no_tail:      # (tools/: the step without its tail)
             return
         if self.on_records_reuse is not None:
-            self.on_records_reuse(st['rslot'], self.sides)
-        t = _TailState(step=st['step'], cur=cur, fr=self.fr, feat=feat, counts=counts,
-                       heads=self.fr if st['heads'] is None else st['heads'], scratch=self.head_scratch)
+            self.on_records_reuse(st.rslot, self.sides)
+        t = st._replace(fr=self.fr, feat=feat, counts=counts, heads=self.fr if st.heads is None else st.heads,
+                        scratch=self.head_scratch)
         if self.placement == 'img':
             for f0 in range(0, nf, 2):
                 self._pair_img(t, f0)
@@ -1015,7 +1019,7 @@ class FramePairPipeline(object):
                 self._records(t, f)
 
     def _pair_img(self, t, f0):
-        """Placement 'img', pair (f0, f0 + 1).  The map stands since the convs ended (run()).  Its crops at frame 0's
+        """Placement 'img', pair (f0, f0 + 1).  The map stands since the convs ended (_step).  Its crops at frame 0's
         proposals and the correlation head go onto frame 1's stream, in front of that frame's own head -- frame 0's
         stream, which carried them, was the longer chain by their 0.1 ms -- and frame 0's records wait for the offsets."""
         ns = len(self.sides)
@@ -1140,43 +1144,27 @@ class FramePairPipeline(object):
         # box_4ca: all_orientations = atan2 of the angle vectors (dt_avod_model.py:547-548),
         # gathered with the boxes by NMS #2's indices (:631-634) inside the record kernel,
         # which applies the evaluator's heading correction (dt_evaluator.py:1166-1212)
+        # several classes: NMS #2 stays class-agnostic on the largest non-background logit (dt_avod_model.py:606); score
+        # and type come from the n_cls-way softmax (dt_evaluator.py:1226-1255), through the *_classes entries, which
+        # take the column count behind the logits and the types behind the scores
         if self.n_cls > 2:
-            return self._decode_nms2_classes(c, b, h, plane)
-        if self.sched.fused_tail:
-            ops.final_decode(c, b['top_anchors'], h['offsets_4c'], h['cls_logits'],
-                             h['angle_vectors'] if self.box_4ca else None, self.P, b['top_count'], plane,
-                             self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'],
-                             b['nms2_scores'], b['det_scores'], b['orientations'] if self.box_4ca else None)
-            ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
-                    self.cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
+            decode, scores, n_cls, types = ops.final_decode_classes, ops.class_scores, (self.n_cls,), (b['det_types'],)
         else:
-            ops.box_4c_decode(c, b['top_anchors'], h['offsets_4c'], self.P, b['top_count'],
-                              plane, self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'])
-            ops.max_fg_logit(c, h['cls_logits'], 2, self.P, b['top_count'], b['nms2_scores'])
-            ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
-                    self.cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
-            ops.softmax_fg(c, h['cls_logits'], self.P, b['top_count'], b['det_scores'])
-            if self.box_4ca:
-                ops.angle_vector_to_orientation(c, h['angle_vectors'], self.P, b['top_count'], b['orientations'])
-
-    def _decode_nms2_classes(self, c, b, h, plane):
-        """_decode_nms2 for several classes: NMS #2 stays class-agnostic on the largest non-background logit
-        (dt_avod_model.py:606); score and type come from the n_cls-way softmax (dt_evaluator.py:1226-1255)."""
-        if self.sched.fused_tail:
-            ops.final_decode_classes(c, b['top_anchors'], h['offsets_4c'], h['cls_logits'], self.n_cls,
-                                     h['angle_vectors'] if self.box_4ca else None, self.P, b['top_count'], plane,
-                                     self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'],
-                                     b['nms2_scores'], b['det_scores'], b['det_types'],
-                                     b['orientations'] if self.box_4ca else None)
-            ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
-                    self.cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
+            decode, scores, n_cls, types = ops.final_decode, ops.softmax_fg, (), ()
+        fused = self.sched.fused_tail
+        if fused:
+            decode(c, b['top_anchors'], h['offsets_4c'], h['cls_logits'], *n_cls,
+                   h['angle_vectors'] if self.box_4ca else None, self.P, b['top_count'], plane,
+                   self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'],
+                   b['nms2_scores'], b['det_scores'], *types, b['orientations'] if self.box_4ca else None)
         else:
             ops.box_4c_decode(c, b['top_anchors'], h['offsets_4c'], self.P, b['top_count'],
                               plane, self.bev_extents_flat, b['boxes_3d'], b['pred_anchors'], b['nms2_boxes'])
             ops.max_fg_logit(c, h['cls_logits'], self.n_cls, self.P, b['top_count'], b['nms2_scores'])
-            ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
-                    self.cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
-            ops.class_scores(c, h['cls_logits'], self.n_cls, self.P, b['top_count'], b['det_scores'], b['det_types'])
+        ops.nms(c, b['nms2_boxes'], b['nms2_scores'], self.P, b['top_count'], MAX_DET,
+                self.cfg['avod_nms_iou_thresh'], b['det_idx'], b['det_count'])
+        if not fused:
+            scores(c, h['cls_logits'], *n_cls, self.P, b['top_count'], b['det_scores'], *types)
             if self.box_4ca:
                 ops.angle_vector_to_orientation(c, h['angle_vectors'], self.P, b['top_count'], b['orientations'])
 

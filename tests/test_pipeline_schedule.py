@@ -1,7 +1,15 @@
 """resolve_schedule(): the pipeline's switches and the T branch's placement, from an environment and how the pipeline was
-built.  No device."""
+built.  And the schedule FramePairPipeline enqueues, pinned: every case of tests/_pipeline_trace.py's CASES is run over
+the recording stand-ins and compared with tests/golden/pipeline_schedule.json (written by
+tests/golden/make_pipeline_schedule.py) -- per API call and per stream what was enqueued, with which buffers, behind
+which recording of which mark; in pair mode, the benchmark's path, also the order in which each call fed the streams,
+which is part of its speed.  No case has two unordered launches on a buffer that streams share.  No device."""
+import json
+import os
+
 import pytest
 
+import _pipeline_trace as pt
 from dodt_amd.pipeline import resolve_schedule
 
 # (computed heads, frames per sample, environment, T form, side streams) -> (placement, frames of a pair alternate)
@@ -83,3 +91,40 @@ def test_schedule_is_immutable_and_reads_the_process_environment_by_default(monk
     assert s.t_placement('proposals') == ('f1', False) and s.fused_tail
     with pytest.raises(AttributeError):
         s.fused_tail = False
+
+
+# ---- the schedule itself ---------------------------------------------------------------------------------------------
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'pipeline_schedule.json')
+
+
+@pytest.fixture(scope='module')
+def golden():
+    with open(FIXTURE) as f:
+        return json.load(f)
+
+
+def test_the_fixture_holds_exactly_the_cases(golden):
+    assert sorted(golden) == sorted(pt.CASES)
+
+
+@pytest.mark.parametrize('name', sorted(pt.CASES))
+def test_schedule_equals_the_fixture(name, golden, monkeypatch):
+    pipe, trace, calls, extra = pt.run_case(name, monkeypatch)
+    got, want = pt.schedule_digest(pipe, trace, calls, extra), golden[name]
+    assert [c['call'] for c in got['calls']] == [c['call'] for c in want['calls']]
+    text = pt.canonical(pipe, trace, extra)
+    for (label, start, end), g, w in zip(calls, got['calls'], want['calls']):
+        for s in pt.STREAMS:
+            # (a) per stream, call by call: the entries and their digest
+            if g['streams'].get(s) != w['streams'].get(s):
+                mine = [pt.entry_text(t, pt.roles(pipe, extra)) for t in trace[start:end] if t['stream'] == s]
+                pytest.fail('%s, call %r, stream %s: enqueued %s, the fixture has %s; enqueued now:\n%s'
+                            % (name, label, s, g['streams'].get(s), w['streams'].get(s), '\n'.join(mine)))
+        # (b) pair mode: the order across the streams
+        if name in pt.PAIR_MODE:
+            assert g['order'] == w['order'], '%s, call %r: the order in which the streams were fed' % (name, label)
+    assert got['marks'] == want['marks'], '%s: the timing marks' % name
+    assert sum(len(v) for v in text.values()) == len(trace)
+    # (c) every shared buffer is ordered
+    assert pt.races(pipe, trace) == set()
+    assert pipe.pending is None

@@ -82,7 +82,7 @@ def main():
             inside.append(c0.elapsed_ms(s0, c1, s1) * 1e3)
         on.mark_steps, on.marks = (), {}
         # the launch alone, back to back on the last step's records
-        st = dict(rslot=(on.step_idx - 1) % len(on.rec2), step=on.step_idx - 1, recover=False)
+        st = on._step_record(on.step_idx - 1)
         mc = on.img_ctx         # (the stream M runs on)
         mc.mark(0)
         for _ in range(200):
