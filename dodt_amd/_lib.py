@@ -213,6 +213,7 @@ SIGNATURES = {
     'dodt_three_d_iou_matrix': (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     'dodt_interpolate_pairs': (_i, [_vp, _vp, _i, _pi32, _i, _i, _i, _d, _i, _vp, C.POINTER(_d), _i, _vp,
                                     _pi32, _pi32]),
+    'dodt_interpolate_pairs_calibs': (_i, [_vp, _vp, _i, _pi32, _i, _i, _i, _d, _i, _vp, _vp, _i, _vp, _pi32, _pi32]),
     'dodt_track_state_bytes': (_i, [_i, C.POINTER(C.c_size_t)]),
     'dodt_track_reset': (_i, [_vp, _vp, _i]),
     'dodt_track_flush': (_i, [_vp, _vp, _d, _i]),

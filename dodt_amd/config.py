@@ -21,6 +21,8 @@ holds one list of clusters per class.  A configuration without `anchor_strides` 
 class, whose clusters are `anchor_sizes` and whose stride is `anchor_stride`
 (class_anchor_params()).
 """
+import collections
+
 import numpy as np
 
 
@@ -131,6 +133,27 @@ KITTI_TR_VELO_TO_CAM = np.array(
      [1.480249e-02, 7.280733e-04, -9.998902e-01, -7.631618e-02],
      [9.998621e-01, 7.523790e-03, 1.480755e-02, -2.717806e-01]])
 KITTI_IMAGE_WH = (1242, 375)
+
+
+class Calibration(collections.namedtuple('Calibration', 'p2 r0_rect tr_velo_to_cam image_wh')):
+    """The geometry of one sample (a frame pair, or a single frame): p2 (3,4), r0_rect (3,3), tr_velo_to_cam (3,4) as
+    float64 arrays, image_wh (w, h) ints.  KITTI has one per tracking video and one per object frame; both frames of a
+    pair share it.  What the pipeline takes per step (FramePairPipeline.run(..., calib=)); equal by value through
+    key()."""
+    __slots__ = ()
+
+    def __new__(cls, p2, r0_rect, tr_velo_to_cam, image_wh):
+        return super().__new__(cls, np.array(p2, dtype=np.float64).reshape(3, 4),
+                               np.array(r0_rect, dtype=np.float64).reshape(3, 3),
+                               np.array(tr_velo_to_cam, dtype=np.float64).reshape(3, 4),
+                               (int(image_wh[0]), int(image_wh[1])))
+
+    def key(self):
+        """Hashable, equal exactly when every number is (arrays do not compare with ==)."""
+        return (self.p2.tobytes(), self.r0_rect.tobytes(), self.tr_velo_to_cam.tobytes(), self.image_wh)
+
+
+KITTI_CALIBRATION = Calibration(KITTI_P2, KITTI_R0_RECT, KITTI_TR_VELO_TO_CAM, KITTI_IMAGE_WH)
 
 
 def velo_to_cam(r0_rect=KITTI_R0_RECT, tr=KITTI_TR_VELO_TO_CAM):

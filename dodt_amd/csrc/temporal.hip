@@ -16,6 +16,8 @@
 // they are computed one lane per row; only the walk over the rows with the free mask is sequential (wave 0).
 // Output rows are placed by a workgroup prefix over the items (matched and unmatched keyframe-0 detections in
 // order, then the free keyframe-1 detections in index order), one prefix per frame.
+// The recovery's calibration is the launch's one, a kernel argument, or one row per pair of a device array
+// (dodt_interpolate_pairs_calibs): the same kernel body, instantiated for either.
 #include "common.h"
 #include "iou3d.h"
 
@@ -124,16 +126,23 @@ pair_iou_kernel(const T* __restrict__ records, const int32_t* __restrict__ count
     ws[(size_t)p * max_det * max_det + q] = iou_3d(ba, bb);
 }
 
-template <typename T>
+// The calibration pair p recovers with: the launch's one (by value, dodt_interpolate_pairs) or row p of a device array
+// (dodt_interpolate_pairs_calibs: the address is the same for every lane of the workgroup, so the 42 doubles come
+// through the scalar cache and cost neither vector registers nor LDS).
+__device__ inline const Calib& calib_of_pair(const Calib& one, int) { return one; }
+__device__ inline const Calib& calib_of_pair(const Calib* rows, int p) { return rows[p]; }
+
+template <typename T, typename CalibArg>
 __global__ void __launch_bounds__(kThreads)
 interpolate_kernel(const T* __restrict__ records, const int32_t* __restrict__ counts, int max_det, int nf,
-                   double threshold, int next_best, const double* __restrict__ recover, Calib calib, int max_out,
+                   double threshold, int next_best, const double* __restrict__ recover, CalibArg calib_arg, int max_out,
                    const double* __restrict__ ws, double* __restrict__ out, int32_t* __restrict__ out_counts,
                    int32_t* __restrict__ status) {
     extern __shared__ double lds[];
     __shared__ int kept[2][kMaxDet], best[kMaxDet], match[kMaxDet], freelist[kMaxDet];
     __shared__ int wave_tot[kThreads / 64], s_k[2], s_nfree, s_status;
     const int p = blockIdx.x, t = threadIdx.x;
+    const Calib& calib = calib_of_pair(calib_arg, p);
     const bool assoc = nf >= 3;
     double* M = lds;                                          // k0 x k1, row stride k1 (association only)
     const T* rec = records + (size_t)p * 2 * max_det * kRecCols;
@@ -340,21 +349,40 @@ extern "C" int dodt_three_d_iou_matrix(dodt_ctx* ctx, const double* d_a, int na,
     return DODT_OK;
 }
 
-extern "C" int dodt_interpolate_pairs(dodt_ctx* ctx, const void* d_records, int records_f64, const int32_t* d_counts,
-                                      int n_pairs, int max_det, int n_frames, double threshold, int on_conflict,
-                                      const double* d_recover, const double* calib, int max_out, double* d_out,
-                                      int32_t* d_out_counts, int32_t* d_status) {
-    DODT_REQUIRE(ctx && n_pairs >= 0, "dodt_interpolate_pairs: bad arguments");
+namespace {
+
+template <typename T, typename CalibArg>
+int launch_interpolate(dodt_ctx* ctx, const void* d_records, const int32_t* d_counts, int n_pairs, int max_det,
+                       int n_frames, double threshold, int nb, const double* d_recover, CalibArg calib, int max_out,
+                       size_t lds, const double* ws, double* d_out, int32_t* d_out_counts, int32_t* d_status) {
+    static bool attr_set = false;       // (per instantiation)
+    if (!attr_set) {
+        DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&interpolate_kernel<T, CalibArg>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((interpolate_kernel<T, CalibArg>), dim3(n_pairs), dim3(kThreads), lds, ctx->stream,
+                       static_cast<const T*>(d_records), d_counts, max_det, n_frames, threshold, nb, d_recover, calib,
+                       max_out, ws, d_out, d_out_counts, d_status);
+    DODT_LAUNCH_CHECK();
+    return DODT_OK;
+}
+
+// Both entries: `calib` the 42 host doubles of dodt_interpolate_pairs (or NULL), or d_calibs the (n_pairs, 42) device
+// rows of dodt_interpolate_pairs_calibs.
+int interpolate_pairs(const char* who, dodt_ctx* ctx, const void* d_records, int records_f64, const int32_t* d_counts,
+                      int n_pairs, int max_det, int n_frames, double threshold, int on_conflict,
+                      const double* d_recover, const double* calib, const double* d_calibs, int max_out, double* d_out,
+                      int32_t* d_out_counts, int32_t* d_status) {
+    DODT_REQUIRE(ctx && n_pairs >= 0, "%s: bad arguments", who);
     if (n_pairs == 0) return DODT_OK;
-    DODT_REQUIRE(d_records && d_counts && d_out && d_out_counts && d_status, "dodt_interpolate_pairs: NULL argument");
-    DODT_REQUIRE(max_det >= 1 && max_det <= kMaxDet, "dodt_interpolate_pairs: max_det %d outside 1..%d", max_det,
-                 kMaxDet);
-    DODT_REQUIRE(n_frames >= 1 && n_frames <= kMaxFrames, "dodt_interpolate_pairs: n_frames %d outside 1..%d",
-                 n_frames, kMaxFrames);
-    DODT_REQUIRE(max_out >= 2 * max_det, "dodt_interpolate_pairs: max_out %d below 2 * max_det", max_out);
+    DODT_REQUIRE(d_records && d_counts && d_out && d_out_counts && d_status, "%s: NULL argument", who);
+    DODT_REQUIRE(max_det >= 1 && max_det <= kMaxDet, "%s: max_det %d outside 1..%d", who, max_det, kMaxDet);
+    DODT_REQUIRE(n_frames >= 1 && n_frames <= kMaxFrames, "%s: n_frames %d outside 1..%d", who, n_frames, kMaxFrames);
+    DODT_REQUIRE(max_out >= 2 * max_det, "%s: max_out %d below 2 * max_det", who, max_out);
     DODT_REQUIRE(on_conflict == DODT_CONFLICT_RAISE || on_conflict == DODT_CONFLICT_NEXT_BEST,
-                 "dodt_interpolate_pairs: on_conflict must be DODT_CONFLICT_RAISE or DODT_CONFLICT_NEXT_BEST");
-    DODT_REQUIRE(!d_recover || calib, "dodt_interpolate_pairs: d_recover needs calib");
+                 "%s: on_conflict must be DODT_CONFLICT_RAISE or DODT_CONFLICT_NEXT_BEST", who);
+    DODT_REQUIRE(!d_recover || calib || d_calibs, "%s: d_recover needs a calibration", who);
     Calib k;
     memset(&k, 0, sizeof(k));
     if (calib) memcpy(&k, calib, sizeof(k));
@@ -373,23 +401,40 @@ extern "C" int dodt_interpolate_pairs(dodt_ctx* ctx, const void* d_records, int 
                                static_cast<const float*>(d_records), d_counts, max_det, threshold, ws);
         DODT_LAUNCH_CHECK();
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&interpolate_kernel<float>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&interpolate_kernel<double>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr_set = true;
-    }
     const int nb = on_conflict == DODT_CONFLICT_NEXT_BEST;
-    if (records_f64)
-        hipLaunchKernelGGL(interpolate_kernel<double>, dim3(n_pairs), dim3(kThreads), lds, ctx->stream,
-                           static_cast<const double*>(d_records), d_counts, max_det, n_frames, threshold, nb,
-                           d_recover, k, max_out, ws, d_out, d_out_counts, d_status);
-    else
-        hipLaunchKernelGGL(interpolate_kernel<float>, dim3(n_pairs), dim3(kThreads), lds, ctx->stream,
-                           static_cast<const float*>(d_records), d_counts, max_det, n_frames, threshold, nb, d_recover,
-                           k, max_out, ws, d_out, d_out_counts, d_status);
-    DODT_LAUNCH_CHECK();
-    return DODT_OK;
+    if (d_calibs) {
+        const Calib* rows = reinterpret_cast<const Calib*>(d_calibs);
+        return records_f64
+            ? launch_interpolate<double, const Calib*>(ctx, d_records, d_counts, n_pairs, max_det, n_frames, threshold,
+                                                        nb, d_recover, rows, max_out, lds, ws, d_out, d_out_counts, d_status)
+            : launch_interpolate<float, const Calib*>(ctx, d_records, d_counts, n_pairs, max_det, n_frames, threshold,
+                                                       nb, d_recover, rows, max_out, lds, ws, d_out, d_out_counts, d_status);
+    }
+    return records_f64
+        ? launch_interpolate<double, Calib>(ctx, d_records, d_counts, n_pairs, max_det, n_frames, threshold, nb,
+                                            d_recover, k, max_out, lds, ws, d_out, d_out_counts, d_status)
+        : launch_interpolate<float, Calib>(ctx, d_records, d_counts, n_pairs, max_det, n_frames, threshold, nb,
+                                           d_recover, k, max_out, lds, ws, d_out, d_out_counts, d_status);
+}
+
+}  // namespace
+
+extern "C" int dodt_interpolate_pairs(dodt_ctx* ctx, const void* d_records, int records_f64, const int32_t* d_counts,
+                                      int n_pairs, int max_det, int n_frames, double threshold, int on_conflict,
+                                      const double* d_recover, const double* calib, int max_out, double* d_out,
+                                      int32_t* d_out_counts, int32_t* d_status) {
+    DODT_REQUIRE(!d_recover || calib, "dodt_interpolate_pairs: d_recover needs calib");
+    return interpolate_pairs("dodt_interpolate_pairs", ctx, d_records, records_f64, d_counts, n_pairs, max_det, n_frames,
+                             threshold, on_conflict, d_recover, calib, nullptr, max_out, d_out, d_out_counts, d_status);
+}
+
+extern "C" int dodt_interpolate_pairs_calibs(dodt_ctx* ctx, const void* d_records, int records_f64,
+                                             const int32_t* d_counts, int n_pairs, int max_det, int n_frames,
+                                             double threshold, int on_conflict, const double* d_recover,
+                                             const double* d_calibs, int max_out, double* d_out, int32_t* d_out_counts,
+                                             int32_t* d_status) {
+    DODT_REQUIRE(d_recover && d_calibs, "dodt_interpolate_pairs_calibs: needs d_recover and d_calibs");
+    return interpolate_pairs("dodt_interpolate_pairs_calibs", ctx, d_records, records_f64, d_counts, n_pairs, max_det,
+                             n_frames, threshold, on_conflict, d_recover, nullptr, d_calibs, max_out, d_out,
+                             d_out_counts, d_status);
 }

@@ -492,15 +492,29 @@ def temporal_ego(ego, n_frames):
 
 
 def interpolate_pairs(ctx, d_records, d_counts, n_pairs, max_det, n_frames, threshold, on_conflict, d_out,
-                      d_out_counts, d_status, d_recover=None, calib=None, max_out=None):
+                      d_out_counts, d_status, d_recover=None, calib=None, max_out=None, d_calibs=None):
     """Temporal module M for n_pairs keyframe pairs in one launch (dodt_interpolate_pairs): d_records
     (n_pairs, 2, max_det, 17) float32 or float64, d_counts (n_pairs, 2) int32 -> d_out (n_pairs, n_frames, max_out,
     13) float64, d_out_counts (n_pairs, n_frames) int32, d_status (n_pairs,) int32 (1: a 'raise'-mode conflict).
-    d_recover (n_pairs, n_frames, 13) float64 (temporal_ego) with calib (temporal_calib), or None."""
+    d_recover (n_pairs, n_frames, 13) float64 (temporal_ego) with calib (temporal_calib), or None.
+    d_calibs instead of calib: (n_pairs, 42) float64 on the device, pair p recovers with row p
+    (dodt_interpolate_pairs_calibs)."""
     if on_conflict not in ('raise', 'next_best'):
         raise ValueError("on_conflict must be 'raise' or 'next_best'")
     if d_records.dtype not in (np.float32, np.float64):
         raise ValueError('records must be float32 or float64')
+    if d_calibs is not None:
+        if calib is not None or d_recover is None:
+            raise ValueError('d_calibs: instead of calib, with d_recover')
+        if tuple(d_calibs.shape) != (int(n_pairs), 42) or d_calibs.dtype != np.float64:
+            raise ValueError('d_calibs must be (n_pairs, 42) float64')
+        _lib.check(ctx.lib.dodt_interpolate_pairs_calibs(
+            ctx.handle, _p(d_records), int(d_records.dtype == np.float64), _p(d_counts), int(n_pairs), int(max_det),
+            int(n_frames), float(threshold),
+            _lib.CONFLICT_NEXT_BEST if on_conflict == 'next_best' else _lib.CONFLICT_RAISE, _p(d_recover), _p(d_calibs),
+            int(2 * max_det if max_out is None else max_out), _p(d_out), _p(d_out_counts), _p(d_status)),
+            'dodt_interpolate_pairs_calibs')
+        return
     cal = None if calib is None else _arr(C.c_double, calib)
     _lib.check(ctx.lib.dodt_interpolate_pairs(
         ctx.handle, _p(d_records), int(d_records.dtype == np.float64), _p(d_counts), int(n_pairs), int(max_det),

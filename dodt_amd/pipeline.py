@@ -38,6 +38,9 @@ its prep (_prep, _seq_prep: both run the one per-frame chain, _prep_frame), wher
 and which buffers frame f of step k uses -- its prep set, the slot of its count's fetch, its feature views
 (_frame_buffers, asked by the preps and by _tail alike).  A step's record (_Step) is made by the call that enqueues it,
 waits in `pending`, and is completed by its tail.
+The geometry -- calibration and image size -- belongs to the step, not to the pipeline: the constructor's is the default,
+every step call takes `calib=` per sample, and what a step was given travels with it (_Geometry: beside its prep sets and
+in its record) to its tail, the temporal module and the tracker, which are enqueued a call later.
 """
 import os
 from collections import namedtuple
@@ -150,12 +153,62 @@ def resolve_schedule(environ, computed_heads, frames_per_sample, n_side_streams)
 # injected heads or None, whether `recover` came with it) to its tail, which adds (_tail) every frame's buffers (its own +
 # what its prep left), feature-map views and kept-anchor count, resolves `heads` to those buffers when the pipeline
 # computes them, and adds the side streams' head scratch
-_Step = namedtuple('_Step', 'step cur rslot heads recover fr feat counts scratch', defaults=(None,) * 4)
+# `geoms`: the geometry (_Geometry) of every frame of the step, as its prep used it
+_Step = namedtuple('_Step', 'step cur rslot heads recover geoms fr feat counts scratch', defaults=(None,) * 4)
 
 
 def _pad_lookahead(lookahead):
-    """A call's `lookahead` with its optional ego-motion entry: None, or (points, n_points, image(s), ego_motion)."""
-    return None if lookahead is None else tuple(lookahead) + (None,) * (4 - len(lookahead))
+    """A call's `lookahead` with its optional entries: None, or (points, n_points, image(s), ego_motion, calib)."""
+    return None if lookahead is None else tuple(lookahead) + (None,) * (5 - len(lookahead))
+
+
+class _Geometry(object):
+    """One calibration (config.Calibration) as the launches take it, made once per value (FramePairPipeline._geometry):
+    the voxeliser's parameters, the projection and the image size; M's 42 doubles and the BEV support mask when first
+    asked for.  Travels with the step it was given for."""
+
+    def __init__(self, cfg, calib):
+        self.calib, self.key = calib, calib.key()
+        self.p2, self.image_wh = calib.p2, calib.image_wh
+        self.bp = ops.make_bev_params(cfg, _config.velo_to_cam(calib.r0_rect, calib.tr_velo_to_cam), self.p2,
+                                      self.image_wh)
+        self.temporal_calib = None
+
+    def temporal_rows(self):
+        if self.temporal_calib is None:
+            self.temporal_calib = ops.temporal_calib(self.calib.r0_rect, self.calib.tr_velo_to_cam)
+        return self.temporal_calib
+
+
+class SupportUnion(object):
+    """The BEV net's input-support mask under changing calibrations: the OR of the masks (ops.bev_support_mask) of every
+    calibration seen so far.  Any superset of a step's true support is sound -- a cell marked "possibly written" that
+    receives no point is a zero input, and what the tables skip depends on the weights alone either way (DESIGN
+    section 5.0b) --, so the tables are rebuilt only when the union gains a cell: once per calibration of a data set at
+    the most.  mask_of(geometry) -> the (PAD_TOP + Z, X) uint8 mask; geometries are told apart by their `key`."""
+
+    def __init__(self, mask_of):
+        self.mask_of = mask_of
+        self.mask = None               # the union in force
+        self.covered = set()           # keys whose own mask is known to lie inside it (it only grows)
+        self.rebuilds = 0              # times add() found a new cell
+
+    def add(self, geoms):
+        """Take in the geometries of a step.  True when the union gained a cell: the tables are to be rebuilt from
+        `mask` before the step's forward."""
+        grew = False
+        for g in geoms:
+            if g.key in self.covered:
+                continue
+            m = self.mask_of(g) != 0
+            if self.mask is None:
+                self.mask, grew = m.astype(np.uint8), True
+            elif np.any(m & (self.mask == 0)):
+                self.mask = (m | (self.mask != 0)).astype(np.uint8)
+                grew = True
+            self.covered.add(g.key)
+        self.rebuilds += int(grew)
+        return grew
 
 
 class FramePairPipeline(object):
@@ -171,8 +224,12 @@ class FramePairPipeline(object):
                  image_wh=_config.KITTI_IMAGE_WH, n_points_max=120000, rpn_nms_size=1024,
                  pairs_per_step=1, side_streams=None, head_params=None, conv_dtype='f32',
                  head_dtype='f32', reuse_streams_of=None, temporal=None, tracker=None,
-                 bev_input_skip=True, bev_frame_tables=True, t_branch_rows=None, sequence=False):
-        """temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
+                 bev_input_skip=True, bev_frame_tables=True, t_branch_rows=None, sequence=False, image_wh_max=None):
+        """p2, r0_rect, tr_velo_to_cam, image_wh: the DEFAULT calibration -- what a step without `calib=` uses (self.calib,
+        a config.Calibration); every step call takes another one per sample (run()).
+        image_wh_max: None (= image_wh), or the (w, h) no host image exceeds in either dimension: the size of the
+        staging buffers of run_from_host() / push_frame_from_host().
+        temporal: None, or dict(n_frames=tau + 1, threshold=0.1, on_conflict='raise' | 'next_best') -- the temporal
         module M on the device after every step (see _temporal_step, frames()); None enqueues nothing for it.
         tracker: None, or dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3,
         classes=cfg['classes'], max_sequence_dets=65536) -- the IoU tracker on the device after every step: the pairs of
@@ -229,8 +286,14 @@ class FramePairPipeline(object):
         self.img_h, self.img_w = cfg['img_dims']
         self.n_slices = cfg['num_slices']
         self.bev_extents_flat = np.asarray(cfg['bev_extents'], np.float64).reshape(-1)
-        self.bp = ops.make_bev_params(cfg, _config.velo_to_cam(r0_rect, tr_velo_to_cam),
-                                      self.p2, self.image_wh)
+        # the geometries seen so far, by value; the default one also as the attributes it has always been
+        self._geoms = {}
+        self.geom0 = self._geometry(_config.Calibration(self.p2, r0_rect, tr_velo_to_cam, self.image_wh))
+        self.calib, self.p2, self.image_wh, self.bp = self.geom0.calib, self.geom0.p2, self.geom0.image_wh, self.geom0.bp
+        self.image_wh_max = self.image_wh if image_wh_max is None else (int(image_wh_max[0]), int(image_wh_max[1]))
+        if self.image_wh_max[0] < self.image_wh[0] or self.image_wh_max[1] < self.image_wh[1]:
+            raise ValueError('image_wh_max is smaller than image_wh')
+        self.track_geom = None         # the geometry of the tracker's current sequence (None: none has begun)
         # streams: conv stacks of the two nets side by side, per-frame work on its own.  A second pipeline in the same
         # process takes the first one's streams (`reuse_streams_of`): new ones would share hardware queues with them
         if reuse_streams_of is not None:
@@ -262,11 +325,18 @@ class FramePairPipeline(object):
         self.bev_net.load_params(bev_params)
         self.bev_net._ensure(self.nf, self.bev_h, self.bev_w, cfg['bev_depth'])
         # only cells inside the image frustum are ever non-zero (the ego-motion warp comes before the frustum test)
+        # (under several calibrations: the union of their supports, grown in front of the first BEV forward that needs
+        #  it, _grow_support; bev_skipped_items is the current union's count)
         self.bev_skipped_items = 0
+        self.support = None
         if bev_input_skip and conv_dtype == 'f32' and hasattr(self.bev_net, 'set_input_support') \
                 and self.bp.point_format == _lib.PTS_VELO_XYZI:
-            self.bev_skipped_items = self.bev_net.set_input_support(
-                ops.bev_support_mask(self.bp, self.bev_net.PAD_TOP, ctx.lib), frame_tables=bev_frame_tables)
+            # (the callable holds the pad and the library, not the pipeline: a reference cycle would keep a dropped
+            #  pipeline's device memory until the cycle collector happens to run, and free it under another one's steps)
+            pad_top, lib = self.bev_net.PAD_TOP, ctx.lib
+            self.support = SupportUnion(lambda g: ops.bev_support_mask(g.bp, pad_top, lib))
+            self._bev_frame_tables = bev_frame_tables
+            self._grow_support([self.geom0])
         self.img_net = img_cls(ctx=self.img_ctx, shared_gpu=True, conv_dtype=conv_dtype)
         self.img_net.load_params(img_params)
         n_img = 1 if self.sequence else self.nf        # (sequence mode: one forward per NEW frame)
@@ -350,11 +420,16 @@ class FramePairPipeline(object):
             self.prep_sets = [prep_set() for _ in range(PREP_RING)]
             self.pts_ring = [ctx.empty((self.n_points_max, 4), f32) for _ in range(POINT_RING)]
             self.pts_n = [0] * POINT_RING
+            # ... and each keyframe's geometry beside both: what its tails project with, what the plain voxelisation takes
+            self.prep_geoms = [self.geom0] * PREP_RING
+            self.pts_geoms = [self.geom0] * POINT_RING
+            self.seq_geom = self.geom0     # the geometry of the current sequence (a priming push sets it)
             self.d_row_ids = ctx.array(np.arange(self.n_points_max, dtype=i32))     # (the copy is a gather of all rows)
             self.seq_primed = False        # a keyframe stands ready to be frame 0 of the next step
             self.seq_prime_parity = None   # parity of the image input a priming push's forward read (_seq_prep_new)
         else:
             self.prep3 = [[prep_set() for _ in range(self.nf)] for _ in range(3)]
+            self.prep_geoms = [[self.geom0] * self.nf for _ in range(3)]      # (per frame, beside prep3)
         if 3 * self.nf > 32:
             raise ValueError('at most 10 frames per step (count fetch slots)')
         # fetch slot -> the kept-anchor count read from it; None between a prep's fetch_i32_begin and the first tail that
@@ -405,7 +480,7 @@ class FramePairPipeline(object):
         self.on_records_reuse = None
         # ---- temporal module M (opt-in): the frames between a pair's keyframes -----------------
         if self.temporal is not None:
-            self.temporal_calib = ops.temporal_calib(r0_rect, tr_velo_to_cam)
+            self.temporal_calib = self.geom0.temporal_rows()
             self._alloc_frames()
         # ---- the IoU tracker (opt-in): one sequence's state on the device, launches on the image stream ------------
         if self.tracker is not None:
@@ -449,6 +524,51 @@ class FramePairPipeline(object):
         if tk['max_sequence_dets'] < 1:
             raise ValueError('tracker: max_sequence_dets must be >= 1')
         return tk
+
+    # ---- per-sample geometry -------------------------------------------------------------------
+    def _geometry(self, calib):
+        """The _Geometry of a calibration, one per value."""
+        if not isinstance(calib, _config.Calibration):
+            calib = _config.Calibration(*calib)
+        key = calib.key()
+        g = self._geoms.get(key)
+        if g is None:
+            g = self._geoms[key] = _Geometry(self.cfg, calib)
+        return g
+
+    def _step_geoms(self, calib):
+        """A step call's `calib` -> the geometry of every FRAME of the step: None -- the constructor's calibration --, one
+        Calibration for every sample, or a list with one per sample."""
+        if calib is None:
+            return [self.geom0] * self.nf
+        if isinstance(calib, _config.Calibration):
+            return [self._geometry(calib)] * self.nf
+        if len(calib) != self.pairs:
+            raise ValueError('calib: one Calibration, or a list of %d (one per sample of the step)' % self.pairs)
+        return [g for cal in calib for g in [self._geometry(cal)] * self.fps]
+
+    @staticmethod
+    def _same_geoms(a, b):
+        return all(x is y for x, y in zip(a, b))       # (one object per value, _geometry)
+
+    def _check_images(self, images, geoms, host):
+        """Every image of a step against its sample's image size, where the array carries a shape; a host image also
+        against the staging buffers."""
+        for f, (img, g) in enumerate(zip(images, geoms)):
+            w, h = g.image_wh
+            shape = getattr(img, 'shape', None)
+            if shape is not None and tuple(shape) != (h, w, 3):
+                raise ValueError('frame %d: the image is %s, its calibration says (%d, %d, 3)' % (f, tuple(shape), h, w))
+            if host and (w > self.image_wh_max[0] or h > self.image_wh_max[1]):
+                raise ValueError('frame %d: a %d x %d host image exceeds image_wh_max %s' % (f, w, h, self.image_wh_max))
+
+    def _grow_support(self, geoms):
+        """In front of a BEV forward: the skip tables follow the union of the supports of every calibration seen so far
+        (SupportUnion) and are rebuilt -- a stream synchronisation, every table freed and made again, the next forward
+        on full tables -- only when a step brings a calibration whose support has a cell outside it."""
+        if self.support is not None and self.support.add(geoms):
+            self.bev_skipped_items = self.bev_net.set_input_support(self.support.mask,
+                                                                    frame_tables=self._bev_frame_tables)
 
     def _mark(self, c, step, name):
         """Timing mark `name` of step `step` on context c (only for steps in mark_steps)."""
@@ -527,6 +647,8 @@ class FramePairPipeline(object):
         self.fst2 = [self.ctx.zeros((self.pairs,), np.int32) for _ in range(R)]
         # (on the image stream, which M runs on: an upload there is ordered behind M of the step that last read the slot)
         self.ego2 = [self.img_ctx.zeros((self.pairs, n, 13), np.float64) for _ in range(R)]
+        # ... and, for a step whose pairs differ in calibration, M's 42 doubles per pair (_upload_recover)
+        self.cal2 = [self.img_ctx.zeros((self.pairs, 42), np.float64) for _ in range(R)]
         self.d_frames, self.d_frame_counts, self.d_frame_status = self.frames2[0], self.fcnt2[0], self.fst2[0]
 
     def use_record_ring(self, d_rec_ring, d_cnt_ring):
@@ -541,12 +663,21 @@ class FramePairPipeline(object):
                                 [d_cnt_ring.ptr + nc * i for i in range(R)])
 
     # ------------------------------------------------------------------------------------
-    def _stage_from_host(self, k, h_points, n_points, h_images):
+    def _stage_image(self, c, d_stage, h_image, g):
+        """Enqueue the copy of a host image of g's size into the head of the max-sized staging buffer d_stage on stream
+        c.  -> the device array the prep reads: the buffer itself, or its head viewed as that image."""
+        w, h = g.image_wh
+        if (h, w, 3) == d_stage.shape:
+            return d_stage.upload_async(h_image, ctx=c)
+        d_stage.upload_async(h_image, ctx=c, nbytes=h * w * 3)
+        return d_stage.offset(0, (h, w, 3))
+
+    def _stage_from_host(self, k, h_points, n_points, h_images, geoms):
         """Enqueue the copies of step k's raw frames from pinned host memory on its frames' side streams."""
         cur = k & 1
         ns = len(self.sides)
         if not hasattr(self, 'stage'):
-            H, W = self.image_wh[1], self.image_wh[0]
+            H, W = self.image_wh_max[1], self.image_wh_max[0]
             self.stage = [[(self.ctx.empty((self.n_points_max, 4), np.float32),
                             self.ctx.empty((H, W, 3), np.uint8)) for _ in range(self.nf)]
                           for _ in range(2)]
@@ -557,12 +688,11 @@ class FramePairPipeline(object):
             if n_points[f] > self.n_points_max:
                 raise ValueError('frame %d has more than n_points_max points' % f)
             dp.upload_async(h_points[f], ctx=c, nbytes=16 * int(n_points[f]))
-            di.upload_async(h_images[f], ctx=c)
             d_pts.append(dp)
-            d_imgs.append(di)
+            d_imgs.append(self._stage_image(c, di, h_images[f], geoms[f]))
         return d_pts, d_imgs
 
-    def run_from_host(self, h_points, n_points, h_images, heads=None, ego_motion=None, lookahead=None):
+    def run_from_host(self, h_points, n_points, h_images, heads=None, ego_motion=None, lookahead=None, calib=None):
         """run() for raw frames still in (page-locked) host memory: lists of PinnedArray --
         points (n_max,4) float32 of which n_points[f] rows are valid, images (H,W,3) uint8.
         The copies are enqueued on each frame's side stream in front of its prep kernels, so
@@ -571,18 +701,19 @@ class FramePairPipeline(object):
         by alternating two sets)."""
         if self.sequence:
             raise ValueError('run_from_host: a sequence pipeline takes push_frame_from_host()')
+        la = _pad_lookahead(lookahead)
+        geoms, la_geoms = self._check_run(h_images, heads, la, calib, host=True)
         if self.prepped == self.step_idx:       # staged and prepared by the previous call's look-ahead
             d_pts = d_imgs = None
         else:
-            d_pts, d_imgs = self._stage_from_host(self.step_idx, h_points, n_points, h_images)
-        if lookahead is not None:
+            d_pts, d_imgs = self._stage_from_host(self.step_idx, h_points, n_points, h_images, geoms)
+        if la is not None:
             # (the copies of step k + 1 go behind what its side streams hold now, i.e. behind step k's prep)
-            la = _pad_lookahead(lookahead)
-            nd_pts, nd_imgs = self._stage_from_host(self.step_idx + 1, la[0], la[1], la[2])
-            lookahead = (nd_pts, la[1], nd_imgs, la[3])
-        return self.run(d_pts, n_points, d_imgs, heads, ego_motion, lookahead)
+            nd_pts, nd_imgs = self._stage_from_host(self.step_idx + 1, la[0], la[1], la[2], la_geoms)
+            la = (nd_pts, la[1], nd_imgs, la[3], la_geoms)
+        return self._step(self._prep, (d_pts, n_points, d_imgs, ego_motion, geoms), heads, la, None, geoms)
 
-    def _prep(self, k, d_points, n_points, d_images, ego_motion, ahead):
+    def _prep(self, k, d_points, n_points, d_images, ego_motion, geoms, ahead):
         """a0-a7 of step k: the data side of the reference's create_feed_dict, one frame per side stream; its end
         is marked on those streams (PREP_DONE_MARK + k % 3).  `ahead`: enqueued by the previous step's run()
         (look-ahead): the conv inputs of this parity were last read by the convs of step k - 2, which the side
@@ -595,10 +726,11 @@ class FramePairPipeline(object):
             self._mark(c, k, 'prep%d_start' % f)
             ego = ego_motion[f // 2] if ego_motion is not None and self.fps == 2 and f % 2 == 1 else None
             self._prep_frame(c, d_points[f], n_points[f], d_images[f], ego, self.bev_in[cur][f], self.img_in[cur][f],
-                             b, slot)
+                             b, slot, geoms[f])
             self._mark(c, k, 'prep%d_end' % f)
         for c in self.sides:
             c.mark(PREP_DONE_MARK + k % 3)
+        self.prep_geoms[k % 3] = list(geoms)
         self.prepped = k
 
     def _frame_buffers(self, k, f):
@@ -614,21 +746,22 @@ class FramePairPipeline(object):
         views = dict(views, **self.img_ring_views[slots.img[f]])
         return self.prep_sets[slots.prep[f]], self.sides[1 % ns], PREP_RING * (1 % ns) + slots.prep[f], views
 
-    def _prep_frame(self, c, d_points, n_points, d_image, ego_motion, d_bev, d_img, b, slot):
+    def _prep_frame(self, c, d_points, n_points, d_image, ego_motion, d_bev, d_img, b, slot, g):
         """One frame's prep chain on stream c (a0-a7): BEV maps (registered by `ego_motion`, a pair's (trans, matrix), or
         None) into d_bev, the anchor filter on the un-registered grid, the fetch of its count into `slot`, the kept
-        anchors' projections -- all into the set b --, and the preprocessed image into d_img."""
-        bp = self.bp if ego_motion is None else ops.with_ego_motion(self.bp, *ego_motion)
+        anchors' projections -- all into the set b --, and the preprocessed image into d_img; under the geometry g of the
+        frame's sample."""
+        bp = g.bp if ego_motion is None else ops.with_ego_motion(g.bp, *ego_motion)
         ops.bev_slices(c, d_points, n_points, bp, d_bev, b['occ'])
         ops.anchor_filter(c, b['occ'], self.nx, self.nz, self.d_cells, self.n_all, b['keep'], b['count'])
         ops.fetch_i32_begin(c, b['count'], 1, slot)
         self.kept_counts[slot] = None
         ops.project_anchors_f64(c, self.d_anchor_table, b['keep'], self.n_all, b['count'], self.bev_extents_flat,
-                                self.p2, self.image_wh, b['bev_norm'], b['img_norm'], b['anchors'])
-        ops.img_preprocess(c, d_image, (self.image_wh[1], self.image_wh[0]), (self.img_h, self.img_w), 4,
+                                g.p2, g.image_wh, b['bev_norm'], b['img_norm'], b['anchors'])
+        ops.img_preprocess(c, d_image, (g.image_wh[1], g.image_wh[0]), (self.img_h, self.img_w), 4,
                            (self.img_net._R_MEAN, self.img_net._G_MEAN, self.img_net._B_MEAN), d_img)
 
-    def run(self, d_points, n_points, d_images, heads=None, ego_motion=None, lookahead=None, recover=None):
+    def run(self, d_points, n_points, d_images, heads=None, ego_motion=None, lookahead=None, recover=None, calib=None):
         """Enqueue one step.  Lists of length 2 * pairs_per_step, frame order
         [pair0 f0, pair0 f1, pair1 f0, ...]: d_points[f] (n,4) float32 velodyne xyzi;
         d_images[f] (H,W,3) uint8; heads[f] dict of device arrays rpn_logits (N,2),
@@ -639,7 +772,7 @@ class FramePairPipeline(object):
         registration of the pair's second frame into the first frame's coordinates
         (datasets.kitti.kitti_tracking_utils.coordinate_transform; applied to the second
         frame's BEV maps, not to its anchor-filter grid, like the reference).
-        lookahead: None, or (d_points, n_points, d_images[, ego_motion]) of the NEXT step: its prep is enqueued now,
+        lookahead: None, or (d_points, n_points, d_images[, ego_motion[, calib]]) of the NEXT step: its prep is enqueued now,
         in front of the previous step's tail on the side streams, so that the next step's convs do not wait for
         that tail (a caller that knows its next inputs -- a stream of frames -- should pass them; the next call
         must then be made with those inputs).
@@ -647,23 +780,55 @@ class FramePairPipeline(object):
         delta) for frames 1..n_frames-1 -- the recovery of those frames' detections into their own coordinates
         (kitti_tracking_utils.recovery_coordinate).  Copied to the device behind the main stream's work so far, which
         the host waits for.
+        calib: the geometry of the step's samples -- None: the constructor's calibration; one config.Calibration: every
+        sample's; a list of pairs_per_step of them: one per sample (both frames of a pair share it, and d_images[f] is
+        (h, w, 3) for its sample's image_wh).  It travels with the step: its prep, its tail -- enqueued by the NEXT call --,
+        M and the tracker all take it, whatever the calls in between bring.  A step announced by a look-ahead must come
+        with an equal calibration; with a tracker it changes only behind end_sequence().  Everything refused here is
+        refused before anything is enqueued.
         Returns the parity (0/1) of the record buffers this step will fill.  The
         detections of the PREVIOUS step are complete on the main stream when this returns
         (self.d_records / self.fr / self.last_anchor_counts then describe that step);
         call finish() after the last step (run(); finish() is the unpipelined form)."""
         if self.sequence:
             raise ValueError('run: a sequence pipeline takes push_frame()')
+        la = _pad_lookahead(lookahead)
+        geoms, la_geoms = self._check_run(d_images, heads, la, calib, host=False)
+        if la is not None:
+            la = la[:4] + (la_geoms,)
+        return self._step(self._prep, (d_points, n_points, d_images, ego_motion, geoms), heads, la, recover, geoms)
+
+    def _check_run(self, images, heads, la, calib, host):
+        """What run() / run_from_host() refuse, before anything is enqueued.  -> the frames' geometries of this step and
+        of the look-ahead's (None without one)."""
         if (heads is None) != (self.rpn_head is not None):
             raise ValueError('pass `heads` exactly when the pipeline has no head_params')
-        return self._step(self._prep, (d_points, n_points, d_images, ego_motion), heads, _pad_lookahead(lookahead),
-                          recover)
+        geoms = self._step_geoms(calib)
+        la_geoms = None if la is None else self._step_geoms(la[4])
+        if self.prepped == self.step_idx:
+            if not self._same_geoms(geoms, self.prep_geoms[self.step_idx % 3]):
+                raise ValueError('calib: not the calibration the previous call announced with its look-ahead')
+        elif images is not None:
+            self._check_images(images, geoms, host)
+        if la is not None:
+            self._check_images(la[2], la_geoms, host)
+        if self.tracker is not None:
+            # (the pairs of the steps, in order, are ONE sequence until end_sequence(): one video, one calibration.  A
+            #  look-ahead may already belong to the next sequence: it is checked when its step comes)
+            if any(g is not geoms[0] for g in geoms) or self.track_geom not in (None, geoms[0]):
+                raise ValueError('calib: with a tracker the calibration changes only behind end_sequence()')
+        return geoms, la_geoms
 
-    def _step(self, prep, inputs, heads, lookahead, recover):
-        """The step body of run() and push_frame(): `prep`(k, points, n_points, image(s), ego_motion, ahead=) is the
-        mode's prep (_prep, _seq_prep), `inputs` and the padded `lookahead` its arguments for this step and the next."""
+    def _step(self, prep, inputs, heads, lookahead, recover, geoms):
+        """The step body of run() and push_frame(): `prep`(k, points, n_points, image(s), ego_motion, geometry, ahead=)
+        is the mode's prep (_prep, _seq_prep), `inputs` and the padded `lookahead` its arguments for this step and the
+        next; `geoms` the geometry of every frame of this step (what its prep takes or, enqueued a call ago, took), which
+        the step's record carries to its tail, M and the tracker."""
         main, img = self.ctx, self.img_ctx
         self._resolve_t_branch()
-        self._upload_recover(recover)
+        self._upload_recover(recover, geoms)
+        if self.tracker is not None:
+            self.track_geom = geoms[0]
         k = self.step_idx
         cur = k & 1
         feat = self.feat[cur]
@@ -676,6 +841,7 @@ class FramePairPipeline(object):
         # frames, the image stack over the new one) --------
         self._mark(main, k, 'bev_start')
         self._mark(img, k, 'img_start')
+        self._grow_support(geoms)
         self.bev_net.forward_device_padded(self.in_bev[cur], feat['bev_feat'], feat['bev_bneck'])
         self._image_forward(k)
         self._mark(main, k, 'bev_end')
@@ -698,13 +864,14 @@ class FramePairPipeline(object):
             prep(k + 1, *lookahead, ahead=True)
         # -- the previous step's tail runs under this step's convs --------------------------
         self._pending_tail()
-        self.pending = self._step_record(k, heads, recover is not None)
+        self.pending = self._step_record(k, heads, recover is not None, geoms)
         self.step_idx += 1
         return cur
 
-    def _step_record(self, k, heads=None, recover=False):
+    def _step_record(self, k, heads=None, recover=False, geoms=None):
         """The record of step k as the call that enqueues it leaves it in `pending` (_Step)."""
-        return _Step(step=k, cur=k & 1, rslot=k % len(self.rec2), heads=heads, recover=recover)
+        return _Step(step=k, cur=k & 1, rslot=k % len(self.rec2), heads=heads, recover=recover,
+                     geoms=[self.geom0] * self.nf if geoms is None else geoms)
 
     def _image_forward(self, k):
         """The image stack of step k on the image stream: over every frame of the step into feat[k & 1]; in sequence
@@ -722,12 +889,13 @@ class FramePairPipeline(object):
         every NEW keyframe's prep and its tail)."""
         return self.sides[0], self.sides[1 % len(self.sides)]
 
-    def _seq_prep_new(self, k, d_points, n_points, d_image, ego_motion, host):
+    def _seq_prep_new(self, k, d_points, n_points, d_image, ego_motion, g, host):
         """The full prep of a NEW keyframe, as frame 1 of step k, on frame 1's side stream: the chain of _prep_frame
         into the ring slots sequence_slots(k) gives it -- its BEV maps (registered by ego_motion) are the only output
         that is this step's alone; occ / keep / count / the projections / anchors and the preprocessed image also serve
         step k + 1, where the frame is frame 0.  host: the frame is in pinned host memory; its points are copied
-        straight into the pipeline's point ring, which otherwise gets a device copy of the caller's array."""
+        straight into the pipeline's point ring, which otherwise gets a device copy of the caller's array.  g: the
+        keyframe's geometry, kept beside its prep set and its points for the step after this one."""
         cur, ps = k & 1, sequence_slots(k).points[1]
         c0 = self._seq_streams()[0]
         b, c, slot, _ = self._frame_buffers(k, 1)
@@ -744,18 +912,19 @@ class FramePairPipeline(object):
         self._mark(c, k, 'prep1_start')
         if host:
             if not hasattr(self, 'seq_img_stage'):       # (read by this stream's own preprocessing only: one buffer)
-                self.seq_img_stage = self.ctx.empty((self.image_wh[1], self.image_wh[0], 3), np.uint8)
+                self.seq_img_stage = self.ctx.empty((self.image_wh_max[1], self.image_wh_max[0], 3), np.uint8)
             d_pts.upload_async(d_points, ctx=c, nbytes=16 * int(n_points))
-            d_image = self.seq_img_stage.upload_async(d_image, ctx=c)
+            d_image = self._stage_image(c, self.seq_img_stage, d_image, g)
             d_points = d_pts
-        self._prep_frame(c, d_points, n_points, d_image, ego_motion, self.bev_in[cur][1], self.img_in[cur][0], b, slot)
+        self._prep_frame(c, d_points, n_points, d_image, ego_motion, self.bev_in[cur][1], self.img_in[cur][0], b, slot, g)
         if not host and n_points > 0:
             ops.gather_rows(c, d_points, 4, self.d_row_ids, n_points, None, d_pts)
         self.pts_n[ps] = int(n_points)
+        self.pts_geoms[ps] = self.prep_geoms[sequence_slots(k).prep[1]] = g
         self._mark(c, k, 'prep1_end')
         c.mark(PREP_DONE_MARK + k % 3)
 
-    def _seq_prep(self, k, d_points, n_points, d_image, ego_motion, ahead, host):
+    def _seq_prep(self, k, d_points, n_points, d_image, ego_motion, g, ahead, host):
         """The prep of sequence step k: on frame 0's stream what is left to do for the carried keyframe -- the plain,
         un-registered voxelisation of the pipeline's copy of its points into in_bev[k & 1][0]; as frame 1 of step
         k - 1 its maps were registered, everything else stands in its ring slots --, beside it on frame 1's stream the new
@@ -771,14 +940,16 @@ class FramePairPipeline(object):
             c0.wait_mark(c1, PREP_DONE_MARK + (k - 1) % 3)
         ps = slots.points[0]
         # (no occupancy output: the frame's grid, from the same un-registered cloud, is in its prep set)
-        ops.bev_slices(c0, self.pts_ring[ps], self.pts_n[ps], self.bp, self.bev_in[cur][0], None)
+        # (under the geometry the keyframe came with, kept beside its points)
+        ops.bev_slices(c0, self.pts_ring[ps], self.pts_n[ps], self.pts_geoms[ps].bp, self.bev_in[cur][0], None)
         self._mark(c0, k, 'prep0_end')
         if c0 is not c1:
             c0.mark(PREP_DONE_MARK + k % 3)
-        self._seq_prep_new(k, d_points, n_points, d_image, ego_motion, host)
+        self._seq_prep_new(k, d_points, n_points, d_image, ego_motion, g, host)
         self.prepped = k
 
-    def push_frame(self, d_points, n_points, d_image, heads=None, ego_motion=None, lookahead=None, recover=None):
+    def push_frame(self, d_points, n_points, d_image, heads=None, ego_motion=None, lookahead=None, recover=None,
+                   calib=None):
         """Sequence mode's run(): ONE new keyframe -- d_points (n,4) float32 velodyne xyzi of which n_points rows are
         valid, d_image (H,W,3) uint8.  The first push of a sequence (after construction or end_sequence()) only primes:
         the frame is prepared, its image forward enqueued, and None returned.  Every later push enqueues the step of
@@ -786,33 +957,49 @@ class FramePairPipeline(object):
         the previous step's detections are then complete on the main stream, and finish() drains the last step.
         heads: as for run(), the two frames' dicts in the pair's order (injected logits are inputs: nothing of them is
         carried); ignored by a priming push.  ego_motion: None, or the (trans, matrix) that registers the new frame into
-        the previous one; lookahead: None, or (d_points, n_points, d_image[, ego_motion]) of the NEXT frame, which the
-        next push must then bring; recover: as for run().  The arrays may be reused once this call's work has run: the
-        pipeline voxelises the frame a second time one step later, from a copy of its own."""
-        return self._push(d_points, n_points, d_image, heads, ego_motion, lookahead, recover, host=False)
+        the previous one; lookahead: None, or (d_points, n_points, d_image[, ego_motion[, calib]]) of the NEXT frame, which
+        the next push must then bring; recover: as for run().  The arrays may be reused once this call's work has run: the
+        pipeline voxelises the frame a second time one step later, from a copy of its own.
+        calib: None (the constructor's calibration) or the Calibration of the frame's sequence: one per sequence, so it
+        may differ from the current one only on a priming push."""
+        return self._push(d_points, n_points, d_image, heads, ego_motion, lookahead, recover, calib, host=False)
 
     def push_frame_from_host(self, h_points, n_points, h_image, heads=None, ego_motion=None, lookahead=None,
-                             recover=None):
+                             recover=None, calib=None):
         """push_frame() for a frame still in (page-locked) host memory, PinnedArrays as for run_from_host(): the points
         are copied straight into the pipeline's point ring and the image into a staging buffer, on the new frame's side
         stream in front of its prep; the host does not wait.  A look-ahead's frame is in pinned memory too."""
-        return self._push(h_points, n_points, h_image, heads, ego_motion, lookahead, recover, host=True)
+        return self._push(h_points, n_points, h_image, heads, ego_motion, lookahead, recover, calib, host=True)
 
-    def _push(self, d_points, n_points, d_image, heads, ego_motion, lookahead, recover, host):
+    def _push(self, d_points, n_points, d_image, heads, ego_motion, lookahead, recover, calib, host):
         if not self.sequence:
             raise ValueError('push_frame: the pipeline was built without sequence=True')
         img = self.img_ctx
         c0, c1 = self._seq_streams()
         la = _pad_lookahead(lookahead)
         k = self.step_idx
+        # -- what is refused, before anything is enqueued: a sequence is one video, so it has one calibration ----
+        g = self._step_geoms(calib)[0]
+        if self.seq_primed and g is not self.seq_geom:
+            raise ValueError('calib: a sequence has one calibration; it changes only on the push that begins one')
+        if self.seq_primed and (heads is None) != (self.rpn_head is not None):
+            raise ValueError('pass `heads` exactly when the pipeline has no head_params')
+        if self.prepped != k or not self.seq_primed:         # (else: prepared, and checked, by the previous call)
+            self._check_images([d_image], [g], host)
+        if la is not None:
+            if self._step_geoms(la[4])[0] is not g:
+                raise ValueError('calib: the look-ahead frame belongs to the same sequence, its calibration differs')
+            self._check_images([la[2]], [g], host)
+            la = la[:4] + (g,)
 
         def prep(k, *inputs, ahead):
             self._seq_prep(k, *inputs, ahead=ahead, host=host)
         if not self.seq_primed:
+            self.seq_geom = g
             # the frame is prepared as if it were frame 1 of step k - 1: every buffer it writes is that step's, whose
             # readers a finished sequence has left behind (end_sequence() follows finish()); its image forward is marked
             # as that step's image stack
-            self._seq_prep_new(k - 1, d_points, n_points, d_image, None, host)
+            self._seq_prep_new(k - 1, d_points, n_points, d_image, None, g, host)
             img.wait_mark(c1, PREP_DONE_MARK + (k - 1) % 3)
             img.wait_for(c0)                            # (the last sequence's tails, frame 0's, read the image ring too)
             self._mark(img, k - 1, 'img_start')
@@ -823,12 +1010,16 @@ class FramePairPipeline(object):
             if la is not None:
                 prep(k, *la, ahead=True)
             return None
-        if (heads is None) != (self.rpn_head is not None):
-            raise ValueError('pass `heads` exactly when the pipeline has no head_params')
-        return self._step(prep, (d_points, n_points, d_image, ego_motion), heads, la, recover)
+        return self._step(prep, (d_points, n_points, d_image, ego_motion, g), heads, la, recover, [g, g])
 
-    def _upload_recover(self, recover):
-        """The step's recovery parameters for M (run()'s `recover`), into the slot of the step about to be enqueued."""
+    @staticmethod
+    def _mixed(geoms):
+        """The pairs of a step differ in calibration (M then takes one row per pair)."""
+        return any(x is not geoms[0] for x in geoms)
+
+    def _upload_recover(self, recover, geoms):
+        """The step's recovery parameters for M (run()'s `recover`), into the slot of the step about to be enqueued; with
+        them, when its pairs differ in calibration, M's 42 doubles per pair."""
         if recover is None:
             return
         if self.temporal is None:
@@ -838,6 +1029,8 @@ class FramePairPipeline(object):
         n = self.temporal['n_frames']
         # slot k % R was last read by M of step k - R, enqueued on `main` before this copy
         self.ego2[self.step_idx % len(self.rec2)].upload(np.stack([ops.temporal_ego(e, n) for e in recover]))
+        if self._mixed(geoms):      # (the same slot, the same ordering argument)
+            self.cal2[self.step_idx % len(self.rec2)].upload(np.stack([g.temporal_rows() for g in geoms[::self.fps]]))
 
     def _pending_tail(self):
         """Enqueue the tail of the step before the one just enqueued, then M and the tracker over its records."""
@@ -887,10 +1080,15 @@ class FramePairPipeline(object):
             return
         T, r, c = self.temporal, st.rslot, self.img_ctx
         self._mark(c, st.step, 'temporal_start')
+        # the recovery's calibration: the step's one, by value; pairs that differ in it (pairs_per_step > 1, samples of
+        # several videos) take one row each from the slot _upload_recover filled (dodt_interpolate_pairs_calibs)
+        if st.recover and self._mixed(st.geoms):
+            cal = dict(d_calibs=self.cal2[r])
+        else:
+            cal = dict(calib=st.geoms[0].temporal_rows() if st.recover else None)
         ops.interpolate_pairs(c, self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, T['n_frames'], T['threshold'],
                               T['on_conflict'], self.frames2[r], self.fcnt2[r], self.fst2[r],
-                              d_recover=self.ego2[r] if st.recover else None,
-                              calib=self.temporal_calib if st.recover else None, max_out=2 * MAX_DET)
+                              d_recover=self.ego2[r] if st.recover else None, max_out=2 * MAX_DET, **cal)
         self._mark(c, st.step, 'temporal_end')
         self.d_frames, self.d_frame_counts, self.d_frame_status = self.frames2[r], self.fcnt2[r], self.fst2[r]
 
@@ -903,7 +1101,8 @@ class FramePairPipeline(object):
             return
         r, c = st.rslot, self.img_ctx
         self._mark(c, st.step, 'tracker_start')
-        self.track_state.track_records(self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, self.p2, self.image_wh, ctx=c)
+        g = st.geoms[0]        # (one per sequence, _check_run / _push)
+        self.track_state.track_records(self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, g.p2, g.image_wh, ctx=c)
         self._mark(c, st.step, 'tracker_end')
 
     def _frame_ids(self, frame_ids):
@@ -932,6 +1131,7 @@ class FramePairPipeline(object):
             raise ValueError('end_sequence: the pipeline has no tracker')
         if self.pending is not None:
             raise ValueError('end_sequence: call finish() first (the last step is not tracked yet)')
+        self.track_geom = None         # (the next sequence may bring another calibration)
         if self.sequence:
             self.seq_primed, self.prepped = False, -1
             if self.tracker is None:
@@ -1065,6 +1265,7 @@ class FramePairPipeline(object):
     def _proposals(self, t, f):
         """Frame f up to its 7x7 crops: RPN crops, RPN head, decode, NMS #1, the kept proposals and their projections."""
         c, b, h, A, v = self.sides[f % len(self.sides)], t.fr[f], t.heads[f], t.counts[f], t.feat[f]
+        g = t.geoms[f]             # (of the step the tail belongs to, not of the call that enqueues it)
         bev_hw, img_hw, FC = (self.bev_fh, self.bev_fw), (self.img_fh, self.img_fw), self.feat_c
         self._mark(c, t.step, 'tail%d_start' % f)
         # -- a11: RPN crops (3x3 on the 1-channel bottlenecks) ------------------------
@@ -1083,19 +1284,19 @@ class FramePairPipeline(object):
                            b['regressed'], b['prop_bev'], b['scores'])
         else:
             ops.offset_to_anchor(c, b['anchors'], h['rpn_offsets'], A, None, b['regressed'])
-            ops.project_anchors_f32(c, b['regressed'], A, None, self.bev_extents_flat, self.p2,
-                                    self.image_wh, d_bev_norm_tf=b['prop_bev'])
+            ops.project_anchors_f32(c, b['regressed'], A, None, self.bev_extents_flat, g.p2,
+                                    g.image_wh, d_bev_norm_tf=b['prop_bev'])
             ops.softmax_fg(c, h['rpn_logits'], A, None, b['scores'])
         ops.nms(c, b['prop_bev'], b['scores'], A, None, self.P, self.cfg['rpn_nms_iou_thresh'], b['top_idx'], b['top_count'])
         if self.sched.fused_tail:
             ops.gather_project(c, b['regressed'], b['top_idx'], self.P, b['top_count'], self.bev_extents_flat,
-                               self.p2, self.image_wh, b['top_anchors'], b['top_bev'], b['top_img'])
+                               g.p2, g.image_wh, b['top_anchors'], b['top_bev'], b['top_img'])
             self._mark(c, t.step, 'tail%d_nms1' % f)
         else:
             ops.gather_rows(c, b['regressed'], 6, b['top_idx'], self.P, b['top_count'], b['top_anchors'])
             self._mark(c, t.step, 'tail%d_nms1' % f)
-            ops.project_anchors_f32(c, b['top_anchors'], self.P, b['top_count'], self.bev_extents_flat, self.p2,
-                                    self.image_wh, d_bev_norm_tf=b['top_bev'], d_img_norm_tf=b['top_img'])
+            ops.project_anchors_f32(c, b['top_anchors'], self.P, b['top_count'], self.bev_extents_flat, g.p2,
+                                    g.image_wh, d_bev_norm_tf=b['top_bev'], d_img_norm_tf=b['top_img'])
         ops.crop_and_resize(c, v['bev_feat'], bev_hw + (FC,), b['top_bev'], self.P, b['top_count'], (ROI, ROI),
                             b['bev_rois'])
         ops.crop_and_resize(c, v['img_feat'], img_hw + (FC,), b['top_img'], self.P, b['top_count'], (ROI, ROI),

@@ -695,6 +695,14 @@ int dodt_interpolate_pairs(dodt_ctx* ctx, const void* d_records, int records_f64
                            int n_pairs, int max_det, int n_frames, double threshold, int on_conflict,
                            const double* d_recover, const double* calib, int max_out, double* d_out,
                            int32_t* d_out_counts, int32_t* d_status);
+/* The same with one calibration per pair: d_calibs (n_pairs, 42) float64 on the device, row p the 42 doubles
+ * above for pair p (pairs of one launch that come from different videos).  Needs d_recover, the only reader of
+ * a calibration.  The same kernels and arithmetic: with equal rows the outputs are the bytes
+ * dodt_interpolate_pairs writes for that calibration; the rows are read when the launch runs. */
+int dodt_interpolate_pairs_calibs(dodt_ctx* ctx, const void* d_records, int records_f64, const int32_t* d_counts,
+                                  int n_pairs, int max_det, int n_frames, double threshold, int on_conflict,
+                                  const double* d_recover, const double* d_calibs, int max_out, double* d_out,
+                                  int32_t* d_out_counts, int32_t* d_status);
 
 /* ---- (g) the IoU tracker of the temporal module: detections -> tracks ------------------------
  * The reference's tracking evaluation turns each pair's records into KITTI label rows
