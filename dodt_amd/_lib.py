@@ -219,6 +219,9 @@ SIGNATURES = {
     'dodt_track_flush': (_i, [_vp, _vp, _d, _i]),
     'dodt_track_encode': (_i, [_vp, _vp, _i, _pi32, _i, _i, C.POINTER(_d), _d, _d, _d, _pf, _pf, _pi32]),
     'dodt_track_pairs': (_i, [_vp, _vp, _vp, _i, _pi32, _i, _i, C.POINTER(_d), _d, _d, _d, _d, _d, _i]),
+    'dodt_track_lanes_stride': (_i, [_i, C.POINTER(C.c_size_t)]),
+    'dodt_track_lanes': (_i, [_vp, _vp, C.c_size_t, _i, C.POINTER(C.c_ubyte), _vp, _i, _pi32, _i, C.POINTER(_d),
+                              C.POINTER(_d), _d, _d, _d, _i]),
     'dodt_track_encoded': (_i, [_vp, _vp, _pf, _pf, _pi32, _i, _i, _d, _d, _i]),
 }
 COMM_ID_BYTES = 128

@@ -14,6 +14,9 @@
 //                     tracker state.
 //   walk_kernel       one workgroup: the step's pairs in order -- merge, argmax over the free columns, finish or drop,
 //                     new tracks -- on the precomputed tables; the active list lives in LDS during the launch.
+// Lanes (dodt_track_lanes): pair i of a batch belongs to lane i, each lane with a state, a calibration and an image size
+// of its own -- the same three launches, the encode indexed by a by-value table of the lanes' calibrations, the tables
+// and the walk over per-lane views (a batch of ONE pair against the lane's own state), one walk workgroup per lane.
 // Float64 IoUs with the host's kitti-row permutation (ry <- z, l <-> h) and iou_3d of iou3d.h; float32 rows rounded to
 // 3 decimals exactly as numpy rounds (rint(x * 1000) / 1000 in float64).  Builds with -ffp-contract=off.
 #include "common.h"
@@ -153,10 +156,12 @@ __device__ bool kitti_row(const double* p, const P2& P, double iw, double ih, do
     return true;
 }
 
+// one workgroup encodes pair blockIdx.x under the calibration P and the image size iw x ih
 template <typename T>
-__global__ void __launch_bounds__(kThreads)
-encode_kernel(const T* __restrict__ records, const int32_t* __restrict__ counts, int max_det, P2 P, double iw,
-              double ih, double thr, float* __restrict__ trk, float* __restrict__ k1, int32_t* __restrict__ cnt) {
+__device__ __forceinline__ void encode_pair(const T* __restrict__ records, const int32_t* __restrict__ counts,
+                                            int max_det, const P2& P, double iw, double ih, double thr,
+                                            float* __restrict__ trk, float* __restrict__ k1,
+                                            int32_t* __restrict__ cnt) {
     __shared__ int wave_tot[kThreads / 64];
     const int pr = blockIdx.x, t = threadIdx.x;
     int n[3];
@@ -198,6 +203,34 @@ encode_kernel(const T* __restrict__ records, const int32_t* __restrict__ counts,
     }
 }
 
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+encode_kernel(const T* __restrict__ records, const int32_t* __restrict__ counts, int max_det, P2 P, double iw,
+              double ih, double thr, float* __restrict__ trk, float* __restrict__ k1, int32_t* __restrict__ cnt) {
+    encode_pair(records, counts, max_det, P, iw, ih, thr, trk, k1, cnt);
+}
+
+// The calibrations of a chunk of lanes, by value in the kernel arguments (kChunk * 112 = 1792 bytes): read before the
+// call returns like p2, no upload, no lifetime; the index is blockIdx.x, uniform over the workgroup.
+struct LaneCal {
+    P2 P;
+    double iw, ih;
+};
+struct LaneTable {
+    LaneCal c[kChunk];
+};
+__device__ bool lane_on(unsigned mask, int lane) { return (mask >> lane) & 1u; }
+
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+encode_lanes_kernel(const T* __restrict__ records, const int32_t* __restrict__ counts, int max_det, LaneTable tab,
+                    unsigned mask, double thr, float* __restrict__ trk, float* __restrict__ k1,
+                    int32_t* __restrict__ cnt) {
+    if (!lane_on(mask, blockIdx.x)) return;
+    const LaneCal& cal = tab.c[blockIdx.x];
+    encode_pair(records, counts, max_det, cal.P, cal.iw, cal.ih, thr, trk, k1, cnt);
+}
+
 __device__ bool skipped(const Lists& ls, int p) { return ls.cnt_stride > 2 && ls.cnt[(size_t)p * ls.cnt_stride + 2]; }
 __device__ int n_trk(const Lists& ls, int p) { return min(max(ls.cnt[(size_t)p * ls.cnt_stride], 0), ls.rows); }
 __device__ int n_k1(const Lists& ls, int p) { return min(max(ls.cnt[(size_t)p * ls.cnt_stride + 1], 0), ls.rows); }
@@ -232,11 +265,17 @@ __device__ const float* col_box(const Lists& ls, int p, int nt, const K1Src& src
     return c < nt ? ls.trk + ((size_t)p * ls.rows + c) * kTrk + 8 : src.rows + (size_t)(c - nt) * kK1 + 8;
 }
 
-// T(p) (kCols x kCols) and S(p) (kRows x kCols) of every pair of the batch; grid (kCols + kRows, n_pairs).
-__global__ void __launch_bounds__(kThreads)
-iou_tables_kernel(Lists ls, const Header* __restrict__ hdr_p, const float* __restrict__ prev_off,
-                  const float* __restrict__ prev_k1, double* __restrict__ T, double* __restrict__ S) {
-    const int p = blockIdx.y;
+// lane i's pair as a batch of its own: the lists from pair i on
+__device__ Lists lane_lists(const Lists& ls, int i) {
+    return {ls.trk + (size_t)i * ls.rows * kTrk, ls.k1 + (size_t)i * ls.rows * kK1, ls.cnt + (size_t)i * ls.cnt_stride,
+            ls.cnt_stride, ls.rows};
+}
+
+// workgroup blockIdx.x's share of T(p) and S(p) of pair p of the batch `ls`
+__device__ __forceinline__ void iou_tables_pair(const Lists& ls, int p, const Header* __restrict__ hdr_p,
+                                                const float* __restrict__ prev_off,
+                                                const float* __restrict__ prev_k1, double* __restrict__ T,
+                                                double* __restrict__ S) {
     if (skipped(ls, p)) return;
     const Header h = *hdr_p;
     const int nt = n_trk(ls, p);
@@ -268,6 +307,26 @@ iou_tables_kernel(Lists ls, const Header* __restrict__ hdr_p, const float* __res
         kitti_box(col_box(ls, p, nt, src, c), b);
         S[((size_t)p * kRows + i) * kCols + c] = iou_3d(a, b);
     }
+}
+
+// T(p) (kCols x kCols) and S(p) (kRows x kCols) of every pair of the batch; grid (kCols + kRows, n_pairs).
+__global__ void __launch_bounds__(kThreads)
+iou_tables_kernel(Lists ls, const Header* __restrict__ hdr_p, const float* __restrict__ prev_off,
+                  const float* __restrict__ prev_k1, double* __restrict__ T, double* __restrict__ S) {
+    iou_tables_pair(ls, blockIdx.y, hdr_p, prev_off, prev_k1, T, S);
+}
+
+// Lanes: grid (kCols + kRows, lanes); lane blockIdx.y is a batch of one pair against its OWN state (no pair of the
+// batch precedes it: k1_source / pred_of always end at the state), its tables in slice blockIdx.y of T and S.
+__global__ void __launch_bounds__(kThreads)
+iou_tables_lanes_kernel(Lists ls, unsigned mask, const char* __restrict__ states, size_t stride,
+                        double* __restrict__ T, double* __restrict__ S) {
+    const int i = blockIdx.y;
+    if (!lane_on(mask, i)) return;
+    const char* b = states + (size_t)i * stride;
+    iou_tables_pair(lane_lists(ls, i), 0, reinterpret_cast<const Header*>(b),
+                    reinterpret_cast<const float*>(b + kPrevOffOff), reinterpret_cast<const float*>(b + kPrevK1Off),
+                    T + (size_t)i * kCols * kCols, S + (size_t)i * kRows * kCols);
 }
 
 // np.argmax order: a NaN beats everything (the first NaN wins), otherwise the larger value, the first index on ties
@@ -317,12 +376,14 @@ __device__ void write_log(LogEntry* log, int idx, int slot, const Item& it, int 
         e->pair = it.pair;
         e->kf = it.kf;
         e->row = it.idx;
+        e->pad = 0;         // (as a new track's entry: the log's bytes depend on the pairs alone, not on the buffer's past)
     }
 }
 
-__global__ void __launch_bounds__(kThreads)
-walk_kernel(Lists ls, int n_pairs, void* state, const double* __restrict__ T, const double* __restrict__ S,
-            double iou_thr, float high, int t_min) {
+// The walk of one workgroup: the n_pairs pairs of `ls` in order on `state`, with their tables T and S.  The one body
+// of walk_kernel (a batch of one sequence) and walk_lanes_kernel (per workgroup a lane's view: one pair, its state).
+__device__ __forceinline__ void walk_pairs(const Lists& ls, int n_pairs, void* state, const double* __restrict__ T,
+                                           const double* __restrict__ S, double iou_thr, float high, int t_min) {
     __shared__ Active act[2][kCols];
     __shared__ int detL[kCols], colL[kCols], best_c[kCols];
     __shared__ double best_v[kCols];
@@ -549,6 +610,22 @@ walk_kernel(Lists ls, int n_pairs, void* state, const double* __restrict__ T, co
     }
 }
 
+__global__ void __launch_bounds__(kThreads)
+walk_kernel(Lists ls, int n_pairs, void* state, const double* __restrict__ T, const double* __restrict__ S,
+            double iou_thr, float high, int t_min) {
+    walk_pairs(ls, n_pairs, state, T, S, iou_thr, high, t_min);
+}
+
+// Lanes: grid = lanes, one workgroup per lane; an inactive lane's workgroup leaves at once (the mask is uniform).
+__global__ void __launch_bounds__(kThreads)
+walk_lanes_kernel(Lists ls, unsigned mask, char* states, size_t stride, const double* __restrict__ T,
+                  const double* __restrict__ S, double iou_thr, float high, int t_min) {
+    const int i = blockIdx.x;
+    if (!lane_on(mask, i)) return;
+    walk_pairs(lane_lists(ls, i), 1, states + (size_t)i * stride, T + (size_t)i * kCols * kCols,
+               S + (size_t)i * kRows * kCols, iou_thr, high, t_min);
+}
+
 // finish the remaining active tracks, in order; the active list is emptied
 __global__ void __launch_bounds__(kThreads) flush_kernel(void* state, float high, int t_min) {
     __shared__ int wave_tot[kThreads / 64];
@@ -671,6 +748,65 @@ extern "C" int dodt_track_pairs(dodt_ctx* ctx, void* d_state, const void* d_reco
         if (rc != DODT_OK) return rc;
         rc = walk(ctx, d_state, Lists{trk, k1, cnt, kCnt, kRows}, n, high_threshold, iou_threshold, t_min);
         if (rc != DODT_OK) return rc;
+    }
+    return DODT_OK;
+}
+
+extern "C" int dodt_track_lanes_stride(int log_capacity, size_t* stride) {
+    DODT_REQUIRE(log_capacity >= 1 && stride, "dodt_track_lanes_stride: bad arguments");
+    *stride = (state_bytes(log_capacity) + 255) / 256 * 256;
+    return DODT_OK;
+}
+
+extern "C" int dodt_track_lanes(dodt_ctx* ctx, void* d_states, size_t stride, int n_lanes,
+                                const unsigned char* active, const void* d_records, int records_f64,
+                                const int32_t* d_counts, int max_det, const double* p2s, const double* image_whs,
+                                double score_threshold, double high_threshold, double iou_threshold, int t_min) {
+    DODT_REQUIRE(ctx && d_states && n_lanes >= 0, "dodt_track_lanes: bad arguments");
+    if (n_lanes == 0) return DODT_OK;
+    DODT_REQUIRE(d_records && d_counts && p2s && image_whs, "dodt_track_lanes: NULL argument");
+    DODT_REQUIRE(max_det >= 1 && max_det <= kRows, "dodt_track_lanes: max_det %d outside 1..%d", max_det, kRows);
+    DODT_REQUIRE(stride >= state_bytes(1) && stride % alignof(Header) == 0,
+                 "dodt_track_lanes: stride %zu is no distance between two states", stride);
+    const size_t enc_bytes = (size_t)kChunk * kRows * (kTrk + kK1) * sizeof(float) + kChunk * kCnt * sizeof(int32_t);
+    if (ctx->tracking_enc.reserve(enc_bytes) != DODT_OK) return DODT_ERR_HIP;
+    if (ctx->tracking_ws.reserve((size_t)kChunk * (kCols + kRows) * kCols * sizeof(double)) != DODT_OK)
+        return DODT_ERR_HIP;
+    float* trk = static_cast<float*>(ctx->tracking_enc.ptr);
+    float* k1 = trk + (size_t)kChunk * kRows * kTrk;
+    int32_t* cnt = reinterpret_cast<int32_t*>(k1 + (size_t)kChunk * kRows * kK1);
+    double* T = static_cast<double*>(ctx->tracking_ws.ptr);
+    double* S = T + (size_t)kChunk * kCols * kCols;
+    const Lists ls{trk, k1, cnt, kCnt, kRows};
+    const size_t rec_bytes = records_f64 ? sizeof(double) : sizeof(float);
+    for (int l0 = 0; l0 < n_lanes; l0 += kChunk) {
+        const int n = n_lanes - l0 < kChunk ? n_lanes - l0 : kChunk;
+        LaneTable tab{};
+        unsigned mask = 0;
+        for (int i = 0; i < n; ++i) {
+            memcpy(tab.c[i].P.p, p2s + (size_t)(l0 + i) * 12, sizeof(tab.c[i].P.p));
+            tab.c[i].iw = image_whs[2 * (l0 + i)];
+            tab.c[i].ih = image_whs[2 * (l0 + i) + 1];
+            if (!active || active[l0 + i]) mask |= 1u << i;
+        }
+        if (!mask) continue;
+        const char* rec = static_cast<const char*>(d_records) + (size_t)l0 * 2 * max_det * kRecCols * rec_bytes;
+        char* states = static_cast<char*>(d_states) + (size_t)l0 * stride;
+        if (records_f64)
+            hipLaunchKernelGGL(encode_lanes_kernel<double>, dim3(n), dim3(kThreads), 0, ctx->stream,
+                               reinterpret_cast<const double*>(rec), d_counts + 2 * l0, max_det, tab, mask,
+                               score_threshold, trk, k1, cnt);
+        else
+            hipLaunchKernelGGL(encode_lanes_kernel<float>, dim3(n), dim3(kThreads), 0, ctx->stream,
+                               reinterpret_cast<const float*>(rec), d_counts + 2 * l0, max_det, tab, mask,
+                               score_threshold, trk, k1, cnt);
+        DODT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(iou_tables_lanes_kernel, dim3(kCols + kRows, n), dim3(kThreads), 0, ctx->stream, ls, mask,
+                           static_cast<const char*>(states), stride, T, S);
+        DODT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(walk_lanes_kernel, dim3(n), dim3(kThreads), 0, ctx->stream, ls, mask, states, stride, T, S,
+                           iou_threshold, (float)high_threshold, t_min);
+        DODT_LAUNCH_CHECK();
     }
     return DODT_OK;
 }

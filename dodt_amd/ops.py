@@ -562,6 +562,35 @@ def track_pairs(ctx, d_state, d_records, d_counts, n_pairs, max_det, p2, image_w
         'dodt_track_pairs')
 
 
+def track_lanes_stride(log_capacity):
+    """Bytes between two lanes' states in one buffer (dodt_track_lanes_stride)."""
+    n = C.c_size_t()
+    _lib.check(_lib.load().dodt_track_lanes_stride(int(log_capacity), C.byref(n)), 'dodt_track_lanes_stride')
+    return int(n.value)
+
+
+def track_lanes(ctx, d_states, stride, n_lanes, d_records, d_counts, max_det, p2s, image_whs, score_threshold,
+                high_threshold, iou_threshold, t_min, active=None):
+    """One pair per lane, lane i on the state at d_states + i * stride with its own p2s[i] (3, 4) and image_whs[i]
+    (w, h) (dodt_track_lanes): d_records (n_lanes, 2, max_det, 17), d_counts (n_lanes, 2); active: None, or one
+    truth value per lane (a lane that is not active keeps its state untouched)."""
+    if d_records.dtype not in (np.float32, np.float64):
+        raise ValueError('records must be float32 or float64')
+    n_lanes = int(n_lanes)
+    p2s, whs = np.asarray(p2s, np.float64).reshape(-1), np.asarray(image_whs, np.float64).reshape(-1)
+    if len(p2s) != 12 * n_lanes or len(whs) != 2 * n_lanes:
+        raise ValueError('track_lanes: one p2 (3, 4) and one image_wh per lane')
+    act = None
+    if active is not None:
+        if len(active) != n_lanes:
+            raise ValueError('track_lanes: active has %d entries for %d lanes' % (len(active), n_lanes))
+        act = (C.c_ubyte * n_lanes)(*[1 if a else 0 for a in active])
+    _lib.check(ctx.lib.dodt_track_lanes(
+        ctx.handle, _p(d_states), int(stride), n_lanes, act, _p(d_records), int(d_records.dtype == np.float64),
+        _p(d_counts), int(max_det), _arr(C.c_double, p2s), _arr(C.c_double, whs), float(score_threshold),
+        float(high_threshold), float(iou_threshold), int(t_min)), 'dodt_track_lanes')
+
+
 def track_encoded(ctx, d_state, d_track, d_ious, d_counts, n_pairs, max_rows, high_threshold, iou_threshold, t_min):
     """Track n_pairs already encoded pairs (dodt_track_encoded): d_track (n_pairs, max_rows, 23), d_ious (n_pairs,
     max_rows, 16) float32, d_counts (n_pairs, 2) int32."""

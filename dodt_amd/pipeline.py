@@ -154,7 +154,8 @@ def resolve_schedule(environ, computed_heads, frames_per_sample, n_side_streams)
 # what its prep left), feature-map views and kept-anchor count, resolves `heads` to those buffers when the pipeline
 # computes them, and adds the side streams' head scratch
 # `geoms`: the geometry (_Geometry) of every frame of the step, as its prep used it
-_Step = namedtuple('_Step', 'step cur rslot heads recover geoms fr feat counts scratch', defaults=(None,) * 4)
+# `active`: None, or per tracker lane whether the step's pair belongs to that lane's video (tracker=dict(lanes=True))
+_Step = namedtuple('_Step', 'step cur rslot heads recover geoms fr feat counts scratch active', defaults=(None,) * 5)
 
 
 def _pad_lookahead(lookahead):
@@ -234,7 +235,9 @@ class FramePairPipeline(object):
         tracker: None, or dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3,
         classes=cfg['classes'], max_sequence_dets=65536) -- the IoU tracker on the device after every step: the pairs of
         the steps, in order, are one sequence until end_sequence() (see _tracker_step, tracks_so_far()); None enqueues and allocates nothing
-        for it.
+        for it.  With lanes=True pair p of every step belongs to LANE p instead: pairs_per_step (at most 5, the
+        pipeline's limit) videos side by side, each lane with its own tracker state, calibration and
+        end_sequence(lane=) (run()'s `active`); needs sequence=False.
         bev_input_skip: the fp32 BEV net skips the tiles that no BEV cell inside the camera's frustum reaches (their
         values depend on the weights alone, dodt_extractor_set_input_support); False: full tables.
         bev_frame_tables: with bev_input_skip, every step also filters those tables on the device by the cells that are
@@ -294,6 +297,8 @@ class FramePairPipeline(object):
         if self.image_wh_max[0] < self.image_wh[0] or self.image_wh_max[1] < self.image_wh[1]:
             raise ValueError('image_wh_max is smaller than image_wh')
         self.track_geom = None         # the geometry of the tracker's current sequence (None: none has begun)
+        self.lanes = self.tracker is not None and self.tracker['lanes']
+        self.track_geoms = [None] * self.pairs      # (lanes: the same per lane)
         # streams: conv stacks of the two nets side by side, per-frame work on its own.  A second pipeline in the same
         # process takes the first one's streams (`reuse_streams_of`): new ones would share hardware queues with them
         if reuse_streams_of is not None:
@@ -485,10 +490,15 @@ class FramePairPipeline(object):
         # ---- the IoU tracker (opt-in): one sequence's state on the device, launches on the image stream ------------
         if self.tracker is not None:
             tk = self.tracker
-            self.track_state = tracking.Tracker(self.ctx, tk['max_sequence_dets'], tk['high_threshold'],
-                                                tk['iou_threshold'], tk['t_min'], tk['score_threshold'])
+            if self.lanes:     # one state per pair of a step, in one buffer
+                self.track_state = tracking.TrackerLanes(self.ctx, self.pairs, tk['max_sequence_dets'],
+                                                         tk['high_threshold'], tk['iou_threshold'], tk['t_min'],
+                                                         tk['score_threshold'])
+            else:
+                self.track_state = tracking.Tracker(self.ctx, tk['max_sequence_dets'], tk['high_threshold'],
+                                                    tk['iou_threshold'], tk['t_min'], tk['score_threshold'])
             self.img_ctx.wait_for(self.ctx)          # (the state's reset went on the main stream)
-            self.last_sequence_tracks = None
+            self.last_sequence_tracks = [None] * self.pairs if self.lanes else None
         self.mark_steps = ()           # tools/pipe_marks.py: steps whose stages get timing marks
         self.marks = {}                # name -> (context, slot)
         ctx.sync()
@@ -518,9 +528,12 @@ class FramePairPipeline(object):
         tk = dict(score_threshold=float(t.pop('score_threshold', 0.1)),
                   high_threshold=float(t.pop('high_threshold', 0.5)),
                   iou_threshold=float(t.pop('iou_threshold', 0.005)), t_min=int(t.pop('t_min', 3)),
-                  classes=tuple(t.pop('classes', self.classes)), max_sequence_dets=int(t.pop('max_sequence_dets', 65536)))
+                  classes=tuple(t.pop('classes', self.classes)), max_sequence_dets=int(t.pop('max_sequence_dets', 65536)),
+                  lanes=bool(t.pop('lanes', False)))
         if t:
             raise ValueError('tracker: unknown keys %s' % sorted(t))
+        if tk['lanes'] and self.sequence:
+            raise ValueError('tracker: lanes need sequence=False (one lane per pair of a step)')
         if tk['max_sequence_dets'] < 1:
             raise ValueError('tracker: max_sequence_dets must be >= 1')
         return tk
@@ -692,7 +705,8 @@ class FramePairPipeline(object):
             d_imgs.append(self._stage_image(c, di, h_images[f], geoms[f]))
         return d_pts, d_imgs
 
-    def run_from_host(self, h_points, n_points, h_images, heads=None, ego_motion=None, lookahead=None, calib=None):
+    def run_from_host(self, h_points, n_points, h_images, heads=None, ego_motion=None, lookahead=None, calib=None,
+                      active=None):
         """run() for raw frames still in (page-locked) host memory: lists of PinnedArray --
         points (n_max,4) float32 of which n_points[f] rows are valid, images (H,W,3) uint8.
         The copies are enqueued on each frame's side stream in front of its prep kernels, so
@@ -702,7 +716,7 @@ class FramePairPipeline(object):
         if self.sequence:
             raise ValueError('run_from_host: a sequence pipeline takes push_frame_from_host()')
         la = _pad_lookahead(lookahead)
-        geoms, la_geoms = self._check_run(h_images, heads, la, calib, host=True)
+        geoms, la_geoms, active = self._check_run(h_images, heads, la, calib, host=True, active=active)
         if self.prepped == self.step_idx:       # staged and prepared by the previous call's look-ahead
             d_pts = d_imgs = None
         else:
@@ -711,7 +725,7 @@ class FramePairPipeline(object):
             # (the copies of step k + 1 go behind what its side streams hold now, i.e. behind step k's prep)
             nd_pts, nd_imgs = self._stage_from_host(self.step_idx + 1, la[0], la[1], la[2], la_geoms)
             la = (nd_pts, la[1], nd_imgs, la[3], la_geoms)
-        return self._step(self._prep, (d_pts, n_points, d_imgs, ego_motion, geoms), heads, la, None, geoms)
+        return self._step(self._prep, (d_pts, n_points, d_imgs, ego_motion, geoms), heads, la, None, geoms, active)
 
     def _prep(self, k, d_points, n_points, d_images, ego_motion, geoms, ahead):
         """a0-a7 of step k: the data side of the reference's create_feed_dict, one frame per side stream; its end
@@ -761,7 +775,8 @@ class FramePairPipeline(object):
         ops.img_preprocess(c, d_image, (g.image_wh[1], g.image_wh[0]), (self.img_h, self.img_w), 4,
                            (self.img_net._R_MEAN, self.img_net._G_MEAN, self.img_net._B_MEAN), d_img)
 
-    def run(self, d_points, n_points, d_images, heads=None, ego_motion=None, lookahead=None, recover=None, calib=None):
+    def run(self, d_points, n_points, d_images, heads=None, ego_motion=None, lookahead=None, recover=None, calib=None,
+            active=None):
         """Enqueue one step.  Lists of length 2 * pairs_per_step, frame order
         [pair0 f0, pair0 f1, pair1 f0, ...]: d_points[f] (n,4) float32 velodyne xyzi;
         d_images[f] (H,W,3) uint8; heads[f] dict of device arrays rpn_logits (N,2),
@@ -786,6 +801,11 @@ class FramePairPipeline(object):
         M and the tracker all take it, whatever the calls in between bring.  A step announced by a look-ahead must come
         with an equal calibration; with a tracker it changes only behind end_sequence().  Everything refused here is
         refused before anything is enqueued.
+        active (pipelines built with tracker=dict(lanes=True) only): None -- every lane --, or one truth value per pair of
+        the step: whether the pair belongs to its lane's video.  An idle lane's slot is computed like any other (records,
+        M; fill it with any valid frames, such as that lane's previous pair), but its tracker state stays untouched and its
+        pair numbering does not advance.  The pairs of a step may differ in calibration; lane i's changes only on its first
+        active step after construction or end_sequence(lane=i).
         Returns the parity (0/1) of the record buffers this step will fill.  The
         detections of the PREVIOUS step are complete on the main stream when this returns
         (self.d_records / self.fr / self.last_anchor_counts then describe that step);
@@ -793,14 +813,16 @@ class FramePairPipeline(object):
         if self.sequence:
             raise ValueError('run: a sequence pipeline takes push_frame()')
         la = _pad_lookahead(lookahead)
-        geoms, la_geoms = self._check_run(d_images, heads, la, calib, host=False)
+        geoms, la_geoms, active = self._check_run(d_images, heads, la, calib, host=False, active=active)
         if la is not None:
             la = la[:4] + (la_geoms,)
-        return self._step(self._prep, (d_points, n_points, d_images, ego_motion, geoms), heads, la, recover, geoms)
+        return self._step(self._prep, (d_points, n_points, d_images, ego_motion, geoms), heads, la, recover, geoms,
+                          active)
 
-    def _check_run(self, images, heads, la, calib, host):
+    def _check_run(self, images, heads, la, calib, host, active=None):
         """What run() / run_from_host() refuse, before anything is enqueued.  -> the frames' geometries of this step and
-        of the look-ahead's (None without one)."""
+        of the look-ahead's (None without one), and the step's `active` as the step record takes it (lanes: a tuple of
+        bool, one per lane; None otherwise)."""
         if (heads is None) != (self.rpn_head is not None):
             raise ValueError('pass `heads` exactly when the pipeline has no head_params')
         geoms = self._step_geoms(calib)
@@ -812,22 +834,37 @@ class FramePairPipeline(object):
             self._check_images(images, geoms, host)
         if la is not None:
             self._check_images(la[2], la_geoms, host)
-        if self.tracker is not None:
+        if active is not None and not self.lanes:
+            raise ValueError('active: needs a pipeline built with tracker=dict(lanes=True)')
+        if self.lanes:
+            # (pair p of every step is lane p's: one video, one calibration per LANE until end_sequence(lane=p); an idle
+            #  lane's slot may hold anything)
+            active = (True,) * self.pairs if active is None else tuple(bool(a) for a in active)
+            if len(active) != self.pairs:
+                raise ValueError('active: one entry per lane (%d), not %d' % (self.pairs, len(active)))
+            for i, on in enumerate(active):
+                if on and self.track_geoms[i] not in (None, geoms[self.fps * i]):
+                    raise ValueError('calib: lane %d\'s calibration changes only behind end_sequence(lane=%d)' % (i, i))
+        elif self.tracker is not None:
             # (the pairs of the steps, in order, are ONE sequence until end_sequence(): one video, one calibration.  A
             #  look-ahead may already belong to the next sequence: it is checked when its step comes)
             if any(g is not geoms[0] for g in geoms) or self.track_geom not in (None, geoms[0]):
                 raise ValueError('calib: with a tracker the calibration changes only behind end_sequence()')
-        return geoms, la_geoms
+        return geoms, la_geoms, active
 
-    def _step(self, prep, inputs, heads, lookahead, recover, geoms):
+    def _step(self, prep, inputs, heads, lookahead, recover, geoms, active=None):
         """The step body of run() and push_frame(): `prep`(k, points, n_points, image(s), ego_motion, geometry, ahead=)
         is the mode's prep (_prep, _seq_prep), `inputs` and the padded `lookahead` its arguments for this step and the
         next; `geoms` the geometry of every frame of this step (what its prep takes or, enqueued a call ago, took), which
-        the step's record carries to its tail, M and the tracker."""
+        the step's record carries to its tail, M and the tracker, like `active` (lanes)."""
         main, img = self.ctx, self.img_ctx
         self._resolve_t_branch()
         self._upload_recover(recover, geoms)
-        if self.tracker is not None:
+        if self.lanes:
+            for i, on in enumerate(active):
+                if on:
+                    self.track_geoms[i] = geoms[self.fps * i]
+        elif self.tracker is not None:
             self.track_geom = geoms[0]
         k = self.step_idx
         cur = k & 1
@@ -864,14 +901,14 @@ class FramePairPipeline(object):
             prep(k + 1, *lookahead, ahead=True)
         # -- the previous step's tail runs under this step's convs --------------------------
         self._pending_tail()
-        self.pending = self._step_record(k, heads, recover is not None, geoms)
+        self.pending = self._step_record(k, heads, recover is not None, geoms, active)
         self.step_idx += 1
         return cur
 
-    def _step_record(self, k, heads=None, recover=False, geoms=None):
+    def _step_record(self, k, heads=None, recover=False, geoms=None, active=None):
         """The record of step k as the call that enqueues it leaves it in `pending` (_Step)."""
         return _Step(step=k, cur=k & 1, rslot=k % len(self.rec2), heads=heads, recover=recover,
-                     geoms=[self.geom0] * self.nf if geoms is None else geoms)
+                     geoms=[self.geom0] * self.nf if geoms is None else geoms, active=active)
 
     def _image_forward(self, k):
         """The image stack of step k on the image stream: over every frame of the step into feat[k & 1]; in sequence
@@ -1101,6 +1138,14 @@ class FramePairPipeline(object):
             return
         r, c = st.rslot, self.img_ctx
         self._mark(c, st.step, 'tracker_start')
+        if self.lanes:
+            # every lane's pair in one launch triple: lane i under the calibration the step brought for pair i, the idle
+            # lanes of the step left as they are
+            gs = st.geoms[::self.fps]
+            self.track_state.track_records(self.rec2[r], self.cnt2[r], MAX_DET, [g.p2 for g in gs],
+                                           [g.image_wh for g in gs], active=st.active, ctx=c)
+            self._mark(c, st.step, 'tracker_end')
+            return
         g = st.geoms[0]        # (one per sequence, _check_run / _push)
         self.track_state.track_records(self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, g.p2, g.image_wh, ctx=c)
         self._mark(c, st.step, 'tracker_end')
@@ -1112,23 +1157,50 @@ class FramePairPipeline(object):
         tau = self.temporal['n_frames'] - 1 if self.temporal is not None else 1
         return lambda pair, kf: pair * tau + kf * tau
 
-    def tracks_so_far(self, frame_ids=None):
+    def _lane(self, lane, what):
+        """The Tracker a per-sequence method works on: the pipeline's one, or lane `lane` of a lanes pipeline."""
+        if self.tracker is None:
+            raise ValueError('%s: the pipeline has no tracker' % what)
+        if not self.lanes:
+            if lane is not None:
+                raise ValueError('%s: lane= needs a pipeline built with tracker=dict(lanes=True)' % what)
+            return self.track_state
+        if lane is None or isinstance(lane, bool) or not 0 <= int(lane) < self.pairs:
+            raise ValueError('%s: a lanes pipeline needs lane=0..%d' % (what, self.pairs - 1))
+        return self.track_state.lane(int(lane))
+
+    def tracks_so_far(self, frame_ids=None, lane=None):
         """The tracks the device has finished so far in this sequence, up to the last step whose tail has been enqueued
         (every step after finish()), downloaded: the host's track dicts (dt_evaluator_utils.track_through_ious on
         encode_tracking_dets of the same records).  frame_ids: None -- pair j of the sequence is frames (j * tau,
-        j * tau + tau), tau = n_frames - 1 of `temporal` or 1 --, or one (frame_0, frame_1) per pair."""
-        if self.tracker is None:
-            raise ValueError('tracks_so_far: the pipeline has no tracker')
+        j * tau + tau), tau = n_frames - 1 of `temporal` or 1 --, or one (frame_0, frame_1) per pair.  lane: which lane's
+        sequence (lanes pipelines, where a pair's number counts the lane's own active steps)."""
+        state = self._lane(lane, 'tracks_so_far')
         self.ctx.wait_for(self.img_ctx)             # (the downloads go through the main stream)
-        return tracking.tracks_from_log(self.track_state.read(), self._frame_ids(frame_ids), self.tracker['classes'])
+        return tracking.tracks_from_log(state.read(), self._frame_ids(frame_ids), self.tracker['classes'])
 
-    def end_sequence(self, frame_ids=None):
+    def end_sequence(self, frame_ids=None, lane=None):
         """End the sequence after finish(): finish the remaining active tracks, download, and start a new sequence.
         Returns the host function's tracks_finished (kept as last_sequence_tracks for kitti_tracking_rows()).
         Sequence mode: the next push_frame() primes again, and a look-ahead that no push followed is dropped; without a
-        tracker that is all (returns None)."""
+        tracker that is all (returns None).  Lanes: ends lane `lane`'s sequence alone -- its state is flushed, downloaded
+        and reset, the other lanes go on --, kept as last_sequence_tracks[lane]; finish() first all the same, so ending one
+        video drains the pipeline once."""
         if self.tracker is None and not self.sequence:
             raise ValueError('end_sequence: the pipeline has no tracker')
+        if self.lanes:
+            state = self._lane(lane, 'end_sequence')
+            if self.pending is not None:
+                raise ValueError('end_sequence: call finish() first (the last step is not tracked yet)')
+            lane = int(lane)
+            self.track_geoms[lane] = None           # (the lane's next video may bring another calibration)
+            state.flush(ctx=self.img_ctx)
+            tracks = self.tracks_so_far(frame_ids, lane=lane)
+            state.reset(ctx=self.img_ctx)
+            self.last_sequence_tracks[lane] = tracks
+            return tracks
+        if lane is not None:
+            raise ValueError('end_sequence: lane= needs a pipeline built with tracker=dict(lanes=True)')
         if self.pending is not None:
             raise ValueError('end_sequence: call finish() first (the last step is not tracked yet)')
         self.track_geom = None         # (the next sequence may bring another calibration)
@@ -1142,14 +1214,18 @@ class FramePairPipeline(object):
         self.last_sequence_tracks = tracks
         return tracks
 
-    def kitti_tracking_rows(self, tracks=None):
-        """convert_trajectory_to_kitti_format of `tracks` (default: the last sequence end_sequence() returned): the
-        reference's KITTI tracking rows, as strings."""
+    def kitti_tracking_rows(self, tracks=None, lane=None):
+        """convert_trajectory_to_kitti_format of `tracks` (default: the last sequence end_sequence() returned, on a lanes
+        pipeline the last one of lane `lane`): the reference's KITTI tracking rows, as strings."""
         from dodt_amd.core.dt_evaluator_utils import convert_trajectory_to_kitti_format
         if tracks is None:
-            if self.tracker is None or self.last_sequence_tracks is None:
+            if self.lanes:
+                self._lane(lane, 'kitti_tracking_rows')
+                tracks = self.last_sequence_tracks[int(lane)]
+            else:
+                tracks = None if self.tracker is None else self.last_sequence_tracks
+            if tracks is None:
                 raise ValueError('kitti_tracking_rows: no sequence has ended')
-            tracks = self.last_sequence_tracks
         return convert_trajectory_to_kitti_format(tracks)           # (a track's type is its name in cfg['classes'])
 
     def frames(self):

@@ -25,10 +25,12 @@ _FIN_WORDS, _LOG_WORDS = 4, 28
 class Tracker(object):
     """One sequence's tracker state on the device (track_through_ious' tracks_active / tracks_finished, and a log
     of every detection that entered a track).  log_capacity bounds the log and the finished list; running past it
-    raises when the tracks are read.  Every launch goes on `ctx` (default: the state's context)."""
+    raises when the tracks are read.  Every launch goes on `ctx` (default: the state's context).  d_state: None -- the
+    tracker allocates its state --, or a view of ops.track_state_bytes(log_capacity) bytes that holds it (a lane of
+    TrackerLanes)."""
 
     def __init__(self, ctx=None, log_capacity=65536, high_threshold=0.5, iou_threshold=0.005, t_min=3,
-                 score_threshold=0.1):
+                 score_threshold=0.1, d_state=None):
         self.ctx = ctx or device.default_context()
         self.cap = int(log_capacity)
         if self.cap < 1:
@@ -37,7 +39,9 @@ class Tracker(object):
         self.score_threshold = float(score_threshold)
         nbytes = ops.track_state_bytes(self.cap)
         assert nbytes == _FIN_OFF + self.cap * 4 * (_FIN_WORDS + _LOG_WORDS), 'state layout'
-        self.d_state = self.ctx.empty((nbytes,), np.uint8)
+        if d_state is not None and d_state.nbytes < nbytes:
+            raise ValueError('d_state: %d bytes, the state needs %d' % (d_state.nbytes, nbytes))
+        self.d_state = self.ctx.empty((nbytes,), np.uint8) if d_state is None else d_state
         self.reset()
 
     def reset(self, ctx=None):
@@ -84,6 +88,39 @@ class Tracker(object):
                 raise RuntimeError('tracker: track %d has %d log entries, length %d' % (slot, len(rows), length))
             out.append((int(start), np.array(score_bits, np.int32).view(np.float32)[()], rows))
         return out
+
+
+class TrackerLanes(object):
+    """n_lanes tracker states in ONE device buffer, ops.track_lanes_stride(log_capacity) bytes apart: pair i of a step
+    belongs to lane i (one video or camera each), and every lane advances in one launch triple (dodt_track_lanes).
+    lane(i) is a Tracker over lane i's slice: reset / flush / header / read as on a state of its own."""
+
+    def __init__(self, ctx=None, n_lanes=1, log_capacity=65536, high_threshold=0.5, iou_threshold=0.005, t_min=3,
+                 score_threshold=0.1):
+        self.ctx = ctx or device.default_context()
+        self.n_lanes, self.cap = int(n_lanes), int(log_capacity)
+        if self.n_lanes < 1:
+            raise ValueError('n_lanes must be >= 1')
+        if self.cap < 1:
+            raise ValueError('log_capacity must be >= 1')
+        self.high, self.iou, self.t_min = float(high_threshold), float(iou_threshold), int(t_min)
+        self.score_threshold = float(score_threshold)
+        self.stride = ops.track_lanes_stride(self.cap)
+        nbytes = ops.track_state_bytes(self.cap)
+        self.d_states = self.ctx.empty((self.n_lanes * self.stride,), np.uint8)
+        self.lanes = [Tracker(self.ctx, self.cap, self.high, self.iou, self.t_min, self.score_threshold,
+                              d_state=self.d_states.offset(i * self.stride, (nbytes,), np.uint8))
+                      for i in range(self.n_lanes)]
+
+    def lane(self, i):
+        return self.lanes[i]
+
+    def track_records(self, d_records, d_counts, max_det, p2s, image_whs, active=None, ctx=None):
+        """Encode and track one step: d_records (n_lanes, 2, max_det, 17), d_counts (n_lanes, 2), lane i taking pair i
+        under p2s[i] and image_whs[i]; active: None, or one truth value per lane -- a lane that is not active keeps
+        its state (and its pair numbering) as it is."""
+        ops.track_lanes(ctx or self.ctx, self.d_states, self.stride, self.n_lanes, d_records, d_counts, max_det, p2s,
+                        image_whs, self.score_threshold, self.high, self.iou, self.t_min, active=active)
 
 
 def _floats(rows, a, b):

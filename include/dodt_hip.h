@@ -746,6 +746,27 @@ int dodt_track_pairs(dodt_ctx* ctx, void* d_state, const void* d_records, int re
                      const int32_t* d_counts, int n_pairs, int max_det, const double* p2, double image_w,
                      double image_h, double score_threshold, double high_threshold, double iou_threshold,
                      int t_min);
+/* Lanes: several sequences (videos, cameras) advance by one pair each in one call.  The distance in bytes
+ * between two lanes' states in one buffer: dodt_track_state_bytes(log_capacity) rounded up to a multiple
+ * of 256.  Needs no context. */
+int dodt_track_lanes_stride(int log_capacity, size_t* stride);
+/* Pair i of the batch belongs to lane i.  Lane i's state is the ordinary state layout at d_states +
+ * i * stride (dodt_track_reset, dodt_track_flush and the host's reader work on that address unchanged);
+ * d_records (n_lanes, 2, max_det, 17) and d_counts (n_lanes, 2) are one step's records, lane i consuming
+ * pair i.  Host arrays, all read before the call returns: active, n_lanes bytes (non-zero: the lane takes
+ * its pair) or NULL for every lane; p2s (n_lanes, 12) and image_whs (n_lanes, 2) doubles, lane i's
+ * projection and image size.  For every active lane the live parts of its state afterwards -- the header,
+ * act[0:n_active], prev_off[0:prev_nL], prev_k1[0:prev_n1], fin[0:n_fin], log[0:n_log] -- are byte for
+ * byte what dodt_track_pairs(ctx, d_states + i * stride, pair i, n_pairs = 1, p2s[i], image_whs[i], ...)
+ * leaves, the skip rule (both keyframes empty: seq_pair advances, nothing else) and the overflow status
+ * included; of an inactive lane no byte is written; nothing of one lane reaches another.  Three launches
+ * per 16 lanes on ctx's stream, in the workspaces dodt_track_pairs uses: the encoding (one workgroup per
+ * lane, the lanes' calibrations by value in the kernel arguments), the IoU tables (each lane a batch of
+ * one pair against its own state) and the walk (one workgroup per lane, the body dodt_track_pairs runs). */
+int dodt_track_lanes(dodt_ctx* ctx, void* d_states, size_t stride, int n_lanes, const unsigned char* active,
+                     const void* d_records, int records_f64, const int32_t* d_counts, int max_det,
+                     const double* p2s, const double* image_whs, double score_threshold,
+                     double high_threshold, double iou_threshold, int t_min);
 /* Track only, from lists already encoded (the host-array form): d_track (n_pairs, max_rows, 23) and
  * d_ious (n_pairs, max_rows, 16) float32 in dodt_track_encode's layout (only the box cols 8..14, the
  * score col 15 and the offsets cols 16..22 are read; the log copies cols 0..15), d_counts (n_pairs, 2):
