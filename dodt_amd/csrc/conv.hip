@@ -54,10 +54,7 @@ const std::vector<KernelVariant>& dodt::variants() {
         Inst<16, 4, 4, 1, 64, true>::variant(),
         Inst<8, 4, 4, 1, 64, true>::variant(),
         Inst<4, 4, 4, 1, 64, true>::variant(),
-        // fp32 Winograd F(2x2,3x3): 16 x 16 px x 64 ch, 32 x 16 px x 32 ch
-        InstWino<1, 4>::variant(),
-        InstWino<2, 2>::variant(),
-        InstWino<1, 2>::variant(),    // 16 x 16 px x 32 ch, 128 accumulators: two workgroups per CU
+        InstWino<1, 2>::variant(),    // fp32 Winograd F(2x2,3x3): 16 x 16 px x 32 ch, two workgroups per CU
         InstWino43::variant(),        // F(4x4,3x3): 32 x 16 px x 32 ch, one workgroup per CU
         InstDeconvDma<2>::variant(),  // transposed conv, LDS-DMA staged: 16 x 16 input px x 32 ch
         InstDeconvDma<1>::variant(),  //   ... x 16 ch: twice the items, for layers with few of them
@@ -76,159 +73,174 @@ extern "C" int dodt_conv_mode(void) {
     static const int mode = [] {
         const char* e = getenv("DODT_CONV_WINO");
         const int m = e ? atoi(e) : DODT_CONV_MODE_DEFAULT;
-        return (m == 0 || m == 1 || m == 2 || m == 4) ? m : DODT_CONV_MODE_DEFAULT;
+        return (m == 0 || m == 2 || m == 4) ? m : DODT_CONV_MODE_DEFAULT;
     }();
     return mode;
 }
 
+// every switch the conv path reads, once per process; unset or anything but 0 leaves a form on
+const ConvSwitches& dodt::conv_switches() {
+    static const ConvSwitches s = [] {
+        auto on = [](const char* name) {
+            const char* e = getenv(name);
+            return !(e && atoi(e) == 0);
+        };
+        ConvSwitches c;
+        c.wino = dodt_conv_mode();
+        c.deconv_dma = on("DODT_CONV_DECONV_DMA");
+        c.bf16_dma = on("DODT_CONV_BF16_DMA");
+        c.bf16_stream = on("DODT_CONV_BF16_STREAM");
+        c.bf16_first2 = on("DODT_CONV_BF16_FIRST2");
+        c.bf16_xcd = on("DODT_CONV_BF16_XCD");
+        c.f32_xcd = on("DODT_CONV_F32_XCD");
+        const char* dbg = getenv("DODT_CONV_DEBUG");
+        c.debug = dbg ? atoi(dbg) : 0;
+        c.stamp_layer = getenv("DODT_CONV_STAMP_LAYER");
+        c.debug_plan = getenv("DODT_DEBUG_PLAN") != nullptr;
+        return c;
+    }();
+    return s;
+}
+
 namespace {
 
-// bf16 LDS-DMA conv kernel: one work queue per group of blocks that share an XCD (DODT_CONV_BF16_XCD=0: one queue)
-bool bf16_xcd_queue() {
-    static const bool on = !(getenv("DODT_CONV_BF16_XCD") && atoi(getenv("DODT_CONV_BF16_XCD")) == 0);
-    return on;
-}
-// the same for the fp32 Winograd F(2x2) / transposed-conv kernels (DODT_CONV_F32_XCD=0: one queue): both stacks
-// 2.90 -> 2.80 ms alone, nothing in the pipeline, half the excess fabric traffic
-bool f32_xcd_queue() {
-    static const bool on = !(getenv("DODT_CONV_F32_XCD") && atoi(getenv("DODT_CONV_F32_XCD")) == 0);
-    return on;
-}
-bool variant_xcd_queue(const dodt::KernelVariant& v) {
-    if (v.dma || (v.deconv_dma && v.bf16)) return bf16_xcd_queue();
-    if ((v.wino && v.wino_m != 4) || (v.deconv_dma && !v.bf16)) return f32_xcd_queue();
+// One work queue per group of blocks that share an XCD (conv_bf16_dma.h) in the persistent LDS-DMA kernels.  fp32:
+// both stacks 2.90 -> 2.80 ms alone, nothing in the pipeline, half the excess fabric traffic.
+bool variant_xcd_queue(const KernelVariant& v) {
+    switch (v.family) {
+        case Family::Bf16Dma:
+        case Family::Bf16Stream:
+        case Family::Bf16First2: return conv_switches().bf16_xcd;
+        case Family::DeconvDma: return v.bf16 ? conv_switches().bf16_xcd : conv_switches().f32_xcd;
+        case Family::Wino22: return conv_switches().f32_xcd;
+        case Family::Wino43:
+        case Family::Direct:
+        case Family::SmallCin: return false;
+    }
     return false;
 }
 
-// smallest padded pixel count wins; ties go to the larger output tile
-int pick_variant(bool deconv, int H, int W, int Cin, int Cout, bool bf16, int parts, int batch,
-                 int num_cus) {
+// ---------------------------------------------------------------------------
+// Which kernel a layer runs: pick_variant asks the families' rules in order; each returns a table index or -1.
+// The measurements behind the rules: DESIGN.md section 5.
+// ---------------------------------------------------------------------------
+struct LayerShape {
+    bool deconv;
+    int H, W, Cin, Cout;
+    bool bf16;   // bf16 activations: the bf16 and the split extractor
+    int parts;
+    int batch, num_cus;
+};
+
+long variant_items(const KernelVariant& v, const LayerShape& s) {
+    return (long)dodt::ceil_div(s.H, v.TH) * dodt::ceil_div(s.W, v.TW) * (s.Cout / v.BN) * s.batch;
+}
+
+// fp32 3x3 stride-1 convs with >= 4 chunks of input channels run as Winograd.  mode 2 (default):
+// F(2x2,3x3), two workgroups per CU -- both stacks 3.0 ms against the direct kernels' 4.8, rounding noise at their
+// level.  mode 4: F(4x4,3x3) -- 2.8 ms, but its fp32 accumulation in the transformed domain is 7x noisier, which
+// costs a third of the end-to-end agreement with the exact result: opt-in.  mode 0: the direct kernels.
+int pick_wino(const LayerShape& s, int mode) {
+    if (mode == 0 || s.deconv || s.bf16 || s.parts != 1 || s.Cin < 32 || s.Cin % 16 != 0) return -1;
     const auto& vs = variants();
-    const bool small = Cin < dodt::kCK;
+    int best = -1;
+    for (size_t i = 0; i < vs.size(); ++i) {
+        if (s.Cout % vs[i].BN != 0) continue;
+        if (vs[i].family == Family::Wino43 && mode == 4) return (int)i;
+        if (vs[i].family == Family::Wino22 && (best < 0 || vs[i].BN > vs[best].BN)) best = (int)i;
+    }
+    return best;
+}
+
+// Transposed convs, fp32 and bf16: the LDS-DMA staged kernel (deconv_kernel.h).  32-channel tiles unless that leaves
+// fewer than four items per CU (the CUs are MFMA-bound: what counts is how evenly the items spread).
+int pick_deconv_dma(const LayerShape& s) {
+    if (!s.deconv || s.parts != 1 || s.Cin < 32 || s.Cin % 16 != 0) return -1;
+    const auto& vs = variants();
+    const int n32 = dodt::ceil_div(s.H, 16) * dodt::ceil_div(s.W, 16) * (s.Cout / 32) * s.batch;
+    const int want_bn = (s.Cout % 32 == 0 && n32 >= 4 * s.num_cus) ? 32 : 16;
+    for (size_t i = 0; i < vs.size(); ++i)
+        if (vs[i].family == Family::DeconvDma && vs[i].bf16 == s.bf16 && vs[i].BN == want_bn && s.Cout % want_bn == 0)
+            return (int)i;
+    return -1;
+}
+
+// bf16 3x3 stride-1 convs: the LDS-DMA staged kernels (conv_bf16_dma.h: scalar-only copy issue between the MFMAs,
+// accumulators pinned in place; stacks alone as fast as the template's bf16 instantiation, frame-pair pipeline 7 %
+// faster).
+//  * The level-1 layers (32 output channels, 2 / 4 chunks): the streaming kernel.
+//  * 8-row tiles (three workgroups per CU) only where the 16-row tiles give fewer than 1.6 items per CU -- the
+//    88 x 100 / 45 x 150 maps of the deepest level: conv4_2 34 -> 30 us; at 1.9 items per CU (the image net's level
+//    3) they are slower, 26 -> 29 us.
+//  * Among the tiles of that height the widest channel tile that still leaves four items per CU (two resident
+//    workgroups, two rounds); if none does, the one with the most items.
+int pick_bf16_dma(const LayerShape& s, bool stream) {
+    if (!s.bf16 || s.parts != 1 || s.deconv || s.Cin < 32 || s.Cin % 32 != 0) return -1;
+    const auto& vs = variants();
+    if (stream && s.Cout == 32)
+        for (size_t i = 0; i < vs.size(); ++i)
+            if (vs[i].family == Family::Bf16Stream && vs[i].stream_nch * 16 == s.Cin) return (int)i;
+    long n16 = 0, n8 = 0;
+    for (const KernelVariant& v : vs)
+        if (v.family == Family::Bf16Dma && s.Cout % v.BN == 0) {
+            if (v.TH == 16) n16 = std::max(n16, variant_items(v, s));
+            if (v.TH == 8) n8 = std::max(n8, variant_items(v, s));
+        }
+    const bool rows8 = n8 > 0 && n16 < 8L * s.num_cus / 5;
+    const long enough_items = 4L * s.num_cus;
+    int best = -1;
+    long best_n = 0;
+    for (size_t i = 0; i < vs.size(); ++i) {
+        if (vs[i].family != Family::Bf16Dma || s.Cout % vs[i].BN != 0 || (vs[i].TH == 8) != rows8) continue;
+        const long n = variant_items(vs[i], s);
+        const bool enough = n >= enough_items, best_enough = best_n >= enough_items;
+        if (best < 0 || (enough && !best_enough) || (enough && best_enough && vs[i].BN > vs[best].BN) ||
+            (!enough && !best_enough && n > best_n)) {
+            best = (int)i; best_n = n;
+        }
+    }
+    return best;
+}
+
+// The register-staged template and the first-layer kernel: the cheapest tiling by a cost model.  Which model is
+// measured.  fp32 and the first layer: padded pixels, with a mild preference for more work per staged byte (the
+// round model's choices run a lone net 9 % faster but the frame-pair pipeline 4 % slower).  bf16 and split: the
+// round model (stacks 15 % faster alone, pipeline 4-6 % faster) -- workgroups sharing a CU share its matrix pipe,
+// so a layer takes ceil(items / CUs) item times; an item = its 32x32 MFMA tiles over the variant's in-tile
+// efficiency (2x2 tiles per wave 1.0, 2 tiles 0.9, 1 tile 0.8).  Ties go to the entry that stands first.
+int pick_direct(const LayerShape& s) {
+    const auto& vs = variants();
+    const bool small = s.Cin < dodt::kCK;
     int best = -1;
     double best_cost = 1e300;
-    // fp32 3x3 stride-1 convs with >= 4 chunks of input channels run as Winograd.
-    // dodt_conv_mode(): 2 (default) = F(2x2,3x3) with 128 accumulators, two workgroups per CU
-    // (wino_kernels.h: both stacks 3.0 ms, rounding noise at the direct kernels' level), 4 =
-    // F(4x4,3x3) (wino43_kernel.h: 2.8 ms, but its fp32 accumulation in the transformed domain is
-    // 7x noisier, which costs a third of the end-to-end agreement with the exact result: opt-in), 1 = the
-    // 256-accumulator F(2x2) variants, one workgroup per CU (no faster than direct), 0 = the direct
-    // kernels (4.8 ms).
-    static const int wino_mode = dodt_conv_mode();
-    if (wino_mode > 0 && !deconv && !bf16 && parts == 1 && Cin >= 32 && Cin % 16 == 0) {
-        for (size_t i = 0; i < vs.size(); ++i) {
-            if (!vs[i].wino || Cout % vs[i].BN != 0) continue;
-            if (vs[i].wino_m == 4) {
-                if (wino_mode == 4) return (int)i;
-                continue;
-            }
-            if ((wino_mode == 1) == (vs[i].blocks_per_cu == 2)) continue;
-            if (best < 0 || vs[i].BN > vs[best].BN) best = (int)i;
-        }
-        if (best >= 0) return best;
-    }
-    // fp32 transposed convs: the LDS-DMA staged kernel (deconv_kernel.h; DODT_CONV_DECONV_DMA=0: the
-    // register-staged direct kernel's deconv instantiation)
-    static const bool deconv_dma = !(getenv("DODT_CONV_DECONV_DMA") && atoi(getenv("DODT_CONV_DECONV_DMA")) == 0);
-    // (bf16 transposed convs take the same kernel on the bf16 MFMA since round 3; DODT_CONV_DECONV_DMA=0
-    //  puts both back on the register-staged template)
-    if (deconv_dma && deconv && parts == 1 && Cin >= 32 && Cin % 16 == 0) {
-        // 32-channel tiles unless that leaves fewer than four items per CU (the CUs are MFMA-bound:
-        // what counts is how evenly the items spread)
-        const int n32 = dodt::ceil_div(H, 16) * dodt::ceil_div(W, 16) * (Cout / 32) * batch;
-        const int want_bn = (Cout % 32 == 0 && n32 >= 4 * num_cus) ? 32 : 16;
-        for (size_t i = 0; i < vs.size(); ++i)
-            if (vs[i].deconv_dma && vs[i].bf16 == bf16 && vs[i].BN == want_bn && Cout % want_bn == 0) return (int)i;
-    }
-    // bf16 3x3 stride-1 layers: the LDS-DMA staged kernel (conv_bf16_dma.h: scalar-only copy issue
-    // between the MFMAs, accumulators pinned in place; stacks alone as fast as the template's bf16
-    // instantiation, frame-pair pipeline 7 % faster: 625 against 585 pairs/s).  DODT_CONV_BF16_DMA=0
-    // selects the template.
-    static const bool bf16_dma = !(getenv("DODT_CONV_BF16_DMA") && atoi(getenv("DODT_CONV_BF16_DMA")) == 0);
-    if (bf16_dma && bf16 && parts == 1 && !deconv && Cin >= 32 && Cin % 32 == 0) {
-        // the widest channel tile that still leaves four items per CU (two resident workgroups,
-        // two rounds); if none does, the one with the most items (half-height tiles were tried for
-        // the small maps: slower, the per-item cost grows faster than the balance improves)
-        // the level-1 layers (32 output channels, 2 / 4 chunks): the streaming kernel (DODT_CONV_BF16_STREAM=0: not)
-        static const bool stream = !(getenv("DODT_CONV_BF16_STREAM") && atoi(getenv("DODT_CONV_BF16_STREAM")) == 0);
-        // (DODT_CONV_BF16_STREAM_LDS=<KB>: the deepest ring within that much LDS per workgroup; the table lists them deepest first)
-        static const int stream_lds = getenv("DODT_CONV_BF16_STREAM_LDS") ? atoi(getenv("DODT_CONV_BF16_STREAM_LDS")) * 1024 : 1 << 30;
-        if (stream && Cout == 32)
-            for (size_t i = 0; i < vs.size(); ++i)
-                if (vs[i].stream_nch > 0 && vs[i].stream_nch * 16 == Cin && vs[i].lds_bytes <= stream_lds) return (int)i;
-        long best_n = 0;
-        static const long per_cu = getenv("DODT_CONV_BF16_ITEMS_PER_CU") ? atol(getenv("DODT_CONV_BF16_ITEMS_PER_CU")) : 4;
-        // 8-row tiles (three workgroups per CU): first only where the 16-row tiles gave fewer than 1.6 items per CU -- the
-        // 88 x 100 / 45 x 150 maps of the deepest level: conv4_2 34 -> 30 us, stacks 1.065 -> 1.043 ms alone, nothing in
-        // the pipeline; at 1.9 items per CU (the image net's level 3, 480 items) they are slower: 26 -> 29 us
-        // (DODT_CONV_BF16_MT2=0: never; DODT_CONV_BF16_MT2_BELOW=<items>: another threshold)
-        static const bool mt2 = !(getenv("DODT_CONV_BF16_MT2") && atoi(getenv("DODT_CONV_BF16_MT2")) == 0);
-        static const long mt2_below = getenv("DODT_CONV_BF16_MT2_BELOW") ? atol(getenv("DODT_CONV_BF16_MT2_BELOW")) : 0;
-        long n16 = 0;
-        for (size_t i = 0; i < vs.size(); ++i)
-            if (vs[i].dma && !vs[i].stream_nch && !vs[i].first2 && vs[i].TH == 16 && Cout % vs[i].BN == 0)
-                n16 = std::max(n16, (long)dodt::ceil_div(H, 16) * dodt::ceil_div(W, vs[i].TW) * (Cout / vs[i].BN) * batch);
-        // Round 4, late (the epilogue's cost per item fell), measured and NOT the default: a round model instead of the item
-        // threshold (DODT_CONV_BF16_MT2_RULE=rounds) -- 16-row tiles take ceil(items / 2 per CU) rounds of an item time, 8-row
-        // tiles ceil(items / 3 per CU) rounds of 0.625 of it; 8-row tiles where that is a tenth shorter.  It adds the BEV net's
-        // level-2 / level-3 layers (1 144 and 616 items on 512 slots: a mostly empty last round): conv2_2 35 -> 30, conv3_2
-        // 33 -> 28, conv3_3 35 -> 29 us, both stacks 0.875 -> 0.849 ms ALONE -- but 0.695 -> 0.71 ms side by side (three
-        // workgroups per CU leave the other stack's kernels less room) and 1 013-1 027 -> 1 009 pairs/s in the pipeline.
-        static const bool rounds_rule = getenv("DODT_CONV_BF16_MT2_RULE") && !strcmp(getenv("DODT_CONV_BF16_MT2_RULE"), "rounds");
-        long n8 = 0;
-        for (size_t i = 0; i < vs.size(); ++i)
-            if (vs[i].dma && !vs[i].stream_nch && !vs[i].first2 && vs[i].TH == 8 && Cout % vs[i].BN == 0)
-                n8 = std::max(n8, (long)dodt::ceil_div(H, 8) * dodt::ceil_div(W, vs[i].TW) * (Cout / vs[i].BN) * batch);
-        const double t16 = (double)dodt::ceil_div((int)n16, 2 * num_cus), t8 = 0.625 * dodt::ceil_div((int)n8, 3 * num_cus);
-        const bool want_mt2 = mt2 && n8 > 0 && (rounds_rule ? t8 < 0.9 * t16
-                                                            : n16 < (mt2_below > 0 ? mt2_below : 8L * num_cus / 5));
-        for (size_t i = 0; i < vs.size(); ++i) {
-            if (!vs[i].dma || vs[i].stream_nch || vs[i].first2 || Cout % vs[i].BN != 0) continue;
-            if ((vs[i].TH == 8) != want_mt2) continue;
-            const long n = (long)dodt::ceil_div(H, vs[i].TH) * dodt::ceil_div(W, vs[i].TW) * (Cout / vs[i].BN) * batch;
-            const bool enough = n >= per_cu * num_cus, best_enough = best_n >= per_cu * num_cus;
-            if (best < 0 || (enough && !best_enough) || (enough && best_enough && vs[i].BN > vs[best].BN) ||
-                (!enough && !best_enough && n > best_n)) {
-                best = (int)i; best_n = n;
-            }
-        }
-        if (best >= 0) return best;
-    }
     for (size_t i = 0; i < vs.size(); ++i) {
         const KernelVariant& v = vs[i];
-        if (v.wino || v.dma || v.deconv_dma) continue;
-        if (v.deconv != deconv || v.small_cin != small || v.tail_only || v.bf16 != bf16 ||
-            v.parts != parts || Cout % v.BN != 0)
-            continue;
-        static const int max_bn = getenv("DODT_CONV_MAX_BN") ? atoi(getenv("DODT_CONV_MAX_BN")) : 1024;
-        if (v.BN > max_bn) continue;
+        if (v.family != (small ? Family::SmallCin : Family::Direct)) continue;
+        if (v.deconv != s.deconv || v.tail_only || v.bf16 != s.bf16 || v.parts != s.parts || s.Cout % v.BN != 0) continue;
         // the chunk pipeline needs >= 2 chunks (8 channels fp32, 16 channels bf16) per item
-        if (small ? (Cin != v.CK || Cout != 32) : (Cin % v.CK != 0 || Cin < 32)) continue;
-        const double padded = (double)dodt::ceil_div(H, v.TH) * v.TH * dodt::ceil_div(W, v.TW) * v.TW;
+        if (small ? (s.Cin != v.CK || s.Cout != 32) : (s.Cin % v.CK != 0 || s.Cin < 32)) continue;
         double cost;
-        // which model: measured.  fp32: the padded-pixel rule (the round model's choices run a
-        // lone net 9 % faster but the frame-pair pipeline 4 % slower); bf16: the round model
-        // (stacks 15 % faster alone, pipeline 4-6 % faster).  DODT_CONV_ROUND_MODEL=0/1 forces.
-        static const int force = getenv("DODT_CONV_ROUND_MODEL") ? atoi(getenv("DODT_CONV_ROUND_MODEL")) : -1;
-        const bool model = force >= 0 ? force != 0 : bf16;
-        if (!model || small) {
-            // padded pixels, mild preference for more work per staged byte
+        if (!s.bf16 || small) {
+            const double padded = (double)dodt::ceil_div(s.H, v.TH) * v.TH * dodt::ceil_div(s.W, v.TW) * v.TW;
             cost = padded * (1.0 + 0.04 / v.MTB + 1.0 / v.BN);
         } else {
-            // round model: workgroups sharing a CU share its matrix pipe, so a layer takes
-            // ceil(items / CUs) item times; an item = its 32x32 MFMA tiles over the variant's
-            // in-tile efficiency (2x2 tiles per wave 1.0, 2 tiles 0.9, 1 tile 0.8)
-            const double items = (double)dodt::ceil_div(H, v.TH) * dodt::ceil_div(W, v.TW) * batch *
-                                 (Cout / v.BN);
-            const int wave_tiles = deconv ? 4 * (v.BN / 32 / v.WN)
-                                          : (v.MTB / v.WM) * (v.BN / 32 / v.WN);
+            const double items = (double)dodt::ceil_div(s.H, v.TH) * dodt::ceil_div(s.W, v.TW) * s.batch * (s.Cout / v.BN);
+            const int wave_tiles = s.deconv ? 4 * (v.BN / 32 / v.WN) : (v.MTB / v.WM) * (v.BN / 32 / v.WN);
             const double eff = wave_tiles >= 4 ? 1.0 : wave_tiles >= 2 ? 0.9 : 0.8;
             const double units = (double)(v.TW * v.TH / 32) * (v.BN / 32);
-            cost = std::ceil(items / num_cus) * units / eff;
+            cost = std::ceil(items / s.num_cus) * units / eff;
         }
         if (cost < best_cost) { best_cost = cost; best = (int)i; }
     }
     return best;
+}
+
+int pick_variant(const LayerShape& s) {
+    const ConvSwitches& sw = conv_switches();
+    int i = pick_wino(s, sw.wino);
+    if (i < 0 && sw.deconv_dma) i = pick_deconv_dma(s);
+    if (i < 0 && sw.bf16_dma) i = pick_bf16_dma(s, sw.bf16_stream);
+    return i >= 0 ? i : pick_direct(s);
 }
 
 // ---------------------------------------------------------------------------
@@ -367,7 +379,8 @@ void report_launch(const dodt_extractor* ex, const Layer& l, const KernelVariant
             fprintf(stderr, "[dodt]   steps 0..11: %d stamp ticks in %d ticks of the 100 MHz clock (%.0f MHz)\n",
                     h[66] - h[0], h[73] - h[72], 100.0 * (h[66] - h[0]) / (h[73] - h[72]));
     }
-    if ((a.debug & 128) && v.dma) {   // diagnostic: when the workgroups of this launch started and ended
+    const bool bf16_dma = v.family == Family::Bf16Dma || v.family == Family::Bf16Stream || v.family == Family::Bf16First2;
+    if ((a.debug & 128) && bf16_dma) {   // diagnostic: when the workgroups of this launch started and ended
         std::vector<int> h(4 * grid_x);
         (void)hipStreamSynchronize(ex->ctx->stream);
         (void)hipMemcpy(h.data(), ex->d_counters + 64 + 256, h.size() * sizeof(int), hipMemcpyDeviceToHost);
@@ -402,11 +415,8 @@ void report_launch(const dodt_extractor* ex, const Layer& l, const KernelVariant
 
 // persistent workgroups: as many as stay resident on num_cus CUs, each walks items with that stride
 int launch_grid(const KernelVariant& v, int n_items, int num_cus) {
-    static const int bpc_env = getenv("DODT_CONV_BPC") ? atoi(getenv("DODT_CONV_BPC")) : 0;
     // (the first-layer kernel is persistent since round 4: three workgroups per CU by its registers)
-    static const int small_bpc = getenv("DODT_CONV_SMALL_BPC") ? atoi(getenv("DODT_CONV_SMALL_BPC")) : 3;
-    const int vb = v.small_cin ? small_bpc : v.blocks_per_cu;
-    const int bpc = (bpc_env > 0 && bpc_env < vb) ? bpc_env : vb;
+    const int bpc = v.family == Family::SmallCin ? 3 : v.blocks_per_cu;
     return std::min(n_items, num_cus * bpc);
 }
 
@@ -442,19 +452,15 @@ int run_launch(const dodt_extractor* ex, const Pass& p, const Layer& l, int whic
     a.relu = 1;
     a.out_y0 = out_y0;
     a.out_nhwc = override_out ? 1 : 0;
-    {
-        static const int dbg = getenv("DODT_CONV_DEBUG") ? atoi(getenv("DODT_CONV_DEBUG")) : 0;
-        a.debug = dbg;
-        // DODT_CONV_STAMP_LAYER=<name>: in-kernel step stamps of that layer's launch (diagnostic)
-        static const char* stamp_layer = getenv("DODT_CONV_STAMP_LAYER");
-        if (stamp_layer && l.name == stamp_layer) a.debug |= 32;     // (+ DODT_CONV_DEBUG=64: the streaming kernel's producer wave)
-    }
+    a.debug = conv_switches().debug;
+    // in-kernel step stamps of one layer's launch (+ DODT_CONV_DEBUG=64: the streaming kernel's producer wave)
+    if (conv_switches().stamp_layer && l.name == conv_switches().stamp_layer) a.debug |= 32;
     a.counter = ex->d_counters + 2 * li + which;
     a.counter_base = ex->d_counters + 64;
     // (eight counters, 64 bytes apart, per layer: words 2048.. of the block)
     a.xcd_counters = variant_xcd_queue(v) ? ex->d_counters + 2048 + 128 * li : nullptr;
     // the first-layer kernel derives a full table's coordinates from the item index (no table load ahead of its patch)
-    a.items = v.small_cin && t.dense && t.n == a.tiles_x * a.tiles_y * p.frames ? nullptr : t.items;
+    a.items = v.family == Family::SmallCin && t.dense && t.n == a.tiles_x * a.tiles_y * p.frames ? nullptr : t.items;
     a.n_items = t.n;
     if (a.n_items == 0) return DODT_OK;   // every item of the launch skipped
     // per-frame tables: the builder's launches ahead in the stream wrote this forward's items and their count
@@ -483,9 +489,18 @@ int run_launch(const dodt_extractor* ex, const Pass& p, const Layer& l, int whic
 
 // a variant's waves hold both rows of every 2x2 pooling window (conv_kernels.h kCanPool)
 bool variant_can_pool(const KernelVariant& v) {
-    if (v.wino) return true;   // a lane's 2x2 outputs are one pooling window
+    switch (v.family) {
+        case Family::Wino22:
+        case Family::Wino43: return true;   // a lane's output block is whole 2x2 pooling windows
+        case Family::SmallCin:
+        case Family::DeconvDma: return false;
+        case Family::Direct:
+        case Family::Bf16Dma:
+        case Family::Bf16Stream:
+        case Family::Bf16First2: break;
+    }
     const int rows_per_mt = 32 / v.TW, mt = v.MTB / v.WM;
-    return !v.deconv && !v.small_cin && (rows_per_mt >= 2 || mt % 2 == 0) && v.TH % 2 == 0;
+    return !v.deconv && (rows_per_mt >= 2 || mt % 2 == 0) && v.TH % 2 == 0;
 }
 
 bool layer_can_pool(const Layer& l) {
@@ -510,13 +525,17 @@ int run_layer(const dodt_extractor* ex, const Pass& p, const Layer& l, float* ov
 
 // the __global__ function a variant launches (what rocprofv3 --kernel-trace lists)
 const char* kernel_name(const KernelVariant& v) {
-    if (v.wino) return v.wino_m == 4 ? "wino43_f32_kernel" : "wino3x3_f32_kernel";
-    if (v.deconv_dma) return "deconv3x3_dma_kernel";
-    if (v.first2) return "conv3x3_bf16_first2_kernel";
-    if (v.stream_nch) return "conv3x3_bf16_stream_kernel";
-    if (v.dma) return "conv3x3_bf16_dma_kernel";
-    if (v.small_cin) return "conv3x3_small_cin_kernel";
-    return "conv3x3_mfma_kernel";
+    switch (v.family) {
+        case Family::Direct: return "conv3x3_mfma_kernel";
+        case Family::SmallCin: return "conv3x3_small_cin_kernel";
+        case Family::Wino22: return "wino3x3_f32_kernel";
+        case Family::Wino43: return "wino43_f32_kernel";
+        case Family::DeconvDma: return "deconv3x3_dma_kernel";
+        case Family::Bf16Dma: return "conv3x3_bf16_dma_kernel";
+        case Family::Bf16Stream: return "conv3x3_bf16_stream_kernel";
+        case Family::Bf16First2: return "conv3x3_bf16_first2_kernel";
+    }
+    return "";
 }
 
 // frac: share of the layer's work items that run (skip tables: Layer::skip_frac)
@@ -530,8 +549,11 @@ double layer_direct_flops(const dodt_extractor* ex, const Layer& l, double frac 
 double layer_executed_flops(const dodt_extractor* ex, const Layer& l, double frac = 1.0) {
     const KernelVariant& kv = variants()[l.main.variant];
     const double direct = layer_direct_flops(ex, l, frac);
-    if (kv.wino) return direct * (kv.wino_m == 4 ? 36.0 / 144.0 : 16.0 / 36.0);
-    return kv.parts == 2 ? 3.0 * direct : direct;
+    switch (kv.family) {
+        case Family::Wino22: return direct * (16.0 / 36.0);
+        case Family::Wino43: return direct * (36.0 / 144.0);
+        default: return kv.parts == 2 ? 3.0 * direct : direct;
+    }
 }
 
 // algorithmic HBM bytes of a layer: input map and weights read once, output map (and its pooled
@@ -581,20 +603,18 @@ void plan_layer(Layer& l, int batch, int num_cus, bool allow_tail, std::vector<i
     }
     l.main.variant = l.variant;
     l.tail.variant = -1;
-    if (v.small_cin || v.wino || v.dma || v.deconv_dma) return;
-    static const bool no_tail = getenv("DODT_CONV_NO_TAIL") != nullptr;
+    if (v.family != Family::Direct) return;   // (only the template has quarter-size companions)
     const int n = (int)main_items.size();
     const int G = num_cus * v.blocks_per_cu;
     const int surplus = n % G;
-    if (no_tail || !allow_tail || n < G || surplus == 0) return;
-    // companion: same TW and kind, dividing the big tile, as small as possible
+    if (!allow_tail || n < G || surplus == 0) return;
+    // companion: a template entry of the same kind and data type, same TW, dividing the big tile, as small as possible
     int best = -1, best_units = 1 << 30;
     const int big_units = (v.TW * v.TH / 32) * (v.BN / 32);
     for (size_t i = 0; i < vs.size(); ++i) {
         const KernelVariant& c = vs[i];
-        if (c.small_cin || c.deconv != v.deconv || c.TW != v.TW || v.TH % c.TH != 0 ||
-            v.BN % c.BN != 0)
-            continue;
+        if (c.family != Family::Direct || c.deconv != v.deconv || c.bf16 != v.bf16 || c.parts != v.parts) continue;
+        if (c.TW != v.TW || v.TH % c.TH != 0 || v.BN % c.BN != 0) continue;
         const int units = (c.TW * c.TH / 32) * (c.BN / 32);
         if (units < big_units && units < best_units) { best = (int)i; best_units = units; }
     }
@@ -645,8 +665,7 @@ int forward(dodt_extractor* ex, const float* d_in, const float* d_x0, float* d_f
 }  // namespace
 
 int dodt::fused_pool_buffer(const Layer& l) {
-    static const bool no_fuse = getenv("DODT_CONV_NO_POOL_FUSE") != nullptr;
-    return no_fuse || !layer_can_pool(l) ? -1 : l.pool;
+    return layer_can_pool(l) ? l.pool : -1;
 }
 
 bool dodt::bneck_fused(const Layer& last) {
@@ -742,7 +761,7 @@ int dodt::plan_convs(int kind, int in_h, int in_w, int in_c, int pad_top, int ba
         l.pool = pool;
         l.name = name; l.deconv = deconv; l.H = h; l.W = w; l.Cin = cin; l.Cout = cout;
         l.src = src; l.src_coff = src_coff; l.dst = dst; l.dst_coff = dst_coff;
-        l.variant = pick_variant(deconv, h, w, cin, cout, bf16, plan.parts, batch, num_cus);
+        l.variant = pick_variant(LayerShape{deconv, h, w, cin, cout, bf16, plan.parts, batch, num_cus});
         l.real_cin = cin;
         plan.layers.push_back(l);
     };
@@ -783,17 +802,18 @@ int dodt::plan_convs(int kind, int in_h, int in_w, int in_c, int pad_top, int ba
     {
         // bf16 conv path: conv1_1 folded into conv1_2's launch when conv1_2 runs on the streaming kernel (same tiles, same
         // weight blocking) and the input rows are whole 16-byte slots (DODT_CONV_BF16_FIRST2=0: two launches)
-        static const bool first2 = !(getenv("DODT_CONV_BF16_FIRST2") && atoi(getenv("DODT_CONV_BF16_FIRST2")) == 0);
         const Layer& c11 = plan.layers[CONV1_1];
         const Layer& c12 = plan.layers[CONV1_2];
         const auto& vs = variants();
         // (the input buffer holds exactly conv1_1's in_c channels)
-        if (first2 && bf16 && plan.parts == 1 && vs[c12.variant].stream_nch == 2 && c12.tail.n_items == 0 &&
+        const KernelVariant& v12 = vs[c12.variant];
+        if (conv_switches().bf16_first2 && bf16 && plan.parts == 1 && v12.family == Family::Bf16Stream &&
+            v12.stream_nch == 2 && c12.tail.n_items == 0 &&
             c11.Cout == 32 && c11.src_coff == 0 && (W * c11.Cin * 4) % 16 == 0 &&
-            variant_can_pool(vs[c12.variant]))
+            variant_can_pool(v12))
             for (size_t i = 0; i < vs.size() && plan.first2_variant < 0; ++i)
-                if (vs[i].first2 == c11.Cin && vs[i].TH == vs[c12.variant].TH && vs[i].TW == vs[c12.variant].TW &&
-                    vs[i].lds_bytes <= (getenv("DODT_CONV_BF16_STREAM_LDS") ? atoi(getenv("DODT_CONV_BF16_STREAM_LDS")) * 1024 : 1 << 30))
+                if (vs[i].family == Family::Bf16First2 && vs[i].first2_cin == c11.Cin && vs[i].TH == v12.TH &&
+                    vs[i].TW == v12.TW)
                     plan.first2_variant = (int)i;
     }
     return DODT_OK;
@@ -857,13 +877,20 @@ int dodt_conv_variant_info(int i, dodt_conv_variant* out) {
     memset(out, 0, sizeof(*out));
     out->tw = v.TW; out->th = v.TH; out->bn = v.BN; out->ck = v.CK;
     out->blocks_per_cu = v.blocks_per_cu;
-    out->flags = (v.deconv ? DODT_VARIANT_DECONV : 0) | (v.small_cin ? DODT_VARIANT_SMALL_CIN : 0) |
-                 (v.tail_only ? DODT_VARIANT_TAIL_ONLY : 0) | (v.bf16 ? DODT_VARIANT_BF16 : 0) |
-                 (v.parts == 2 ? DODT_VARIANT_SPLIT : 0) | (v.wino ? DODT_VARIANT_WINO : 0) |
-                 (v.wino && v.wino_m == 4 ? DODT_VARIANT_WINO43 : 0) | (v.dma ? DODT_VARIANT_DMA : 0) |
-                 (v.deconv_dma ? DODT_VARIANT_DECONV_DMA : 0) | (v.first2 ? DODT_VARIANT_FIRST2 : 0) |
-                 (v.stream_nch ? DODT_VARIANT_STREAM : 0) | (variant_xcd_queue(v) ? DODT_VARIANT_XCD_QUEUE : 0) |
-                 (variant_can_pool(v) ? DODT_VARIANT_CAN_POOL : 0);
+    int family_flags = 0;
+    switch (v.family) {
+        case Family::Direct: break;
+        case Family::SmallCin: family_flags = DODT_VARIANT_SMALL_CIN; break;
+        case Family::Wino22: family_flags = DODT_VARIANT_WINO; break;
+        case Family::Wino43: family_flags = DODT_VARIANT_WINO | DODT_VARIANT_WINO43; break;
+        case Family::DeconvDma: family_flags = DODT_VARIANT_DECONV_DMA; break;
+        case Family::Bf16Dma: family_flags = DODT_VARIANT_DMA; break;
+        case Family::Bf16Stream: family_flags = DODT_VARIANT_DMA | DODT_VARIANT_STREAM; break;
+        case Family::Bf16First2: family_flags = DODT_VARIANT_DMA | DODT_VARIANT_FIRST2; break;
+    }
+    out->flags = family_flags | (v.deconv ? DODT_VARIANT_DECONV : 0) | (v.tail_only ? DODT_VARIANT_TAIL_ONLY : 0) |
+                 (v.bf16 ? DODT_VARIANT_BF16 : 0) | (v.parts == 2 ? DODT_VARIANT_SPLIT : 0) |
+                 (variant_xcd_queue(v) ? DODT_VARIANT_XCD_QUEUE : 0) | (variant_can_pool(v) ? DODT_VARIANT_CAN_POOL : 0);
     out->lds_bytes = v.lds_bytes;
     snprintf(out->kernel, sizeof(out->kernel), "%s", kernel_name(v));
     return DODT_OK;
@@ -946,7 +973,7 @@ int dodt_extractor_create(dodt_ctx* ctx, int kind, int in_h, int in_w, int in_c,
         }
     }
     DODT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (getenv("DODT_DEBUG_PLAN")) {
+    if (conv_switches().debug_plan) {
         if (ex->first2_variant >= 0) fprintf(stderr, "[dodt] conv1_1 runs folded into conv1_2's launch\n");
         for (const Layer& l : ex->layers) {
             const KernelVariant& v = variants()[l.variant];
@@ -1028,11 +1055,11 @@ int dodt_extractor_set_layer(dodt_extractor* ex, const char* name, const float* 
             continue;
         }
         const KernelVariant& v = variants()[ln->variant];
-        const WeightTile t{v.BN, v.CK, v.bf16, v.small_cin, v.parts};
-        const std::vector<float> blocked = v.deconv_dma               ? block_deconv_dma(t, l, w, cin, cout)
-                                           : v.wino && v.wino_m == 4 ? block_wino43(t, l, w, cin, cout)
-                                           : v.wino                  ? block_wino22(t, l, w, cin, cout)
-                                                                     : block_direct(t, l, w, cin, cout);
+        const WeightTile t{v.BN, v.CK, v.bf16, v.family == Family::SmallCin, v.parts};
+        const std::vector<float> blocked = v.family == Family::DeconvDma ? block_deconv_dma(t, l, w, cin, cout)
+                                           : v.family == Family::Wino43  ? block_wino43(t, l, w, cin, cout)
+                                           : v.family == Family::Wino22  ? block_wino22(t, l, w, cin, cout)
+                                                                         : block_direct(t, l, w, cin, cout);
         if ((rc = upload(&ln->d_w, blocked, s))) return rc;
     }
     if (li == 0 && ex->bf16 && ex->parts == 1 && l.Cout == 32 && (l.Cin == 6 || l.Cin == 4))

@@ -24,9 +24,6 @@ std::vector<KernelVariant> bf16_variants() {
         Inst<16, 4, 4, 1, 32, true, true>::variant(),
         Inst<8, 4, 4, 1, 32, true, true>::variant(),
         Inst<4, 4, 4, 1, 32, true, true>::variant(),
-        Inst<16, 4, 4, 1, 64, true, true>::variant(),
-        Inst<8, 4, 4, 1, 64, true, true>::variant(),
-        Inst<4, 4, 4, 1, 64, true, true>::variant(),
         // round 2: LDS-DMA staged 3x3 stride-1 kernels, 16 x 32 px x 64 / 32 channels
         InstBf16Dma<4, 2, 2>::variant(),
         InstBf16Dma<4, 1, 2>::variant(),
@@ -34,17 +31,9 @@ std::vector<KernelVariant> bf16_variants() {
         // round 4: producer wave + weights in registers, for the level-1 layers (32 output channels, 2 / 4 chunks)
         InstBf16Stream<2, 2, 8>::variant(),
         InstBf16Stream<2, 4, 6>::variant(),
-        // (shallower rings, less LDS: DODT_CONV_BF16_STREAM_LDS=<KB> picks the deepest ring that fits -- tools/)
-        InstBf16Stream<2, 2, 5>::variant(),
-        InstBf16Stream<2, 2, 3>::variant(),
-        InstBf16Stream<2, 4, 4>::variant(),
-        InstBf16Stream<2, 4, 3>::variant(),
         // round 4: conv1_1 folded into conv1_2 (never picked by shape: dodt_extractor_forward launches it in conv1_2's place)
         InstBf16First2<6, 4>::variant(),
         InstBf16First2<4, 6>::variant(),
-        InstBf16First2<6, 3>::variant(),
-        InstBf16First2<4, 4>::variant(),
-        InstBf16First2<4, 3>::variant(),
         // round 3: the LDS-DMA staged transposed conv on v_mfma_f32_16x16x16_bf16 (deconv_kernel.h)
         InstDeconvDma<2, true>::variant(),
         InstDeconvDma<1, true>::variant(),

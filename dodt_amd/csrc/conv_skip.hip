@@ -459,7 +459,7 @@ int dodt_extractor_set_input_support(dodt_extractor* ex, const uint8_t* mask, in
     for (Layer& l : ex->layers) {
         const KernelVariant& lv = variants()[l.main.variant];
         const Support out = l.deconv ? upconv2(bufs[l.src])
-                            : lv.wino && lv.wino_m == 4 ? wino_blocks(bufs[l.src], 4) : dilate(bufs[l.src], 1);
+                            : lv.family == Family::Wino43 ? wino_blocks(bufs[l.src], 4) : dilate(bufs[l.src], 1);
         Support& d = bufs[l.dst];
         if (d.m.empty()) d = out;
         else
@@ -490,7 +490,7 @@ int dodt_extractor_set_input_support(dodt_extractor* ex, const uint8_t* mask, in
     }
     ex->skip_on = true;
     if (skipped_items) *skipped_items = skipped;
-    if (getenv("DODT_DEBUG_PLAN"))
+    if (conv_switches().debug_plan)
         for (const Layer& l : ex->layers)
             fprintf(stderr, "[dodt] %-16s skip tables: %d of %d items\n", l.name.c_str(),
                     std::max(l.main.n_skip, 0) + std::max(l.tail.n_skip, 0), l.main.n_items + l.tail.n_items);
@@ -507,7 +507,7 @@ int dodt_extractor_set_frame_tables(dodt_extractor* ex, int on, int* enabled) {
     if ((int)ex->layers.size() != ft::kLayers) return DODT_OK;
     for (const Layer& l : ex->layers)
         for (const Launch* ln : {&l.main, &l.tail})
-            if (ln->variant >= 0 && variants()[ln->variant].wino && variants()[ln->variant].wino_m == 4) return DODT_OK;
+            if (ln->variant >= 0 && variants()[ln->variant].family == Family::Wino43) return DODT_OK;
     const size_t words = (size_t)ft::level_words(ex->H, ex->W, 0);
     if (words * 8 > 160 * 1024 - 1024) return DODT_OK;
     DODT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&frame_walk_kernel),

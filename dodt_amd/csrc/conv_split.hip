@@ -23,9 +23,6 @@ std::vector<KernelVariant> split_variants() {
         Inst<16, 4, 4, 1, 32, true, true, 2>::variant(),
         Inst<8, 4, 4, 1, 32, true, true, 2>::variant(),
         Inst<4, 4, 4, 1, 32, true, true, 2>::variant(),
-        Inst<16, 4, 4, 1, 64, true, true, 2>::variant(),
-        Inst<8, 4, 4, 1, 64, true, true, 2>::variant(),
-        Inst<4, 4, 4, 1, 64, true, true, 2>::variant(),
     };
 }
 

@@ -11,9 +11,22 @@
 
 namespace dodt {
 
+// Which __global__ template a variant launches, and with it its queue code, weight blocking and planning rule.
+enum class Family {
+    Direct,      // the register-staged template (conv_kernels.h): conv and transposed conv; fp32, bf16 and split
+    SmallCin,    // the first layer's kernel (conv_kernels.h): 4 / 6 input channels
+    Wino22,      // fp32 Winograd F(2x2,3x3) (wino_kernels.h): 16 weight points, not 9 taps
+    Wino43,      // fp32 Winograd F(4x4,3x3) (wino43_kernel.h)
+    DeconvDma,   // transposed conv, LDS-DMA staged (deconv_kernel.h): fp32 and bf16
+    Bf16Dma,     // bf16 3x3 conv, LDS-DMA staged (conv_bf16_dma.h)
+    Bf16Stream,  // ... with a producer wave and the weights in registers: 32 output channels, stream_nch chunks
+    Bf16First2,  // ... with conv1_1 (first2_cin input channels) folded into conv1_2's launch
+};
+
 struct KernelVariant {
     int TW, MTB, WM, WN, BN, CK;
-    bool deconv, small_cin;
+    bool deconv;
+    Family family;
     int TH, lds_bytes;
     int blocks_per_cu;  // resident workgroups per CU (registers and LDS permitting)
     void (*launch)(const ConvArgs&, dim3 grid, hipStream_t s);
@@ -21,14 +34,25 @@ struct KernelVariant {
     bool tail_only = false;  // quarter-size tiles: never a layer's main variant
     bool bf16 = false;       // CB16 bf16 activations (first-layer kernels: bf16 OUTPUT)
     int parts = 1;           // 2: split mode, every map is a hi + lo pair of bf16 maps
-    bool wino = false;       // Winograd F(2x2,3x3) kernel (wino_kernels.h): 16 weight points, not 9 taps
-    bool dma = false;        // bf16 kernel with LDS-DMA staging (conv_bf16_dma.h)
-    int wino_m = 2;          // Winograd output block: F(2x2,3x3) or F(4x4,3x3) (wino43_kernel.h)
-    bool deconv_dma = false; // transposed conv, LDS-DMA staged (deconv_kernel.h)
-    int first2 = 0;          // 6 / 4: conv1_1 (that many input channels) folded into conv1_2 (conv3x3_bf16_first2_kernel)
-    int stream_nch = 0;      // > 0: bf16 LDS-DMA kernel with a producer wave and the weights in registers
-                             // (conv3x3_bf16_stream_kernel): exactly this many 16-channel chunks, 32 output channels
+    int first2_cin = 0;      // Bf16First2: conv1_1's input channels, 6 / 4
+    int stream_nch = 0;      // Bf16Stream: exactly this many 16-channel input chunks
 };
+
+// What the conv path reads from the environment, once per process (conv.hip).  The forms behind the switches are
+// the references of the tests (each in a child process, held to the default's bars) or documented opt-ins.
+struct ConvSwitches {
+    int wino;            // DODT_CONV_WINO, dodt_conv_mode(): 2 (default) F(2x2,3x3), 4 F(4x4,3x3), 0 the direct kernels
+    bool deconv_dma;     // DODT_CONV_DECONV_DMA=0: transposed convs on the register-staged template
+    bool bf16_dma;       // DODT_CONV_BF16_DMA=0: bf16 3x3 convs on the register-staged template
+    bool bf16_stream;    // DODT_CONV_BF16_STREAM=0: the level-1 bf16 layers on the plain LDS-DMA kernel
+    bool bf16_first2;    // DODT_CONV_BF16_FIRST2=0: conv1_1 and conv1_2 as two launches
+    bool bf16_xcd;       // DODT_CONV_BF16_XCD=0: one work queue per launch, not one per group of blocks sharing an XCD
+    bool f32_xcd;        // DODT_CONV_F32_XCD=0: the same for the fp32 F(2x2) and transposed-conv kernels
+    int debug;           // DODT_CONV_DEBUG: ConvArgs::debug, the kernels' diagnostic bits
+    const char* stamp_layer;  // DODT_CONV_STAMP_LAYER=<name>: in-kernel step stamps of that layer's launch
+    bool debug_plan;     // DODT_DEBUG_PLAN: print the plan and the skip tables' counts
+};
+const ConvSwitches& conv_switches();
 
 inline KernelVariant tail_only(KernelVariant v) {
     v.tail_only = true;
@@ -52,7 +76,7 @@ struct Inst {
         int per_cu = Cfg::kMinWaves;  // one wave of each workgroup per SIMD
         const int by_lds = (160 * 1024) / Cfg::kLdsBytes;
         if (per_cu > by_lds) per_cu = by_lds;
-        KernelVariant v{TW, MTB, WM, WN, BN, BF16 ? 16 : kCK, DECONV, false, Cfg::TH,
+        KernelVariant v{TW, MTB, WM, WN, BN, BF16 ? 16 : kCK, DECONV, Family::Direct, Cfg::TH,
                         Cfg::kLdsBytes, per_cu, &launch, &prepare};
         v.bf16 = BF16;
         v.parts = PARTS;
@@ -72,11 +96,9 @@ struct InstWino {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::kLdsBytes);
     }
     static KernelVariant variant() {
-        // TW, MTB (unused), WM, WN, BN, CK, deconv, small_cin, TH, lds, blocks_per_cu
-        KernelVariant v{Cfg::TW, 0, 4, 1, Cfg::BN, kCK, false, false, Cfg::TH, Cfg::kLdsBytes,
-                        Cfg::kPipe ? 1 : 2, &launch, &prepare};
-        v.wino = true;
-        return v;
+        // TW, MTB (unused), WM, WN, BN, CK, deconv, family, TH, lds, blocks_per_cu
+        return KernelVariant{Cfg::TW, 0, 4, 1, Cfg::BN, kCK, false, Family::Wino22, Cfg::TH, Cfg::kLdsBytes,
+                             2, &launch, &prepare};
     }
 };
 
@@ -91,11 +113,8 @@ struct InstWino43 {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::kLdsBytes);
     }
     static KernelVariant variant() {
-        KernelVariant v{Cfg::TW, 0, 4, 1, Cfg::BN, kCK, false, false, Cfg::TH, Cfg::kLdsBytes, 1,
-                        &launch, &prepare};
-        v.wino = true;
-        v.wino_m = 4;
-        return v;
+        return KernelVariant{Cfg::TW, 0, 4, 1, Cfg::BN, kCK, false, Family::Wino43, Cfg::TH, Cfg::kLdsBytes, 1,
+                             &launch, &prepare};
     }
 };
 
@@ -110,9 +129,8 @@ struct InstDeconvDma {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::kLdsBytes);
     }
     static KernelVariant variant() {
-        KernelVariant v{Cfg::TW, 0, 4, 1, Cfg::BN, BF16 ? 16 : kCK, true, false, Cfg::TH, Cfg::kLdsBytes, 2,
+        KernelVariant v{Cfg::TW, 0, 4, 1, Cfg::BN, BF16 ? 16 : kCK, true, Family::DeconvDma, Cfg::TH, Cfg::kLdsBytes, 2,
                         &launch, &prepare};
-        v.deconv_dma = true;
         v.bf16 = BF16;
         return v;
     }
@@ -133,10 +151,9 @@ struct InstBf16Dma {
         int per_cu = (160 * 1024) / Cfg::kLdsBytes;
         constexpr int kMax = S == 2 ? (MT == 2 ? 3 : 2) : 1;      // the kernel's launch bounds
         if (per_cu > kMax) per_cu = kMax;
-        KernelVariant v{Cfg::TW, 4 * MT, 4, 1, Cfg::BN, 16, false, false, Cfg::TH, Cfg::kLdsBytes,
+        KernelVariant v{Cfg::TW, 4 * MT, 4, 1, Cfg::BN, 16, false, Family::Bf16Dma, Cfg::TH, Cfg::kLdsBytes,
                         per_cu, &launch, &prepare};
         v.bf16 = true;
-        v.dma = true;
         return v;
     }
 };
@@ -153,9 +170,9 @@ struct InstBf16Stream {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::kLdsBytes);
     }
     static KernelVariant variant() {
-        KernelVariant v{Cfg::TW, Cfg::TH, 3, 1, Cfg::BN, 16, false, false, Cfg::TH, Cfg::kLdsBytes, 2, &launch, &prepare};
+        KernelVariant v{Cfg::TW, Cfg::TH, 3, 1, Cfg::BN, 16, false, Family::Bf16Stream, Cfg::TH, Cfg::kLdsBytes, 2,
+                        &launch, &prepare};
         v.bf16 = true;
-        v.dma = true;
         v.stream_nch = NCH;
         return v;
     }
@@ -173,10 +190,10 @@ struct InstBf16First2 {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::kLdsBytes);
     }
     static KernelVariant variant() {
-        KernelVariant v{Cfg::TW, Cfg::TH, 3, 1, Cfg::BN, 16, false, false, Cfg::TH, Cfg::kLdsBytes, 2, &launch, &prepare};
+        KernelVariant v{Cfg::TW, Cfg::TH, 3, 1, Cfg::BN, 16, false, Family::Bf16First2, Cfg::TH, Cfg::kLdsBytes, 2,
+                        &launch, &prepare};
         v.bf16 = true;
-        v.dma = true;
-        v.first2 = CIN0;
+        v.first2_cin = CIN0;
         return v;
     }
 };
@@ -194,7 +211,8 @@ struct InstSmall {
             hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::kLdsBytes);
     }
     static KernelVariant variant() {
-        KernelVariant v{TW, MTB, 4, 1, 32, CK, false, true, Cfg::TH, Cfg::kLdsBytes, 4, &launch,
+        // (blocks_per_cu as dodt_conv_variant_info has always reported it; launch_grid: three by the kernel's registers)
+        KernelVariant v{TW, MTB, 4, 1, 32, CK, false, Family::SmallCin, Cfg::TH, Cfg::kLdsBytes, 4, &launch,
                         &prepare};
         v.bf16 = OUT16;
         v.parts = SPLIT ? 2 : 1;

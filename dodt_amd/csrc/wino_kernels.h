@@ -12,9 +12,9 @@
 // per-layer bar of tests/test_gpu_conv.py is 1e-4).
 //
 // Work decomposition (one workgroup = 4 waves = one 16-column x 16*TB-row output tile of one
-// frame x BN = 16*CB output channels; TB * CB = 4):
+// frame x BN = 16*CB output channels; TB * CB = 2):
 //   * a wave owns TB "tile blocks" (2 x 8 Winograd tiles = 4 x 16 output pixels each) and all
-//     BN channels: 16 points x TB x CB accumulators of v_mfma_f32_16x16x4_f32 = 256 registers.
+//     BN channels: 16 points x TB x CB accumulators of v_mfma_f32_16x16x4_f32 = 128 registers.
 //     Lane l: tile t = l % 16 of the block (B operand column), k-pair g = l / 16: the MFMA's
 //     four k lanes take the chunk's input channels (2g) in one instruction and (2g + 1) in the
 //     next, so every operand is ONE 8-byte LDS read (ds_read_b64) per two MFMAs.
@@ -45,11 +45,10 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 template <int TB, int CB>
 struct WinoCfg {
-    static_assert(TB * CB == 4 || TB * CB == 2, "256 or 128 accumulator registers per wave");
-    // 256 accumulator registers: one wave per SIMD, the step is software-pipelined inside the
-    // wave (kPipe).  128: two workgroups per CU, the partner wave on the SIMD fills the gaps, the
-    // step is the plain sequence copies -> input transform -> MFMAs.
-    static constexpr bool kPipe = TB * CB == 4;
+    // 128 accumulator registers per wave: two workgroups per CU, the partner wave on the SIMD fills the gaps, the
+    // step is the plain sequence copies -> input transform -> MFMAs.  (256 accumulators, one wave per SIMD and a
+    // step software-pipelined inside the wave, were no faster than the direct kernels: DESIGN.md section 5.)
+    static_assert(TB * CB == 2, "128 accumulator registers per wave");
     static constexpr int TW = 16;            // output columns of a workgroup tile
     static constexpr int TH = 16 * TB;       // output rows (4 waves x TB tile blocks x 4 rows)
     static constexpr int BN = 16 * CB;       // output channels of a workgroup tile
@@ -87,7 +86,7 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 
 
 template <int TB, int CB>
-__global__ void __launch_bounds__(256, (TB * CB == 4 ? 1 : 2))
+__global__ void __launch_bounds__(256, 2)
 wino3x3_f32_kernel(const ConvArgs a) {
     using Cfg = WinoCfg<TB, CB>;
     constexpr int BN = Cfg::BN, PW = Cfg::PW;
@@ -241,7 +240,7 @@ wino3x3_f32_kernel(const ConvArgs a) {
         v[i * 4 + 3] = d[i][1] - d[i][3];
     };
 
-    // ---- prologue: patch(0), W(0) [, patch(1); V(0)] ---------------------------------------------
+    // ---- prologue: patch(0), W(0) ---------------------------------------------------------------
     pit = wit = comp_item;
     setup_patch(decode(pit));
     setup_w(decode(wit));
@@ -251,158 +250,81 @@ wino3x3_f32_kernel(const ConvArgs a) {
 #pragma unroll
     for (int n = Cfg::kPatchPerWave; n < kCopies; ++n) copy_n(n, 0, 0);
     advance(wit, wch, false);
-    if constexpr (Cfg::kPipe) {
-#pragma unroll
-        for (int n = 0; n < Cfg::kPatchPerWave; ++n) copy_n(n, 1, 0);
-        advance(pit, pch, true);
-    }
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
-    f32x2_t va[TB][16], vb[Cfg::kPipe ? TB : 1][16];
-    if constexpr (Cfg::kPipe) {
-#pragma unroll
-        for (int tb = 0; tb < TB; ++tb) {
-            f32x2_t d[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) load_d(d, tb, r, 0);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) rows_d(d, c);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) cols_d(d, va[tb], i);
-        }
-        __syncthreads();      // patch image 0 is free for patch(2)
-    }
 
-    // One step = the MFMAs of chunk k (V from registers, weights from weight image k & 1) and,
-    // spread between them: the copies of W(k+1) -> weight image (k+1) & 1 and patch(k+2) ->
-    // patch image k & 1, and the input transform of chunk k+1 from patch image (k+1) & 1.
-    // PAR = k & 1 (the chunk loop is unrolled by two so that images and V sets are static).
+    // One step = per tile block the input transform of chunk k (patch image k & 1) and its MFMAs (weights from
+    // weight image k & 1), and, spread between them, the copies of chunk k+1 into both images (k+1) & 1.
+    // PAR = k & 1 (the chunk loop is unrolled by two so that the images are static).
     int k_stamp = 0;      // steps this wave has run (diagnostic stamps)
-    auto step = [&](auto par, f32x4 (&acc)[TB][CB][16], auto& vcur, auto& vnext, int comp_ch) {
+    auto step = [&](auto par, f32x4 (&acc)[TB][CB][16], int comp_ch) {
         constexpr int PAR = decltype(par)::value;
         if (comp_ch == 0 && tid == 0) {
             const int t = q_first + atomicAdd(q_counter, 1);
             s_ctrl[0] = t < q_hi ? t : n_items;
         }
         const float* sW = sWB + PAR * Cfg::kWFloats + w_lane;
-        f32x2_t d[4][4];
-        if constexpr (!Cfg::kPipe) {
-            // plain step: copies of chunk k+1 (both images PAR ^ 1), then per tile block the
-            // input transform of chunk k and its MFMAs.
-            // (a.debug: diagnostic switches of tools/, 0 in production -- 2: no copies; 32:
-            //  s_memtime stamps of one wave's first 12 steps into counter_base[32..103])
-            const bool stamp = (a.debug & 32) && blockIdx.x == 1 && tid == 0 && k_stamp < 12;
-            int* stamps = a.counter_base + 32 + (k_stamp < 12 ? k_stamp : 0) * 6;
-            if (stamp) {
-                stamps[0] = (int)__builtin_amdgcn_s_memtime();
-                if (k_stamp == 0 || k_stamp == 11)    // 100 MHz reference beside it, to calibrate
-                    a.counter_base[32 + 72 + (k_stamp != 0)] = (int)__builtin_amdgcn_s_memrealtime();
-            }
-            // The copies of chunk k+1 (both images PAR ^ 1: free since the barrier that ended the previous step)
-            // go out one per point over the first points of the MFMA loop below (so that they have the rest of the
-            // step to land), with scalar operands only, in the matrix pipe's shadow -- issued as one burst at the top of the step (round 2) they held this wave's MFMAs back by
-            // their issue time, 400-790 cycles of a 4 800-cycle step.
-            if (stamp) stamps[1] = (int)__builtin_amdgcn_s_memtime();
-#pragma unroll
-            for (int tb = 0; tb < TB; ++tb) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) load_d(d, tb, r, PAR);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) rows_d(d, c);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) cols_d(d, vnext[0], i);
-                if (stamp) {
-                    // make the transform's end observable: the stamp depends on its result
-                    stamps[2] = (int)__builtin_amdgcn_s_memtime() + (vnext[0][15][1] == 12345.f);
-                }
-                // weight fragments two points ahead of the MFMAs that use them (the scheduling barriers that
-                // pin the copies would otherwise leave each read's latency in front of its MFMAs)
-                constexpr int kWAhead = 2;
-                f32x4 wq[kWAhead + 1][CB / 2];
-#pragma unroll
-                for (int i = 0; i < kWAhead; ++i)
-#pragma unroll
-                    for (int cp = 0; cp < CB / 2; ++cp)
-                        wq[i][cp] = *reinterpret_cast<const f32x4*>(sW + (i * 4 * (CB / 2) + cp) * 64);
-#pragma unroll
-                for (int x = 0; x < 16; ++x) {
-                    if (x + kWAhead < 16) {
-#pragma unroll
-                        for (int cp = 0; cp < CB / 2; ++cp)
-                            wq[(x + kWAhead) % (kWAhead + 1)][cp] =
-                                *reinterpret_cast<const f32x4*>(sW + ((x + kWAhead) * 4 * (CB / 2) + cp) * 64);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                        for (int cb = 0; cb < CB; ++cb)
-                            acc[tb][cb][x] = mfma16(wq[x % (kWAhead + 1)][cb >> 1][(cb & 1) * 2 + s2], vnext[0][x][s2],
-                                                    acc[tb][cb][x]);
-                    if (tb == 0 && x < kCopies && !(a.debug & 2)) copy_s(x, PAR ^ 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            if (stamp) stamps[3] = (int)__builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_waitcnt(0);
-            if (stamp) stamps[4] = (int)__builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_barrier();
-            if (stamp) stamps[5] = (int)__builtin_amdgcn_s_memtime();
-            ++k_stamp;
-            if (comp_ch == 0) q0 = s_ctrl[0];
-            advance(pit, pch, true);
-            advance(wit, wch, false);
-            return;
-        } else {
-        // weight fragments are read one slice ahead of the MFMAs that use them (the slices are
-        // pinned by scheduling barriers, so nothing else prefetches them)
-        f32x4 w[2][CB / 2];
-#pragma unroll
-        for (int cp = 0; cp < CB / 2; ++cp)
-            w[0][cp] = *reinterpret_cast<const f32x4*>(sW + cp * 64);
+        f32x2_t d[4][4], v[16];     // the lane's input tile and its transform: they live inside a step
+        // (a.debug: diagnostic switches of tools/, 0 in production -- 2: no copies; 32:
+        //  s_memtime stamps of one wave's first 12 steps into counter_base[32..103])
+        const bool stamp = (a.debug & 32) && blockIdx.x == 1 && tid == 0 && k_stamp < 12;
+        int* stamps = a.counter_base + 32 + (k_stamp < 12 ? k_stamp : 0) * 6;
+        if (stamp) {
+            stamps[0] = (int)__builtin_amdgcn_s_memtime();
+            if (k_stamp == 0 || k_stamp == 11)    // 100 MHz reference beside it, to calibrate
+                a.counter_base[32 + 72 + (k_stamp != 0)] = (int)__builtin_amdgcn_s_memrealtime();
+        }
+        // The copies of chunk k+1 (both images PAR ^ 1: free since the barrier that ended the previous step)
+        // go out one per point over the first points of the MFMA loop below (so that they have the rest of the
+        // step to land), with scalar operands only, in the matrix pipe's shadow -- issued as one burst at the top of the step (round 2) they held this wave's MFMAs back by
+        // their issue time, 400-790 cycles of a 4 800-cycle step.
+        if (stamp) stamps[1] = (int)__builtin_amdgcn_s_memtime();
 #pragma unroll
         for (int tb = 0; tb < TB; ++tb) {
 #pragma unroll
+            for (int r = 0; r < 4; ++r) load_d(d, tb, r, PAR);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) rows_d(d, c);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cols_d(d, v, i);
+            if (stamp) {
+                // make the transform's end observable: the stamp depends on its result
+                stamps[2] = (int)__builtin_amdgcn_s_memtime() + (v[15][1] == 12345.f);
+            }
+            // weight fragments two points ahead of the MFMAs that use them (the scheduling barriers that
+            // pin the copies would otherwise leave each read's latency in front of its MFMAs)
+            constexpr int kWAhead = 2;
+            f32x4 wq[kWAhead + 1][CB / 2];
+#pragma unroll
+            for (int i = 0; i < kWAhead; ++i)
+#pragma unroll
+                for (int cp = 0; cp < CB / 2; ++cp)
+                    wq[i][cp] = *reinterpret_cast<const f32x4*>(sW + (i * 4 * (CB / 2) + cp) * 64);
+#pragma unroll
             for (int x = 0; x < 16; ++x) {
-                const int sl = tb * 16 + x;                       // slice number, 0 .. 16 TB - 1
-                const int wc = sl & 1, wn = wc ^ 1;
-                if (sl + 1 < 16 * TB) {
-                    const int xn = (x + 1) & 15;
+                if (x + kWAhead < 16) {
 #pragma unroll
                     for (int cp = 0; cp < CB / 2; ++cp)
-                        w[wn][cp] = *reinterpret_cast<const f32x4*>(
-                            sW + (xn * 4 * (CB / 2) + cp) * 64);
+                        wq[(x + kWAhead) % (kWAhead + 1)][cp] =
+                            *reinterpret_cast<const f32x4*>(sW + ((x + kWAhead) * 4 * (CB / 2) + cp) * 64);
                 }
-                // transform of chunk k+1, tile block tb: loads in slices 0..3, rows 5..8,
-                // columns 10..13 of this tile block's 16 slices (issued ahead of the MFMAs of
-                // the slice, in whose shadow they run)
-                if (x <= 3) load_d(d, tb, x, PAR ^ 1);
-                if (x >= 5 && x <= 8) rows_d(d, x - 5);
-                if (x >= 10 && x <= 13) cols_d(d, vnext[tb], x - 10);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
                     for (int cb = 0; cb < CB; ++cb)
-                        acc[tb][cb][x] = mfma16(w[wc][cb >> 1][(cb & 1) * 2 + s2],
-                                                vcur[tb][x][s2], acc[tb][cb][x]);
-                if (sl < kCopies) copy_n(sl, PAR, PAR ^ 1);       // patch(k+2) -> PAR, W(k+1) -> PAR^1
-                // One wave per SIMD issues in order: whatever follows a burst of MFMAs waits for
-                // the whole burst.  Interleave: after every MFMA (32 cycles in the matrix pipe)
-                // two vector instructions and one LDS read of the slice's side work.
-#pragma unroll
-                for (int i = 0; i < 2 * CB; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // VALU
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
-                }
+                        acc[tb][cb][x] = mfma16(wq[x % (kWAhead + 1)][cb >> 1][(cb & 1) * 2 + s2], v[x][s2],
+                                                acc[tb][cb][x]);
+                if (tb == 0 && x < kCopies && !(a.debug & 2)) copy_s(x, PAR ^ 1);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        }
-        // the copies issued in this step have landed (they are waited for ahead of an epilogue's
-        // stores, which share the vmcnt counter); then one barrier per chunk
+        if (stamp) stamps[3] = (int)__builtin_amdgcn_s_memtime();
         __builtin_amdgcn_s_waitcnt(0);
+        if (stamp) stamps[4] = (int)__builtin_amdgcn_s_memtime();
         __builtin_amdgcn_s_barrier();
+        if (stamp) stamps[5] = (int)__builtin_amdgcn_s_memtime();
+        ++k_stamp;
         if (comp_ch == 0) q0 = s_ctrl[0];
         advance(pit, pch, true);
         advance(wit, wch, false);
@@ -418,13 +340,8 @@ wino3x3_f32_kernel(const ConvArgs a) {
                 for (int x = 0; x < 16; ++x) acc[tb][cb][x] = f32x4{0.f, 0.f, 0.f, 0.f};
 
         for (int comp_ch = 0; comp_ch < nchunks; comp_ch += 2) {     // Cin / 8 is even
-            if constexpr (Cfg::kPipe) {
-                step(std::integral_constant<int, 0>{}, acc, va, vb, comp_ch);
-                step(std::integral_constant<int, 1>{}, acc, vb, va, comp_ch + 1);
-            } else {      // (V lives only inside a step: `va` is scratch for it)
-                step(std::integral_constant<int, 0>{}, acc, vb, va, comp_ch);
-                step(std::integral_constant<int, 1>{}, acc, vb, va, comp_ch + 1);
-            }
+            step(std::integral_constant<int, 0>{}, acc, comp_ch);
+            step(std::integral_constant<int, 1>{}, acc, comp_ch + 1);
         }
 
         // ---- epilogue: Y = A^T M A, batch-norm + ReLU, stores (they drain under the next

@@ -233,10 +233,11 @@ typedef struct dodt_extractor dodt_extractor;
  * (tests/test_gpu_conv_split.py runs them at the fp32 tolerances). */
 #define DODT_EXTRACTOR_SPLIT 0x400
 /* Form of the fp32 3x3 stride-1 layers (everything else has one kernel): 4 = Winograd F(4x4,3x3),
- * 2 = Winograd F(2x2,3x3), 1 = its one-workgroup-per-CU variants, 0 = direct implicit GEMM.  All are
+ * 2 = Winograd F(2x2,3x3), 0 = direct implicit GEMM.  All are
  * fp32 throughout and within the 1e-4 layer bar; they differ in speed and in how far the rounding
  * noise of a whole stack lies from the exact sums (DESIGN.md 2 / 5.0 give both, and the rule that
- * chose the default).  DODT_CONV_WINO in the environment overrides the default, once per process. */
+ * chose the default).  DODT_CONV_WINO in the environment overrides the default, once per process;
+ * any other value is the default. */
 #define DODT_CONV_MODE_DEFAULT 2
 int dodt_conv_mode(void);
 /* in_c: channels of the input tensor as stored (6 for BEV; 4 for the padded

@@ -21,11 +21,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = collections.OrderedDict([
     ('default', {}),
     ('wino0', {'DODT_CONV_WINO': '0'}),
-    ('wino1', {'DODT_CONV_WINO': '1'}),
     ('wino4', {'DODT_CONV_WINO': '4'}),
     ('deconv_direct', {'DODT_CONV_DECONV_DMA': '0'}),
     ('bf16_template', {'DODT_CONV_BF16_DMA': '0'}),
     ('one_queue', {'DODT_CONV_BF16_XCD': '0', 'DODT_CONV_F32_XCD': '0'}),
+])
+# two more forms a switch keeps, planned for the pin of tests/golden/conv_plans.json only (the device tests run them
+# from tests/test_gpu_conv_bf16.py): the level-1 layers without the streaming kernel, conv1_1 and conv1_2 as two launches
+PIN_MODES = collections.OrderedDict([
+    ('no_stream', {'DODT_CONV_BF16_STREAM': '0'}),
+    ('two_launch', {'DODT_CONV_BF16_FIRST2': '0'}),
 ])
 # every switch of the conv path a mode does not set must be unset: the plans are the library's defaults
 CONV_SWITCH_PREFIX = 'DODT_CONV_'
@@ -71,7 +76,7 @@ CASES = [
     Case('bev_plain', 'f32', 33, 42, 3, 8, 'wino0'),      # (a frame is whole float4s: 33 x 41 x 6 is not)
     Case('bev', 'f32', 104, 72, 1, 8, 'wino0'),
     Case('bev', 'f32', 200, 72, 2, 8, 'wino0'),
-    Case('img', 'f32', 32, 48, 1, 8, 'wino1'),
+    Case('img', 'f32', 32, 48, 1, 8, 'wino0'),            # (the fp32 first-layer kernel's 16 x 32 tile of four channels)
     Case('bev', 'f32', 24, 40, 1, 8, 'wino4'),
     Case('bev', 'f32', 40, 104, 3, 8, 'wino4'),
     # the register-staged transposed convs, fp32 and bf16
@@ -117,7 +122,7 @@ def host_plan(c):
 
 def mode_env(mode):
     env = {k: v for k, v in os.environ.items() if not k.startswith(CONV_SWITCH_PREFIX)}
-    env.update(MODES[mode])
+    env.update(MODES[mode] if mode in MODES else PIN_MODES[mode])
     return env
 
 
@@ -144,7 +149,7 @@ def _plans_of_mode(mode, cases):
 def plans(cases):
     """{case: plan} and the variant table per mode, every mode's plans computed in one child process of that mode."""
     out, variants = {}, {}
-    for mode in MODES:
+    for mode in list(MODES) + list(PIN_MODES):
         mine = tuple(c for c in cases if c.mode == mode)
         if not mine:
             continue
@@ -181,9 +186,65 @@ def family(v):
     return 'direct' + d
 
 
+def signature(v):
+    """A variant by what it is, not by its place in the table."""
+    from dodt_amd import _lib
+    names = [(_lib.VARIANT_DECONV, 'deconv'), (_lib.VARIANT_SMALL_CIN, 'small'), (_lib.VARIANT_TAIL_ONLY, 'tail'),
+             (_lib.VARIANT_BF16, 'bf16'), (_lib.VARIANT_SPLIT, 'split')]
+    return '%s %dx%d bn%d ck%d lds%d%s' % (v['kernel'], v['tw'], v['th'], v['bn'], v['ck'], v['lds_bytes'],
+                                           ''.join(' ' + n for bit, n in names if v['flags'] & bit))
+
+
 def launches(plan):
     """(layer record, 0 main / 1 tail, variant index) of every launch of a plan."""
     return [(r, j, r['variant'][j]) for r in plan for j in (0, 1) if r['variant'][j] >= 0]
+
+
+# ---- the pinned plans (tests/golden/conv_plans.json) ----------------------------------------------------------
+
+# the non-default modes a data type's plans can feel: fp32 layers take Winograd and the fp32 grouped queues, the
+# LDS-DMA transposed conv serves fp32 and bf16 (split stays on the template), the rest is bf16 only
+MODES_FELT = {
+    'f32': ('wino0', 'wino4', 'deconv_direct', 'one_queue'),
+    'f32s': (),
+    'bf16': ('deconv_direct', 'bf16_template', 'one_queue', 'no_stream', 'two_launch'),
+}
+PIN_BATCHES, PIN_CUS = (1, 2, 4, 10), (8, 64, 128, 256)
+LAYER_NAMES = ['conv1_1', 'conv1_2', 'conv2_1', 'conv2_2', 'conv3_1', 'conv3_2', 'conv3_3', 'conv4_1', 'conv4_2',
+               'conv4_3', 'upconv3', 'pyramid_fusion3', 'upconv2', 'pyramid_fusion2', 'upconv1', 'pyramid_fusion1']
+
+
+def pin_configs():
+    """Every configuration whose plan is pinned: the cases and the bench rows in their own mode, the bench rows in
+    every other mode their data type can feel, the bench shapes over PIN_BATCHES x PIN_CUS."""
+    out = list(CASES + BENCH)
+    out += [c._replace(mode=m) for c in BENCH for m in MODES_FELT[c.dtype]]
+    out += [c._replace(batch=b, cus=n) for c in BENCH if c.batch == 2 for b in PIN_BATCHES for n in PIN_CUS]
+    return list(collections.OrderedDict.fromkeys(out))
+
+
+def pin_record(plan, variants, intern):
+    """A plan as the golden file holds it: per layer [main, tail, items, grid, pool_fused, bneck_fused, folded] with
+    the two variants as intern(signature) (-1: no launch), never as table indices."""
+    assert [r['name'] for r in plan] == LAYER_NAMES[:len(plan)]
+    sig = lambda vi: intern(signature(variants[vi])) if vi >= 0 else -1
+    return [[sig(r['variant'][0]), sig(r['variant'][1]), r['items'], r['grid'], int(r['pool_fused']),
+             int(r['bneck_fused']), int(r['folded'])] for r in plan]
+
+
+def pinned_plans():
+    """What tests/golden/conv_plans.json holds, computed from the library as built: the interned signatures in
+    order of first use and {case id: pin_record}."""
+    configs = pin_configs()
+    got, variants = plans(configs)
+    sigs = []
+
+    def intern(s):
+        if s not in sigs:
+            sigs.append(s)
+        return sigs.index(s)
+    return dict(signatures=sigs, layers=LAYER_NAMES,
+                plans=collections.OrderedDict((case_id(c), pin_record(got[c], variants[c.mode], intern)) for c in configs))
 
 
 # ---- inputs and weights -------------------------------------------------------------------------------------

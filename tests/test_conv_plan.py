@@ -14,6 +14,9 @@ plan_cus=)); this file computes their plans with dodt_conv_plan_host and asserts
 
 tests/test_gpu_conv_paths.py runs the same cases on the device; a table entry added without a case that reaches
 it, or a case that stops walking several items, fails here first."""
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -24,39 +27,14 @@ from oracle import tfops
 POOLED = ('conv1_2', 'conv2_2', 'conv3_3')
 
 
-def signature(v):
-    """A variant by what it is, not by its place in the table."""
-    names = [(_lib.VARIANT_DECONV, 'deconv'), (_lib.VARIANT_SMALL_CIN, 'small'), (_lib.VARIANT_TAIL_ONLY, 'tail'),
-             (_lib.VARIANT_BF16, 'bf16'), (_lib.VARIANT_SPLIT, 'split')]
-    return '%s %dx%d bn%d ck%d lds%d%s' % (v['kernel'], v['tw'], v['th'], v['bn'], v['ck'], v['lds_bytes'],
-                                           ''.join(' ' + n for bit, n in names if v['flags'] & bit))
+signature = cc.signature
 
-
-_ROUND_MODEL = ('bf16 and split layers are picked by the round model (pick_variant): ceil(items / CUs) x MFMA units.  '
-                'A 64-channel transposed tile has twice the units of the 32-channel tile of the same pixels and half '
-                'the items, ceil(2a / c) <= 2 ceil(a / c), and the 32-channel entry stands first in the table: it '
-                'wins every tie.  Only DODT_CONV_ROUND_MODEL=0 selects these.')
-_STREAM_LDS = ('a shallower ring of the streaming kernels: chosen only under DODT_CONV_BF16_STREAM_LDS=<KB>, which is '
-               'no mode of this table (tests/test_gpu_variants.py runs the bf16 tests with 72)')
 # variants no case of the table can select, each with the reason
 UNREACHABLE = {
-    'conv3x3_mfma_kernel 16x8 bn64 ck16 lds55312 deconv bf16': _ROUND_MODEL,
-    'conv3x3_mfma_kernel 8x16 bn64 ck16 lds58640 deconv bf16': _ROUND_MODEL,
-    'conv3x3_mfma_kernel 4x32 bn64 ck16 lds58000 deconv bf16': _ROUND_MODEL,
-    'conv3x3_mfma_kernel 16x8 bn64 ck16 lds110608 deconv bf16 split': _ROUND_MODEL,
-    'conv3x3_mfma_kernel 8x16 bn64 ck16 lds117264 deconv bf16 split': _ROUND_MODEL,
-    'conv3x3_mfma_kernel 4x32 bn64 ck16 lds115984 deconv bf16 split': _ROUND_MODEL,
     'conv3x3_bf16_stream_kernel 32x6 bn32 ck16 lds74176 bf16':
         'conv1_2 of a bf16 net (two input chunks); by default conv1_1 runs folded into its launch, on the first2 '
         'kernel with the same tiles and ring.  Only DODT_CONV_BF16_FIRST2=0 launches this entry '
         '(tests/test_gpu_conv_bf16.py::test_two_launch_first_layers_match_the_same_bars).',
-    'conv3x3_bf16_stream_kernel 32x6 bn32 ck16 lds46528 bf16': _STREAM_LDS,
-    'conv3x3_bf16_stream_kernel 32x6 bn32 ck16 lds28096 bf16': _STREAM_LDS,
-    'conv3x3_bf16_stream_kernel 32x6 bn32 ck16 lds60352 bf16': _STREAM_LDS,
-    'conv3x3_bf16_stream_kernel 32x6 bn32 ck16 lds51136 bf16': _STREAM_LDS,
-    'conv3x3_bf16_first2_kernel 32x6 bn32 ck16 lds69760 bf16': _STREAM_LDS,
-    'conv3x3_bf16_first2_kernel 32x6 bn32 ck16 lds55136 bf16': _STREAM_LDS,
-    'conv3x3_bf16_first2_kernel 32x6 bn32 ck16 lds48992 bf16': _STREAM_LDS,
 }
 
 # Families whose workgroups cannot walk four items under the default rule, with the reason and the bound that is
@@ -233,6 +211,25 @@ def test_grids_are_what_a_launch_takes(planned):
             assert plans[c][0]['variant'] == [-1, -1] and plans[c][0]['grid'] == [0, 0]
             assert variants[c.mode][plans[c][1]['variant'][0]]['flags'] & _lib.VARIANT_FIRST2
             assert plans[c][1]['pool_fused']
+
+
+def test_plans_are_the_pinned_plans():
+    """The planner decides what tests/golden/conv_plans.json records: per layer of every pinned configuration the main
+    and the tail kernel (by signature), items, grid, pool_fused, bneck_fused, folded.  A change of the selection
+    code that means to keep every choice passes against the file as it stands (tests/golden/make_conv_plans.py)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'conv_plans.json')) as f:
+        want = json.load(f)
+    got = json.loads(json.dumps(cc.pinned_plans()))
+    assert list(got['plans']) == list(want['plans'])
+    assert len(want['plans']) >= len(cc.CASES + cc.BENCH) + 2 * len(cc.PIN_BATCHES) * len(cc.PIN_CUS)
+
+    def named(pinned, rec):      # a layer's record with its two variants as text
+        return [pinned['signatures'][i] if i >= 0 else None for i in rec[:2]] + rec[2:]
+    for cid in want['plans']:
+        for name, w, g in zip(want['layers'], want['plans'][cid], got['plans'][cid]):
+            assert named(got, g) == named(want, w), (cid, name)
+        assert len(got['plans'][cid]) == len(want['plans'][cid]), cid
+    assert got == want          # ... and the file is what the generator writes
 
 
 def test_plan_host_refuses_what_create_refuses():

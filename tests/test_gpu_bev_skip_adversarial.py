@@ -308,11 +308,10 @@ def _run_all():
         _run_signed_zero(kind)
 
 
-@pytest.mark.parametrize('mode', ['0', '1', '4'])
+@pytest.mark.parametrize('mode', ['0', '4'])
 def test_other_conv_forms_in_child_process(mode):
-    """DODT_CONV_WINO is read once per process: the direct kernels (0), the 256-accumulator F(2x2,3x3) (1) and
-    F(4x4,3x3) (4, static tables only: the hand-made masks are what reaches its block-wise rule), one fresh child
-    each."""
+    """DODT_CONV_WINO is read once per process: the direct kernels (0) and F(4x4,3x3) (4, static tables only: the
+    hand-made masks are what reaches its block-wise rule), one fresh child each."""
     env = dict(os.environ, DODT_CONV_WINO=mode)
     code = ('import sys; sys.path.insert(0, %r); import tests.test_gpu_bev_skip_adversarial as t; '
             't._run_all(); print("ok")' % ROOT)

@@ -19,14 +19,8 @@ VARIANTS = [
     ({'DODT_CORR_HALVES': '2'}, ['tests/test_gpu_heads.py', '-k', 'correlation']),
     ({'DODT_CORR_TWO_PASS': '1'}, ['tests/test_gpu_heads.py', '-k', 'correlation']),
     # one work queue per launch instead of one per group of blocks that share an XCD
-    # bf16 convs: 16-row tiles also where the map gives fewer than 1.6 items per CU (the small test maps otherwise
-    # all take the 8-row tiles)
-    ({'DODT_CONV_BF16_MT2': '0'}, ['tests/test_gpu_conv_bf16.py']),
-    ({'DODT_CONV_BF16_MT2_RULE': 'rounds'}, ['tests/test_gpu_conv_bf16.py', '-k', 'all_layers']),
     ({'DODT_CONV_BF16_XCD': '0', 'DODT_CONV_F32_XCD': '0'},
      ['tests/test_gpu_conv_bf16.py', 'tests/test_gpu_conv.py', '-k', 'not other_fp32']),
-    # the streaming bf16 kernels with shallower rings (the default takes the deepest that fits twice per CU)
-    ({'DODT_CONV_BF16_STREAM_LDS': '72'}, ['tests/test_gpu_conv_bf16.py', '-k', 'all_layers']),
     # the tail's elementwise ops as separate launches; the correlation map inside frame 1's tail (round 4's first form)
     ({'DODT_PIPE_FUSED_TAIL': '0', 'DODT_PIPE_CORR_MAP': 'f1'},
      ['tests/test_gpu_heads.py', 'tests/test_gpu_pipeline.py', '-k', 'stagewise or lookahead or pipelined']),
