@@ -89,9 +89,16 @@ struct InstWino {
     using Cfg = WinoCfg<TB, CB>;
     static_assert(Cfg::kLdsBytes <= 160 * 1024, "variant does not fit the LDS");
     static void launch(const ConvArgs& a, dim3 grid, hipStream_t s) {
-        hipLaunchKernelGGL((wino3x3_f32_kernel<TB, CB>), grid, dim3(256), Cfg::kLdsBytes, s, a);
+        // the kernel's diagnostic bits (no epilogue, no copies, stamps) exist in an instantiation of their own
+        if (conv_switches().debug || conv_switches().stamp_layer)
+            hipLaunchKernelGGL((wino3x3_f32_kernel<TB, CB, true>), grid, dim3(256), Cfg::kLdsBytes, s, a);
+        else
+            hipLaunchKernelGGL((wino3x3_f32_kernel<TB, CB>), grid, dim3(256), Cfg::kLdsBytes, s, a);
     }
     static hipError_t prepare() {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino3x3_f32_kernel<TB, CB, true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::kLdsBytes);
+        if (e != hipSuccess) return e;
         return hipFuncSetAttribute(reinterpret_cast<const void*>(&wino3x3_f32_kernel<TB, CB>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::kLdsBytes);
     }

@@ -23,9 +23,11 @@
 //     global_load_lds_dwordx4 (no staging registers, no ds_write pass; out-of-image pixels read
 //     a zero page), double buffered: chunk k+1 lands while chunk k is computed, one barrier
 //     per chunk.  The chunk sequence runs across work items (persistent workgroups).
-//   * per chunk a lane reads its tile's 4x4 pixels (16 ds_read_b64), applies B^T d B (64 VALU
-//     adds, in the shadow of the other tile block's MFMAs), then issues 32 MFMAs per tile block
-//     and channel block pair.
+//   * per chunk a lane reads its tile's 4x4 pixels (16 ds_read_b64, un-paired: inline asm with
+//     counted waits), applies B^T d B (32 packed adds on two channels each, ONE burst in front of
+//     the MFMAs: vector instructions and fp32 MFMAs of a SIMD do not overlap, and every group of
+//     them inside the MFMA stream pays a switch), then issues its 64 MFMAs (16 points x 2 channel
+//     blocks x 2 k-steps) with only weight reads, waits and the next chunk's copies between them.
 //   * epilogue: A^T M A per lane (it holds all 16 points of its tile and 4 consecutive output
 //     channels per channel block), batch-norm scale/shift + ReLU, 16-byte stores into the CB8
 //     (or NHWC) output.  A lane's 2x2 outputs are exactly one window of a following 2x2 max
@@ -84,11 +86,34 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
+// The step's LDS reads are inline asm, one instruction per statement, and `asm volatile` keeps them in source
+// order.  The compiler does not see them: it neither pairs them (it made six ds_read2_b64 of twelve of the
+// sixteen patch reads; ds_read2_b64 is served at half the rate of the ds_read_b64 the patch image's swizzle is
+// laid out for) nor waits for them -- wait_lgkm does, and names the destinations so that no use moves above the
+// wait.  Other LDS or scalar-memory operations in flight only make a counted wait stricter: LDS returns in order.
+// Between a read and its wait the destination counts as written for the compiler: the emitted step must show no
+// v_mov or spill of those registers there (it has none; profiles/wino22_kloop_summary.md says how to look).
+// (off, n: constants once the step is unrolled)
+__device__ __forceinline__ void lds_read64(wino_f32x2& d, int off, unsigned addr) {
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(off));
+}
+__device__ __forceinline__ void lds_read128(f32x4& d, int off, unsigned addr) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(off));
+}
+__device__ __forceinline__ void wait_lgkm(int n, wino_f32x2& a, wino_f32x2& b, wino_f32x2& c, wino_f32x2& d) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(n));
+}
+__device__ __forceinline__ void wait_lgkm(int n, f32x4& a) {
+    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(n));
+}
 
-template <int TB, int CB>
+// kDiag: the instantiation DODT_CONV_DEBUG / DODT_CONV_STAMP_LAYER run (a.debug bits 1: no epilogue, 2: no copies,
+// 32: step stamps).  The production instantiation has none of them: its step is one basic block.
+template <int TB, int CB, bool kDiag = false>
 __global__ void __launch_bounds__(256, 2)
 wino3x3_f32_kernel(const ConvArgs a) {
     using Cfg = WinoCfg<TB, CB>;
+    static_assert(TB == 1 && CB == 2, "one weight fragment (ds_read_b128) per point, 14 LDS reads in flight");
     constexpr int BN = Cfg::BN, PW = Cfg::PW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int* s_ctrl = reinterpret_cast<int*>(smem + 2 * Cfg::kBufFloats);   // behind the four images
@@ -202,43 +227,27 @@ wino3x3_f32_kernel(const ConvArgs a) {
         }
     };
 
-    // lane constants: tile of the lane inside a tile block, weight fragment offset,
-    // float offsets of the lane's 4x4 input tile in the patch image (see WinoCfg)
+    // lane constants: tile of the lane inside a tile block, weight fragment address, byte addresses of the
+    // lane's 4x4 input tile in patch image 0 (see WinoCfg).  Row r + 1 of an even row r lies one image row
+    // (kRowBytes) behind it -- the row's shift (py >> 1) & 1 is the same -- and image 1 kImgBytes behind image 0:
+    // both are immediates of the reads, so a tile block's sixteen taps take eight address registers.
     const int tyl = t >> 3, txl = t & 7;
     const int w_lane = (g * (CB / 2) * 16 + t) * 4;
-    int row_off[TB][4], col_off[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int px = 2 * txl + c;
-        col_off[c] = px * 8 + (((g >> 1) ^ ((px >> 3) & 1)) * 4) + (g & 1) * 2;
-    }
+    constexpr int kRowBytes = Cfg::kPitch * 32, kImgBytes = Cfg::kPatchFloats * 4;
+    const unsigned w_addr = lds0 + (unsigned)(2 * Cfg::kPatchFloats + w_lane) * 4;
+    unsigned tap[TB][2][4];
 #pragma unroll
     for (int tb = 0; tb < TB; ++tb)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int py = 2 * (2 * (wave * TB + tb) + tyl) + r;
-            row_off[tb][r] = (py * Cfg::kPitch + ((py >> 1) & 1)) * 8;
-        }
-
-    // input transform V = B^T d B of the lane's tile in tile block tb from patch image pb,
-    // split in the pieces the main loop spreads between its MFMAs
-    auto load_d = [&](f32x2_t (&d)[4][4], int tb, int r, int pb) {
+        for (int rh = 0; rh < 2; ++rh)
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-            d[r][c] = *reinterpret_cast<const f32x2_t*>(sPB + pb * Cfg::kPatchFloats +
-                                                          row_off[tb][r] + col_off[c]);
-    };
-    auto rows_d = [&](f32x2_t (&d)[4][4], int c) {
-        const f32x2_t t0 = d[0][c] - d[2][c], t1 = d[1][c] + d[2][c];
-        const f32x2_t t2 = d[2][c] - d[1][c], t3 = d[1][c] - d[3][c];
-        d[0][c] = t0; d[1][c] = t1; d[2][c] = t2; d[3][c] = t3;
-    };
-    auto cols_d = [&](const f32x2_t (&d)[4][4], f32x2_t (&v)[16], int i) {
-        v[i * 4 + 0] = d[i][0] - d[i][2];
-        v[i * 4 + 1] = d[i][1] + d[i][2];
-        v[i * 4 + 2] = d[i][2] - d[i][1];
-        v[i * 4 + 3] = d[i][1] - d[i][3];
-    };
+            for (int c = 0; c < 4; ++c) {
+                const int py = 2 * (2 * (wave * TB + tb) + tyl) + 2 * rh;
+                const int px = 2 * txl + c;
+                const int row_off = (py * Cfg::kPitch + ((py >> 1) & 1)) * 8;
+                const int col_off = px * 8 + (((g >> 1) ^ ((px >> 3) & 1)) * 4) + (g & 1) * 2;
+                tap[tb][rh][c] = lds0 + (unsigned)(row_off + col_off) * 4;
+            }
 
     // ---- prologue: patch(0), W(0) ---------------------------------------------------------------
     pit = wit = comp_item;
@@ -253,9 +262,11 @@ wino3x3_f32_kernel(const ConvArgs a) {
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
 
-    // One step = per tile block the input transform of chunk k (patch image k & 1) and its MFMAs (weights from
-    // weight image k & 1), and, spread between them, the copies of chunk k+1 into both images (k+1) & 1.
-    // PAR = k & 1 (the chunk loop is unrolled by two so that the images are static).
+    // One step = the input transform of chunk k (patch image k & 1), then its 64 MFMAs (weights from weight image
+    // k & 1) with nothing but weight reads, waits and the copies of chunk k+1 (into both images (k+1) & 1) between
+    // them.  PAR = k & 1 (the chunk loop is unrolled by two so that the images are static).  The production step
+    // is ONE basic block: with the diagnostics' branches in it the scheduler spread the transform over the MFMA
+    // stream and let its temporaries reuse registers the MFMAs had just written (s_nop 2..6 in the stream).
     int k_stamp = 0;      // steps this wave has run (diagnostic stamps)
     auto step = [&](auto par, f32x4 (&acc)[TB][CB][16], int comp_ch) {
         constexpr int PAR = decltype(par)::value;
@@ -263,67 +274,97 @@ wino3x3_f32_kernel(const ConvArgs a) {
             const int t = q_first + atomicAdd(q_counter, 1);
             s_ctrl[0] = t < q_hi ? t : n_items;
         }
-        const float* sW = sWB + PAR * Cfg::kWFloats + w_lane;
-        f32x2_t d[4][4], v[16];     // the lane's input tile and its transform: they live inside a step
-        // (a.debug: diagnostic switches of tools/, 0 in production -- 2: no copies; 32:
-        //  s_memtime stamps of one wave's first 12 steps into counter_base[32..103])
-        const bool stamp = (a.debug & 32) && blockIdx.x == 1 && tid == 0 && k_stamp < 12;
-        int* stamps = a.counter_base + 32 + (k_stamp < 12 ? k_stamp : 0) * 6;
-        if (stamp) {
-            stamps[0] = (int)__builtin_amdgcn_s_memtime();
-            if (k_stamp == 0 || k_stamp == 11)    // 100 MHz reference beside it, to calibrate
-                a.counter_base[32 + 72 + (k_stamp != 0)] = (int)__builtin_amdgcn_s_memrealtime();
+        // (kDiag, a.debug: diagnostic switches of tools/ -- 2: no copies; 32: s_memtime stamps of one wave's
+        //  first 12 steps into counter_base[32..103])
+        bool stamp = false;
+        int* stamps = nullptr;
+        if constexpr (kDiag) {
+            stamp = (a.debug & 32) && blockIdx.x == 1 && tid == 0 && k_stamp < 12;
+            stamps = a.counter_base + 32 + (k_stamp < 12 ? k_stamp : 0) * 6;
+            if (stamp) {
+                stamps[0] = (int)__builtin_amdgcn_s_memtime();
+                if (k_stamp == 0 || k_stamp == 11)    // 100 MHz reference beside it, to calibrate
+                    a.counter_base[32 + 72 + (k_stamp != 0)] = (int)__builtin_amdgcn_s_memrealtime();
+                stamps[1] = (int)__builtin_amdgcn_s_memtime();
+            }
         }
         // The copies of chunk k+1 (both images PAR ^ 1: free since the barrier that ended the previous step)
         // go out one per point over the first points of the MFMA loop below (so that they have the rest of the
-        // step to land), with scalar operands only, in the matrix pipe's shadow -- issued as one burst at the top of the step (round 2) they held this wave's MFMAs back by
-        // their issue time, 400-790 cycles of a 4 800-cycle step.
-        if (stamp) stamps[1] = (int)__builtin_amdgcn_s_memtime();
+        // step to land), with scalar operands only, in the matrix pipe's shadow -- issued as one burst at the
+        // top of the step they held this wave's MFMAs back by their issue time.
 #pragma unroll
         for (int tb = 0; tb < TB; ++tb) {
+            typedef wino_f32x2 f32x2;
+            f32x2 d[4][4], v[16];       // the lane's input tile and its transform: they live inside a step
+            f32x4 wq[3];                // weight fragments, two points ahead of the MFMAs that use them
+            constexpr int kW = PAR * Cfg::kWFloats * 4;      // byte offset of the step's weight image
+            // The lgkmcnt counter holds 15: twelve patch reads go out, the last four and the first two weight
+            // fragments follow when column 0 is there.  A wait counts the reads issued BEHIND the ones it needs.
+            auto read_col = [&](int c) {
+                lds_read64(d[0][c], PAR * kImgBytes, tap[tb][0][c]);
+                lds_read64(d[1][c], PAR * kImgBytes + kRowBytes, tap[tb][0][c]);
+                lds_read64(d[2][c], PAR * kImgBytes, tap[tb][1][c]);
+                lds_read64(d[3][c], PAR * kImgBytes + kRowBytes, tap[tb][1][c]);
+            };
+            // B^T d: rows_d / cols_d are the same operations in the same order as ever (V is bit-identical)
+            auto rows_d = [&](int c) {
+                const f32x2 t0 = d[0][c] - d[2][c], t1 = d[1][c] + d[2][c];
+                const f32x2 t2 = d[2][c] - d[1][c], t3 = d[1][c] - d[3][c];
+                d[0][c] = t0; d[1][c] = t1; d[2][c] = t2; d[3][c] = t3;
+            };
+            auto cols_d = [&](int i) {
+                v[i * 4 + 0] = d[i][0] - d[i][2];
+                v[i * 4 + 1] = d[i][1] + d[i][2];
+                v[i * 4 + 2] = d[i][2] - d[i][1];
+                v[i * 4 + 3] = d[i][1] - d[i][3];
+            };
+            read_col(0);
+            read_col(1);
+            read_col(2);
+            wait_lgkm(8, d[0][0], d[1][0], d[2][0], d[3][0]);
+            rows_d(0);
+            read_col(3);
+            lds_read128(wq[0], kW, w_addr);
+            lds_read128(wq[1], kW + 1024, w_addr);
+            wait_lgkm(10, d[0][1], d[1][1], d[2][1], d[3][1]);
+            rows_d(1);
+            wait_lgkm(6, d[0][2], d[1][2], d[2][2], d[3][2]);
+            rows_d(2);
+            wait_lgkm(2, d[0][3], d[1][3], d[2][3], d[3][3]);
+            rows_d(3);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) load_d(d, tb, r, PAR);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) rows_d(d, c);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) cols_d(d, v, i);
-            if (stamp) {
+            for (int i = 0; i < 4; ++i) cols_d(i);
+            if constexpr (kDiag) {
                 // make the transform's end observable: the stamp depends on its result
-                stamps[2] = (int)__builtin_amdgcn_s_memtime() + (v[15][1] == 12345.f);
+                if (stamp) stamps[2] = (int)__builtin_amdgcn_s_memtime() + (v[15][1] == 12345.f);
             }
-            // weight fragments two points ahead of the MFMAs that use them (the scheduling barriers that
-            // pin the copies would otherwise leave each read's latency in front of its MFMAs)
-            constexpr int kWAhead = 2;
-            f32x4 wq[kWAhead + 1][CB / 2];
-#pragma unroll
-            for (int i = 0; i < kWAhead; ++i)
-#pragma unroll
-                for (int cp = 0; cp < CB / 2; ++cp)
-                    wq[i][cp] = *reinterpret_cast<const f32x4*>(sW + (i * 4 * (CB / 2) + cp) * 64);
 #pragma unroll
             for (int x = 0; x < 16; ++x) {
-                if (x + kWAhead < 16) {
-#pragma unroll
-                    for (int cp = 0; cp < CB / 2; ++cp)
-                        wq[(x + kWAhead) % (kWAhead + 1)][cp] =
-                            *reinterpret_cast<const f32x4*>(sW + ((x + kWAhead) * 4 * (CB / 2) + cp) * 64);
-                }
+                // fragment x + 2 overwrites the registers of point x - 1, whose MFMAs have issued (an MFMA
+                // reads SrcA/B as it issues; the LDS returns no sooner than 64 cycles later)
+                if (x + 2 < 16) lds_read128(wq[(x + 2) % 3], kW + (x + 2) * 1024, w_addr);
+                wait_lgkm(x < 14 ? 2 : 15 - x, wq[x % 3]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
+                for (int s2 = 0; s2 < 2; ++s2)      // s2 = 0 before s2 = 1 per accumulator
 #pragma unroll
                     for (int cb = 0; cb < CB; ++cb)
-                        acc[tb][cb][x] = mfma16(wq[x % (kWAhead + 1)][cb >> 1][(cb & 1) * 2 + s2], v[x][s2],
-                                                acc[tb][cb][x]);
-                if (tb == 0 && x < kCopies && !(a.debug & 2)) copy_s(x, PAR ^ 1);
+                        acc[tb][cb][x] = mfma16(wq[x % 3][(cb & 1) * 2 + s2], v[x][s2], acc[tb][cb][x]);
+                if (tb == 0 && x < kCopies) {
+                    if constexpr (kDiag) {
+                        if (!(a.debug & 2)) copy_s(x, PAR ^ 1);
+                    } else {
+                        copy_s(x, PAR ^ 1);
+                    }
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (stamp) stamps[3] = (int)__builtin_amdgcn_s_memtime();
+        if constexpr (kDiag) { if (stamp) stamps[3] = (int)__builtin_amdgcn_s_memtime(); }
         __builtin_amdgcn_s_waitcnt(0);
-        if (stamp) stamps[4] = (int)__builtin_amdgcn_s_memtime();
+        if constexpr (kDiag) { if (stamp) stamps[4] = (int)__builtin_amdgcn_s_memtime(); }
         __builtin_amdgcn_s_barrier();
-        if (stamp) stamps[5] = (int)__builtin_amdgcn_s_memtime();
+        if constexpr (kDiag) { if (stamp) stamps[5] = (int)__builtin_amdgcn_s_memtime(); }
         ++k_stamp;
         if (comp_ch == 0) q0 = s_ctrl[0];
         advance(pit, pch, true);
@@ -339,15 +380,19 @@ wino3x3_f32_kernel(const ConvArgs a) {
 #pragma unroll
                 for (int x = 0; x < 16; ++x) acc[tb][cb][x] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-        for (int comp_ch = 0; comp_ch < nchunks; comp_ch += 2) {     // Cin / 8 is even
+        // (the first two chunks stand outside the loop: the compiler then folds the zeros above into the first
+        //  chunk's MFMAs as the inline constant SrcC = 0, and no v_mov zeroes an accumulator)
+        step(std::integral_constant<int, 0>{}, acc, 0);
+        step(std::integral_constant<int, 1>{}, acc, 1);
+        for (int comp_ch = 2; comp_ch < nchunks; comp_ch += 2) {     // Cin / 8 is even
             step(std::integral_constant<int, 0>{}, acc, comp_ch);
             step(std::integral_constant<int, 1>{}, acc, comp_ch + 1);
         }
 
         // ---- epilogue: Y = A^T M A, batch-norm + ReLU, stores (they drain under the next
         //      item's first chunk) ----------------------------------------------------------------
-        // (a.debug & 1, tools/: the kernel without its epilogues -- what they cost)
-        if (!(a.debug & 1)) {
+        // (kDiag, a.debug & 1, tools/: the kernel without its epilogues -- what they cost)
+        if (!kDiag || !(a.debug & 1)) {
             // The epilogue's arguments come from the kernarg segment again (scalar loads, through a pointer the
             // compiler cannot see through): kept in SGPRs across the K loop they are spilled to vector lanes and
             // every item pays ~100 v_readlane for them on the vector pipe the MFMAs of the other workgroup need.
