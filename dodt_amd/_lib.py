@@ -81,6 +81,14 @@ class NmsPlan(C.Structure):
                 ('scratch_bytes', C.c_int64)]
 
 
+class FcPlan(C.Structure):
+    _fields_ = [('form', C.c_int32), ('name', C.c_char * 24), ('xvec', C.c_int32), ('fuse', C.c_int32),
+                ('vec_store', C.c_int32), ('y_bf16', C.c_int32), ('grid', C.c_int32 * 2),
+                ('Kp', C.c_int32), ('BN', C.c_int32), ('Npad', C.c_int32), ('Kd', C.c_int32), ('dma_bk', C.c_int32),
+                ('skinny', C.c_int32), ('dma', C.c_int32), ('smallk', C.c_int32), ('plain', C.c_int32),
+                ('bf16_rows', C.c_int32)]
+
+
 _vp = C.c_void_p
 _i = C.c_int
 _f = C.c_float
@@ -174,6 +182,8 @@ SIGNATURES = {
     'dodt_fc_forward': (_i, [_vp, _vp, _pf, _pf, _i, _i, _pi32, _pf, _i]),
     'dodt_fc_forward_split': (_i, [_vp, _vp, _pf, _i, _i, _pi32, _i, C.POINTER(_i), C.POINTER(_vp)]),
     'dodt_fc_flops': (_d, [_vp, _i]),
+    'dodt_fc_plan_host': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(FcPlan)]),
+    'dodt_fc_form': (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, C.POINTER(FcPlan)]),
     'dodt_fc_bf16_row_elems': (_i, [_vp]),
     'dodt_fc_forward_bf16': (_i, [_vp, _vp, _vp, _i, _i, _pi32, _vp, _i, _i]),
     'dodt_fc_forward_split_bf16': (_i, [_vp, _vp, _vp, _i, _i, _pi32, _i, C.POINTER(_i), C.POINTER(_vp)]),

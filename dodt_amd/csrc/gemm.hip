@@ -20,6 +20,7 @@
 //   * optional second input: x = (x1 + x2) / 2, the heads' "mean" fusion, folded into the
 //     load of the first layer (tf.reduce_sum over the two crops / 2.0).
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <mutex>
 #include <set>
@@ -312,12 +313,16 @@ hipError_t launch_with_lds(void (*kernel)(Params...), dim3 grid, size_t lds, hip
     return hipSuccess;
 }
 
+// whether fc_mfma_kernel loads x as float4 (XVEC): whole fragments of a row, rows a multiple of 16 bytes apart
+bool fc_tiled_vec(const GemmArgs& a, bool bf16) { return (a.ldx % 4 == 0) && (a.K % (bf16 ? 8 : 4) == 0); }
+
+// grid: fc_grid's (launch_fc_form)
 template <int BM, int BN, int WM, int WN, int kBK, bool BF16>
-int launch_fc(hipStream_t s, const GemmArgs& a, int Npad) {
+int launch_fc(hipStream_t s, const GemmArgs& a, int Npad, const dim3& grid) {
     constexpr int G = BF16 ? kBK / 2 : kBK;
     constexpr size_t lds = 2 * (size_t)(BM * (G + 4) + G * BN) * sizeof(float);
-    const bool vec = (a.ldx % 4 == 0) && (a.K % (BF16 ? 8 : 4) == 0);
-    const dim3 grid(dodt::ceil_div(a.M, BM), Npad / BN);
+    const bool vec = fc_tiled_vec(a, BF16);
+    DODT_REQUIRE((int)grid.x == dodt::ceil_div(a.M, BM) && (int)grid.y == Npad / BN, "dodt_fc: grid of another tile shape");
     hipError_t e;
     if (vec && a.x2) e = launch_with_lds(&fc_mfma_kernel<BM, BN, WM, WN, true, kBK, true, BF16>, grid, lds, s, a);
     else if (vec) e = launch_with_lds(&fc_mfma_kernel<BM, BN, WM, WN, true, kBK, false, BF16>, grid, lds, s, a);
@@ -498,9 +503,9 @@ fc_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
 // nt: 1 or 2 MFMA tiles per wave (select_fc_form); a second input selects the fused-mean instance, which has nt = 1 only.
 // (Round 4 read the shader clock inside the K loop with a probe compiled into this kernel, s_memtime against the 100 MHz
 //  s_memrealtime: 1.91-1.94 GHz, DESIGN.md 5b and profiles/r4_experiments.md; the probe is removed again.)
-int launch_fc_dma(hipStream_t s, const GemmArgs& a, int Npad, int nt) {
-    const int tiles_m = dodt::ceil_div(a.M, kDmaBM), tiles_n = Npad / (64 * nt);
-    const dim3 grid(tiles_m * tiles_n);
+int launch_fc_dma(hipStream_t s, const GemmArgs& a, int Npad, int nt, const dim3& grid) {
+    const int tiles_n = Npad / (64 * nt), tiles_m = (int)grid.x / tiles_n;
+    DODT_REQUIRE(tiles_m == dodt::ceil_div(a.M, kDmaBM) && tiles_m * tiles_n == (int)grid.x, "dodt_fc: grid of another tile shape");
     const size_t x_floats = (size_t)kDmaXFloats * (a.x2 ? 2 : 1);
     const size_t lds = kDmaStages * (x_floats + (size_t)kDmaBK * 64 * nt) * sizeof(float);
     hipError_t e;
@@ -651,9 +656,9 @@ fc_bf16_dma_kernel(const GemmArgs a, int tiles_m, int tiles_n) {
     }
 }
 
-int launch_fc_bf16_dma(hipStream_t s, const GemmArgs& a, int Npad, bool y_bf16, int bk) {
-    const int tiles_m = dodt::ceil_div(a.M, kBfBM), tiles_n = Npad / kBfBN;
-    const dim3 grid(tiles_m * tiles_n);
+int launch_fc_bf16_dma(hipStream_t s, const GemmArgs& a, int Npad, bool y_bf16, int bk, const dim3& grid) {
+    const int tiles_n = Npad / kBfBN, tiles_m = (int)grid.x / tiles_n;
+    DODT_REQUIRE(tiles_m == dodt::ceil_div(a.M, kBfBM) && tiles_m * tiles_n == (int)grid.x, "dodt_fc: grid of another tile shape");
     const size_t lds = (size_t)kBfStages * (kBfBM + kBfBN) * bk * 2;
     hipError_t e;
     if (bk == 64 && y_bf16) e = launch_with_lds(&fc_bf16_dma_kernel<true, 64>, grid, lds, s, a, tiles_m, tiles_n);
@@ -831,17 +836,15 @@ fc_smallk_kernel(const GemmArgs a, const float* __restrict__ w_plain) {
     }
 }
 
-int launch_fc_skinny(hipStream_t s, const GemmArgs& a, const SplitOut& so, bool bf16, bool x_bf16) {
-    if (x_bf16) hipLaunchKernelGGL((fc_skinny_kernel<true, true>), dim3(dodt::ceil_div(a.M, 16)), dim3(512), 0, s, a, so);
-    else if (bf16) hipLaunchKernelGGL(fc_skinny_kernel<true>, dim3(dodt::ceil_div(a.M, 16)), dim3(512), 0, s, a, so);
-    else hipLaunchKernelGGL(fc_skinny_kernel<false>, dim3(dodt::ceil_div(a.M, 16)), dim3(512), 0, s, a, so);
+int launch_fc_skinny(hipStream_t s, const GemmArgs& a, const SplitOut& so, bool bf16, bool x_bf16, const dim3& grid) {
+    if (x_bf16) hipLaunchKernelGGL((fc_skinny_kernel<true, true>), grid, dim3(512), 0, s, a, so);
+    else if (bf16) hipLaunchKernelGGL(fc_skinny_kernel<true>, grid, dim3(512), 0, s, a, so);
+    else hipLaunchKernelGGL(fc_skinny_kernel<false>, grid, dim3(512), 0, s, a, so);
     DODT_LAUNCH_CHECK();
     return DODT_OK;
 }
 
-int launch_fc_smallk(hipStream_t s, const GemmArgs& a, const float* w_plain, bool bf16) {
-    const long long threads = (long long)a.M * (a.N / 4);
-    const dim3 grid((unsigned)((threads + 255) / 256));
+int launch_fc_smallk(hipStream_t s, const GemmArgs& a, const float* w_plain, bool bf16, const dim3& grid) {
     if (bf16) hipLaunchKernelGGL(fc_smallk_kernel<true>, grid, dim3(256), 0, s, a, w_plain);
     else hipLaunchKernelGGL(fc_smallk_kernel<false>, grid, dim3(256), 0, s, a, w_plain);
     DODT_LAUNCH_CHECK();
@@ -926,47 +929,97 @@ extern "C" int dodt_rows_to_bf16(dodt_ctx* ctx, const float* d_a, const float* d
     return DODT_OK;
 }
 
-struct dodt_fc {
-    dodt_ctx* ctx = nullptr;
-    int K = 0, Kp = 0, N = 0, Npad = 0, BN = 0, relu = 0;
+// What (K, N, flags) alone decide about a layer: its weight images and the kernels they allow.  fc_traits is the only
+// place that derives them; it touches no device (dodt_fc_create_ex builds the layer from it, dodt_fc_plan_host plans
+// from it).  The call decides the rest (select_fc_form).
+struct dodt_fc_traits {
+    int K = 0, Kp = 0, N = 0, Npad = 0, BN = 0;
     bool bf16 = false;
-    float* d_w = nullptr;
-    float* d_b = nullptr;
-    float* d_w_plain = nullptr;   // [K][N] as given (bf16 layers: rounded), for K <= kSmallK
-    void* d_w_dma = nullptr;      // bf16 layers with N % 128 == 0: stage images for fc_bf16_dma_kernel
+    bool plain = false;           // the [K][N] weights as given (bf16 layers: rounded) exist: K <= kSmallK, N % 4 == 0
+    bool bf16_rows = false;       // bf16 layers with N % 128 == 0, K >= 128: stage images for fc_bf16_dma_kernel
     int Kd = 0;                   //   ... of K rounded up to 64
     int dma_bk = 0;               //   ... blocked for stages of this many k
-    // what the layer alone allows (dodt_fc_create_ex); the call decides the rest (select_fc_form)
     bool smallk = false;          // fc_smallk_kernel: the plain weights exist and N >= 64
     bool skinny = false;          // fc_skinny_kernel: N <= 32 and K % 16 == 0
     bool dma = false;             // fc_dma_kernel: fp32, 128-wide blocking, K a multiple of a stage and at least two
 };
 
+struct dodt_fc : dodt_fc_traits {
+    dodt_ctx* ctx = nullptr;
+    int relu = 0;
+    float* d_w = nullptr;
+    float* d_b = nullptr;
+    float* d_w_plain = nullptr;   // traits.plain: for K <= kSmallK
+    void* d_w_dma = nullptr;      // traits.bf16_rows: stage images for fc_bf16_dma_kernel
+};
+
 namespace {
 
+// bf16_bk: the stage depth the bf16-row images are blocked for (bf16_dma_bk() in this process)
+dodt_fc_traits fc_traits(int K, int N, int flags, int bf16_bk) {
+    dodt_fc_traits t;
+    t.K = K;
+    t.N = N;
+    t.bf16 = (flags & DODT_FC_BF16) != 0;
+    t.Kp = (int)dodt::align_up((size_t)K, t.bf16 ? 2 * kKAlign : kKAlign);
+    t.BN = (N >= 128) ? 128 : 32;
+    t.Npad = (int)dodt::align_up((size_t)N, (size_t)t.BN);
+    t.skinny = t.Npad == 32 && K % 16 == 0;
+    t.dma = !t.bf16 && t.BN == 128 && K % kDmaBK == 0 && K >= 2 * kDmaBK;
+    if (t.bf16 && N % kBfBN == 0 && K >= 128) {
+        t.bf16_rows = true;
+        t.Kd = (int)dodt::align_up((size_t)K, (size_t)64);
+        t.dma_bk = bf16_bk == 64 ? 64 : 32;
+    }
+    t.plain = K <= kSmallK && N % 4 == 0;
+    t.smallk = t.plain && N >= 64;
+    return t;
+}
+
 // The kernel forms a layer can run on.  select_fc_form is the only place that picks one.
+// (the values are the header's DODT_FC_FORM_*, which dodt_fc_plan reports)
 enum class FcForm {
-    kNone,             // bf16 rows only: the layer or the call has no kernel that reads them
-    kSmallK,           // fc_smallk_kernel, float32 or bf16 arithmetic as the layer says
-    kSkinny,           // fc_skinny_kernel<false>
-    kSkinnyBf16,       // fc_skinny_kernel<true>: float32 rows rounded on load
-    kSkinnyBf16Rows,   // fc_skinny_kernel<true, true>
-    kDmaNt1,           // fc_dma_kernel<false, 1>: 64 x 64 tiles
-    kDmaNt2,           // fc_dma_kernel<false, 2>: 64 x 128 tiles
-    kDmaFused,         // fc_dma_kernel<true, 1>: the mean of two inputs taken on the fragment
-    kBf16RowsDma32,    // fc_bf16_dma_kernel<., 32>, float32 or bf16 output as the call says
-    kBf16RowsDma64,    // fc_bf16_dma_kernel<., 64>
-    kTiled64x128,      // fc_mfma_kernel, register-staged, 64-k stages
-    kTiled128x32,      //   ... 32-k stages
-    kTiled64x128Bf16,  //   ... bf16 arithmetic on float32 rows, 32-k stages
-    kTiled128x32Bf16,  //   ... 64-k stages
+    kNone = DODT_FC_FORM_NONE,                        // bf16 rows only: the layer or the call has no kernel that reads them
+    kSmallK = DODT_FC_FORM_SMALLK,                    // fc_smallk_kernel, float32 or bf16 arithmetic as the layer says
+    kSkinny = DODT_FC_FORM_SKINNY,                    // fc_skinny_kernel<false>
+    kSkinnyBf16 = DODT_FC_FORM_SKINNY_BF16,           // fc_skinny_kernel<true>: float32 rows rounded on load
+    kSkinnyBf16Rows = DODT_FC_FORM_SKINNY_BF16_ROWS,  // fc_skinny_kernel<true, true>
+    kDmaNt1 = DODT_FC_FORM_DMA_NT1,                   // fc_dma_kernel<false, 1>: 64 x 64 tiles
+    kDmaNt2 = DODT_FC_FORM_DMA_NT2,                   // fc_dma_kernel<false, 2>: 64 x 128 tiles
+    kDmaFused = DODT_FC_FORM_DMA_FUSED,               // fc_dma_kernel<true, 1>: the mean of two inputs taken on the fragment
+    kBf16RowsDma32 = DODT_FC_FORM_BF16_ROWS_DMA32,    // fc_bf16_dma_kernel<., 32>, float32 or bf16 output as the call says
+    kBf16RowsDma64 = DODT_FC_FORM_BF16_ROWS_DMA64,    // fc_bf16_dma_kernel<., 64>
+    kTiled64x128 = DODT_FC_FORM_TILED_64X128,         // fc_mfma_kernel, register-staged, 64-k stages
+    kTiled128x32 = DODT_FC_FORM_TILED_128X32,         //   ... 32-k stages
+    kTiled64x128Bf16 = DODT_FC_FORM_TILED_64X128_BF16,  //   ... bf16 arithmetic on float32 rows, 32-k stages
+    kTiled128x32Bf16 = DODT_FC_FORM_TILED_128X32_BF16,  //   ... 64-k stages
 };
+
+const char* fc_form_name(FcForm form) {
+    switch (form) {
+    case FcForm::kNone: return "kNone";
+    case FcForm::kSmallK: return "kSmallK";
+    case FcForm::kSkinny: return "kSkinny";
+    case FcForm::kSkinnyBf16: return "kSkinnyBf16";
+    case FcForm::kSkinnyBf16Rows: return "kSkinnyBf16Rows";
+    case FcForm::kDmaNt1: return "kDmaNt1";
+    case FcForm::kDmaNt2: return "kDmaNt2";
+    case FcForm::kDmaFused: return "kDmaFused";
+    case FcForm::kBf16RowsDma32: return "kBf16RowsDma32";
+    case FcForm::kBf16RowsDma64: return "kBf16RowsDma64";
+    case FcForm::kTiled64x128: return "kTiled64x128";
+    case FcForm::kTiled128x32: return "kTiled128x32";
+    case FcForm::kTiled64x128Bf16: return "kTiled64x128Bf16";
+    case FcForm::kTiled128x32Bf16: return "kTiled128x32Bf16";
+    }
+    return "?";
+}
 
 // The kernel form of one call of a layer.  The call: a (x, x2, y, M, ldx, ldy), whether x holds bf16 rows, whether y
 // takes bf16.  The split entries pass a.y = NULL; they accept the skinny forms only.
-FcForm select_fc_form(const dodt_fc& f, const GemmArgs& a, bool x_bf16, bool y_bf16) {
+FcForm select_fc_form(const dodt_fc_traits& f, const GemmArgs& a, bool x_bf16, bool y_bf16) {
     if (x_bf16) {
-        if (f.d_w_dma) return f.dma_bk == 64 ? FcForm::kBf16RowsDma64 : FcForm::kBf16RowsDma32;
+        if (f.bf16_rows) return f.dma_bk == 64 ? FcForm::kBf16RowsDma64 : FcForm::kBf16RowsDma32;
         if (f.skinny && a.ldx % 4 == 0 && (size_t)a.x % 8 == 0 && !y_bf16) return FcForm::kSkinnyBf16Rows;
         return FcForm::kNone;
     }
@@ -996,24 +1049,51 @@ FcForm select_fc_form(const dodt_fc& f, const GemmArgs& a, bool x_bf16, bool y_b
     return FcForm::kTiled64x128;
 }
 
-int launch_fc_form(FcForm form, const dodt_fc& f, hipStream_t s, GemmArgs a, const SplitOut& so, bool y_bf16) {
+// The grid of a form's launch for M rows (before *d_m): what the launchers are given and what dodt_fc_plan reports.
+dim3 fc_grid(FcForm form, const dodt_fc_traits& f, int M) {
     switch (form) {
-    case FcForm::kSmallK: return launch_fc_smallk(s, a, f.d_w_plain, f.bf16);
-    case FcForm::kSkinny: return launch_fc_skinny(s, a, so, false, false);
-    case FcForm::kSkinnyBf16: return launch_fc_skinny(s, a, so, true, false);
-    case FcForm::kSkinnyBf16Rows: return launch_fc_skinny(s, a, so, true, true);
+    case FcForm::kSmallK: return dim3((unsigned)(((long long)M * (f.N / 4) + 255) / 256));
+    case FcForm::kSkinny:
+    case FcForm::kSkinnyBf16:
+    case FcForm::kSkinnyBf16Rows: return dim3(dodt::ceil_div(M, 16));
     case FcForm::kDmaNt1:
-    case FcForm::kDmaFused: return launch_fc_dma(s, a, f.Npad, 1);
-    case FcForm::kDmaNt2: return launch_fc_dma(s, a, f.Npad, 2);
+    case FcForm::kDmaFused: return dim3(dodt::ceil_div(M, kDmaBM) * (f.Npad / 64));
+    case FcForm::kDmaNt2: return dim3(dodt::ceil_div(M, kDmaBM) * (f.Npad / 128));
+    case FcForm::kBf16RowsDma32:
+    case FcForm::kBf16RowsDma64: return dim3(dodt::ceil_div(M, kBfBM) * (f.Npad / kBfBN));
+    case FcForm::kTiled64x128:
+    case FcForm::kTiled64x128Bf16: return dim3(dodt::ceil_div(M, 64), f.Npad / 128);
+    case FcForm::kTiled128x32:
+    case FcForm::kTiled128x32Bf16: return dim3(dodt::ceil_div(M, 128), f.Npad / 32);
+    case FcForm::kNone: break;
+    }
+    return dim3(0, 0);
+}
+
+bool fc_form_is_tiled(FcForm form) {
+    return form == FcForm::kTiled64x128 || form == FcForm::kTiled128x32 || form == FcForm::kTiled64x128Bf16 ||
+           form == FcForm::kTiled128x32Bf16;
+}
+
+int launch_fc_form(FcForm form, const dodt_fc& f, hipStream_t s, GemmArgs a, const SplitOut& so, bool y_bf16) {
+    const dim3 grid = fc_grid(form, f, a.M);
+    switch (form) {
+    case FcForm::kSmallK: return launch_fc_smallk(s, a, f.d_w_plain, f.bf16, grid);
+    case FcForm::kSkinny: return launch_fc_skinny(s, a, so, false, false, grid);
+    case FcForm::kSkinnyBf16: return launch_fc_skinny(s, a, so, true, false, grid);
+    case FcForm::kSkinnyBf16Rows: return launch_fc_skinny(s, a, so, true, true, grid);
+    case FcForm::kDmaNt1:
+    case FcForm::kDmaFused: return launch_fc_dma(s, a, f.Npad, 1, grid);
+    case FcForm::kDmaNt2: return launch_fc_dma(s, a, f.Npad, 2, grid);
     case FcForm::kBf16RowsDma32:
     case FcForm::kBf16RowsDma64:
         a.w = reinterpret_cast<const float*>(f.d_w_dma);
         a.Kp = f.Kd;
-        return launch_fc_bf16_dma(s, a, f.Npad, y_bf16, f.dma_bk);
-    case FcForm::kTiled64x128: return launch_fc<64, 128, 2, 2, 64, false>(s, a, f.Npad);
-    case FcForm::kTiled128x32: return launch_fc<128, 32, 4, 1, 32, false>(s, a, f.Npad);
-    case FcForm::kTiled64x128Bf16: return launch_fc<64, 128, 2, 2, 32, true>(s, a, f.Npad);
-    case FcForm::kTiled128x32Bf16: return launch_fc<128, 32, 4, 1, 64, true>(s, a, f.Npad);
+        return launch_fc_bf16_dma(s, a, f.Npad, y_bf16, f.dma_bk, grid);
+    case FcForm::kTiled64x128: return launch_fc<64, 128, 2, 2, 64, false>(s, a, f.Npad, grid);
+    case FcForm::kTiled128x32: return launch_fc<128, 32, 4, 1, 32, false>(s, a, f.Npad, grid);
+    case FcForm::kTiled64x128Bf16: return launch_fc<64, 128, 2, 2, 32, true>(s, a, f.Npad, grid);
+    case FcForm::kTiled128x32Bf16: return launch_fc<128, 32, 4, 1, 64, true>(s, a, f.Npad, grid);
     case FcForm::kNone: break;
     }
     dodt::set_error("dodt_fc: no kernel form selected");
@@ -1066,16 +1146,9 @@ int dodt_fc_create_ex(dodt_ctx* ctx, int K, int N, const float* w, const float* 
     DODT_REQUIRE(ctx && w && bias && out, "dodt_fc_create: NULL argument");
     DODT_REQUIRE(K >= 1 && N >= 1, "dodt_fc_create: bad sizes");
     dodt_fc* f = new dodt_fc();
+    static_cast<dodt_fc_traits&>(*f) = fc_traits(K, N, flags, bf16_dma_bk());
     f->ctx = ctx;
-    f->K = K;
-    f->N = N;
     f->relu = relu;
-    f->bf16 = bf16;
-    f->Kp = (int)dodt::align_up((size_t)K, bf16 ? 2 * kKAlign : kKAlign);
-    f->BN = (N >= 128) ? 128 : 32;
-    f->Npad = (int)dodt::align_up((size_t)N, (size_t)f->BN);
-    f->skinny = f->Npad == 32 && K % 16 == 0;
-    f->dma = !bf16 && f->BN == 128 && K % kDmaBK == 0 && K >= 2 * kDmaBK;
     // blocked weights [n-tile][Kp/8][h][BN][4]; k = 8q + 4h + s
     std::vector<float> blk((size_t)f->Kp * f->Npad, 0.0f), b(f->Npad, 0.0f);
     //   bf16: [n-tile][Kp/16][h][BN][8] bf16 (k = 16q + 8h + s), in the first half of blk
@@ -1101,12 +1174,10 @@ int dodt_fc_create_ex(dodt_ctx* ctx, int K, int N, const float* w, const float* 
                                   hipMemcpyHostToDevice, ctx->stream));
     DODT_HIP_CHECK(hipMemcpyAsync(f->d_b, b.data(), b.size() * sizeof(float),
                                   hipMemcpyHostToDevice, ctx->stream));
-    if (bf16 && N % kBfBN == 0 && K >= 128) {
+    if (f->bf16_rows) {
         // fc_bf16_dma_kernel's weights: [n-tile of 128][stage of BK k][column c][slot p] 16 bytes = 8 bf16, slot p
         // holding k = BK stage + 8 (p ^ swz(c)) .. + 7 (the conflict-free LDS image of a stage, contiguous)
-        const int BK = bf16_dma_bk(), S = BK / 8;
-        f->Kd = (int)dodt::align_up((size_t)K, (size_t)64);
-        f->dma_bk = BK;
+        const int BK = f->dma_bk, S = BK / 8;
         const int ns = f->Kd / BK;
         std::vector<uint16_t> img((size_t)(N / kBfBN) * ns * kBfBN * BK, 0);
         for (int k = 0; k < K; ++k)
@@ -1123,7 +1194,7 @@ int dodt_fc_create_ex(dodt_ctx* ctx, int K, int N, const float* w, const float* 
         DODT_HIP_CHECK(hipMemcpy(f->d_w_dma, img.data(), img.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
     std::vector<float> plain;
-    if (K <= kSmallK && N % 4 == 0) {
+    if (f->plain) {
         plain.assign(w, w + (size_t)K * N);
         if (bf16)
             for (float& v : plain) v = dodt::bf16_to_float(dodt::float_to_bf16(v));
@@ -1134,7 +1205,6 @@ int dodt_fc_create_ex(dodt_ctx* ctx, int K, int N, const float* w, const float* 
         }
         DODT_HIP_CHECK(hipMemcpyAsync(f->d_w_plain, plain.data(), plain.size() * sizeof(float),
                                       hipMemcpyHostToDevice, ctx->stream));
-        f->smallk = N >= 64;
     }
     DODT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     *out = f;
@@ -1223,6 +1293,60 @@ int dodt_fc_forward_split_bf16(dodt_fc* f, dodt_ctx* ctx, const void* d_x_bf16, 
     }
     if (M == 0) return DODT_OK;
     return launch_fc_form(form, *f, (ctx ? ctx : f->ctx)->stream, a, so, false);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the record of one call: select_fc_form's answer and what the form's launcher derives from the call
+void fill_fc_plan(const dodt_fc_traits& t, const GemmArgs& a, bool x_bf16, bool y_bf16, dodt_fc_plan* p) {
+    const FcForm form = select_fc_form(t, a, x_bf16, y_bf16);
+    *p = dodt_fc_plan();
+    p->form = (int32_t)form;
+    snprintf(p->name, sizeof(p->name), "%s", fc_form_name(form));
+    const dim3 grid = fc_grid(form, t, a.M);
+    p->grid[0] = (int32_t)grid.x;
+    p->grid[1] = form == FcForm::kNone ? 0 : (int32_t)grid.y;
+    if (fc_form_is_tiled(form)) {
+        p->xvec = fc_tiled_vec(a, t.bf16);
+        p->fuse = a.x2 != nullptr;
+    }
+    if (form == FcForm::kSmallK) p->vec_store = a.ldy % 4 == 0;
+    if (form == FcForm::kBf16RowsDma32 || form == FcForm::kBf16RowsDma64) p->y_bf16 = y_bf16;
+    p->Kp = t.Kp; p->BN = t.BN; p->Npad = t.Npad; p->Kd = t.Kd; p->dma_bk = t.dma_bk;
+    p->skinny = t.skinny; p->dma = t.dma; p->smallk = t.smallk; p->plain = t.plain; p->bf16_rows = t.bf16_rows;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dodt_fc_plan_host(int K, int N, int flags, int M, int ldx, int ldy, int x_off, int x2_off, int y_off, int x_bf16,
+                      int y_bf16, int bf16_bk, dodt_fc_plan* out) {
+    DODT_REQUIRE(out, "dodt_fc_plan_host: NULL argument");
+    DODT_REQUIRE(K >= 1 && N >= 1 && M >= 0, "dodt_fc_plan_host: bad sizes");
+    DODT_REQUIRE(x_off >= 0 && x_off < 16 && x2_off < 16 && y_off >= 0 && y_off < 16,
+                 "dodt_fc_plan_host: offsets are addresses modulo 16 (x2_off < 0: no second input)");
+    DODT_REQUIRE(bf16_bk == 32 || bf16_bk == 64, "dodt_fc_plan_host: stage depth 32 or 64, got %d", bf16_bk);
+    dodt_fc f;      // no device memory: only the traits are read
+    static_cast<dodt_fc_traits&>(f) = fc_traits(K, N, flags, bf16_bk);
+    // stand-ins for the call's pointers: only their low four bits are looked at
+    const size_t base = 0x10000;
+    const GemmArgs a = fc_args(f, reinterpret_cast<const void*>(base + x_off),
+                               x2_off < 0 ? nullptr : reinterpret_cast<const float*>(base + x2_off), ldx, M, nullptr,
+                               reinterpret_cast<void*>(base + y_off), ldy);
+    fill_fc_plan(f, a, x_bf16 != 0, y_bf16 != 0, out);
+    return DODT_OK;
+}
+
+int dodt_fc_form(const dodt_fc* f, const void* d_x, const void* d_x2, int ldx, int M, const void* d_y, int ldy,
+                 int x_bf16, int y_bf16, dodt_fc_plan* out) {
+    DODT_REQUIRE(f && d_x && out, "dodt_fc_form: NULL argument");
+    DODT_REQUIRE(M >= 0, "dodt_fc_form: bad sizes");
+    const GemmArgs a = fc_args(*f, d_x, reinterpret_cast<const float*>(d_x2), ldx, M, nullptr, const_cast<void*>(d_y), ldy);
+    fill_fc_plan(*f, a, x_bf16 != 0, y_bf16 != 0, out);
+    return DODT_OK;
 }
 
 double dodt_fc_flops(const dodt_fc* f, int M) {

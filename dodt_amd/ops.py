@@ -392,6 +392,29 @@ def bf16_to_float(a):
     return (np.asarray(a, np.uint16).astype(np.uint32) << 16).view(np.float32)
 
 
+def _fc_plan_record(p):
+    rec = dict((name, int(getattr(p, name))) for name, _ in p._fields_ if name not in ('name', 'grid'))
+    rec['name'] = p.name.decode('ascii')
+    rec['grid'] = (int(p.grid[0]), int(p.grid[1]))
+    return rec
+
+
+def fc_plan_host(K, N, M, dtype='f32', ldx=None, ldy=None, x_off=0, x2_off=None, y_off=0, x_bf16=False, y_bf16=False,
+                 bf16_bk=32, lib=None):
+    """Which kernel a call of a (K, N) layer would run, the fields of dodt_fc_plan as a dict: 'name' / 'form' the
+    selector's form ('kNone': the call is refused), 'xvec' / 'fuse' the register-staged kernel's instantiation,
+    'vec_store' the small-K kernel's row store, 'grid', and the layer's traits.  x_off, x2_off, y_off: the addresses
+    modulo 16 (x2_off None: no second input); bf16_bk: DODT_FC_BF16_DMA_BK of the creating process.  Host only:
+    needs no GPU (dodt_fc_plan_host)."""
+    lib = lib or _lib.load()
+    p = _lib.FcPlan()
+    _lib.check(lib.dodt_fc_plan_host(
+        int(K), int(N), _lib.FC_BF16 if dtype == 'bf16' else 0, int(M), int(K if ldx is None else ldx),
+        int(N if ldy is None else ldy), int(x_off), -1 if x2_off is None else int(x2_off), int(y_off),
+        1 if x_bf16 else 0, 1 if y_bf16 else 0, int(bf16_bk), C.byref(p)), 'dodt_fc_plan_host')
+    return _fc_plan_record(p)
+
+
 class FullyConnected(object):
     """y = act(x w + b) on the device (dodt_fc_*).  w (K,N) row-major, the layout of the
     TF variable (conv kernels reshaped (kh*kw*cin, cout))."""
@@ -450,6 +473,15 @@ class FullyConnected(object):
         ys = (C.c_void_p * len(d_ys))(*[_p(y) for y in d_ys])
         _lib.check(c.lib.dodt_fc_forward_split_bf16(
             self.handle, c.handle, _p(d_x), int(ldx), int(M), _p(d_m), len(widths), w, ys), 'dodt_fc_forward_split_bf16')
+
+    def form(self, d_x, M, d_y=None, ldx=None, ldy=None, d_x2=None, x_bf16=False, y_bf16=False):
+        """The record of fc_plan_host for this layer and a call's real device pointers (d_y None: the split entries);
+        launches nothing (dodt_fc_form)."""
+        p = _lib.FcPlan()
+        _lib.check(self.ctx.lib.dodt_fc_form(
+            self.handle, _p(d_x), _p(d_x2), int(self.K if ldx is None else ldx), int(M), _p(d_y),
+            int(self.N if ldy is None else ldy), 1 if x_bf16 else 0, 1 if y_bf16 else 0, C.byref(p)), 'dodt_fc_form')
+        return _fc_plan_record(p)
 
     def flops(self, M):
         return 2.0 * M * self.K * self.N

@@ -526,6 +526,42 @@ int dodt_fc_forward_split_bf16(dodt_fc* fc, dodt_ctx* ctx, const void* d_x_bf16,
 int dodt_rows_to_bf16(dodt_ctx* ctx, const float* d_a, const float* d_b, int rows, const int32_t* d_n,
                       int row_floats, int in_ld, void* d_out_bf16, int out_ld);
 double dodt_fc_flops(const dodt_fc* fc, int M);
+/* Which kernel a call of a layer runs.  One selector decides it from the layer's (K, N, flags) and the call's strides,
+ * pointer alignments and row types; these two entries report its answer and launch nothing. */
+#define DODT_FC_FORM_NONE 0              /* bf16 rows that no kernel of the layer reads: the call is refused */
+#define DODT_FC_FORM_SMALLK 1            /* K <= 16, N >= 64, N % 4 == 0: vector ALU */
+#define DODT_FC_FORM_SKINNY 2            /* N <= 32, K % 16 == 0: K split over the waves */
+#define DODT_FC_FORM_SKINNY_BF16 3
+#define DODT_FC_FORM_SKINNY_BF16_ROWS 4
+#define DODT_FC_FORM_DMA_NT1 5           /* fp32, LDS-DMA staged, 64 x 64 tiles */
+#define DODT_FC_FORM_DMA_NT2 6           /* ... 64 x 128 tiles */
+#define DODT_FC_FORM_DMA_FUSED 7         /* ... the mean of two inputs inside */
+#define DODT_FC_FORM_BF16_ROWS_DMA32 8   /* bf16 rows, LDS-DMA staged, 32-k stages */
+#define DODT_FC_FORM_BF16_ROWS_DMA64 9   /* ... 64-k stages */
+#define DODT_FC_FORM_TILED_64X128 10     /* register-staged */
+#define DODT_FC_FORM_TILED_128X32 11
+#define DODT_FC_FORM_TILED_64X128_BF16 12
+#define DODT_FC_FORM_TILED_128X32_BF16 13
+typedef struct dodt_fc_plan {
+    int32_t form;           /* DODT_FC_FORM_* */
+    char name[24];          /* the form's name in the selector, "kDmaNt1" */
+    int32_t xvec, fuse;     /* register-staged forms: x loaded as float4 (else by element); the mean of x and x2 inside */
+    int32_t vec_store;      /* DODT_FC_FORM_SMALLK: rows stored 16 bytes at a time (ldy % 4 == 0), else by element */
+    int32_t y_bf16;         /* DODT_FC_FORM_BF16_ROWS_DMA*: the output rows are bf16 */
+    int32_t grid[2];        /* workgroups of the launch, before *d_m cuts rows; 0, 0 for DODT_FC_FORM_NONE */
+    /* what (K, N, flags) alone decide: padded sizes, the width the weights are blocked for, the bf16-row image */
+    int32_t Kp, BN, Npad, Kd, dma_bk;
+    int32_t skinny, dma, smallk, plain, bf16_rows;
+} dodt_fc_plan;
+/* Host only, touches no device.  x_off, x2_off, y_off: the addresses of x, x2 and y modulo 16 (x2_off < 0: no second
+ * input; the split entries have no y: 0).  x_bf16: the rows are bf16 (dodt_fc_forward_bf16 and its split form), ldx in
+ * elements.  bf16_bk: the stage depth the bf16-row weights are blocked for, 32 or 64 (DODT_FC_BF16_DMA_BK in the
+ * process that creates the layer). */
+int dodt_fc_plan_host(int K, int N, int flags, int M, int ldx, int ldy, int x_off, int x2_off, int y_off, int x_bf16,
+                      int y_bf16, int bf16_bk, dodt_fc_plan* out);
+/* The same record for a built layer and a call's real pointers (d_x2, d_y may be NULL). */
+int dodt_fc_form(const dodt_fc* fc, const void* d_x, const void* d_x2, int ldx, int M, const void* d_y, int ldy,
+                 int x_bf16, int y_bf16, dodt_fc_plan* out);
 
 /* ---- a13: NMS -------------------------------------------------------------------------
  * tf.image.non_max_suppression(boxes, scores, max_output_size, iou_threshold),

@@ -13,6 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VARIANTS = [
     # the bf16-row GEMM with 64-k stages (default 32)
     ({'DODT_FC_BF16_DMA_BK': '64'}, ['tests/test_gpu_heads.py', '-k', 'bf16_rows']),
+    # ... on the case table's bf16-row cases: the layers then select kBf16RowsDma64, as the host plan of that depth says
+    # (DODT_FC_BF16_ROWS at its default, spelled out: it keeps this entry's test id apart from the one above)
+    ({'DODT_FC_BF16_DMA_BK': '64', 'DODT_FC_BF16_ROWS': '1'}, ['tests/test_gpu_fc_forms.py', '-k', 'bf16_rows']),
     # bf16 heads on float32 activations, rounded on every load (round 3's form), through the whole pair
     ({'DODT_FC_BF16_ROWS': '0'}, ['tests/test_gpu_heads.py', '-k', 'stagewise and bf16']),
     # correlation: 512-lane workgroups with the channels split over half-waves; round 3's two-pass kernel
