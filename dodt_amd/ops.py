@@ -629,3 +629,95 @@ def track_encoded(ctx, d_state, d_track, d_ious, d_counts, n_pairs, max_rows, hi
     _lib.check(ctx.lib.dodt_track_encoded(
         ctx.handle, _p(d_state), _p(d_track), _p(d_ious), _p(d_counts), int(n_pairs), int(max_rows),
         float(high_threshold), float(iou_threshold), int(t_min)), 'dodt_track_encoded')
+
+
+# ---- the Kalman-filter tracker (dodt_kf_*, dodt_amd/csrc/kalman.hip) ---------------------------------------------------
+def kf_ego_rows(ego):
+    """One (trans (3,), matrix (3,3), delta) per keyframe, or None for a parked ego -> (n, 13) float64: the rows
+    dodt_kf_* take (the forward transform, no inverse is taken)."""
+    out = np.zeros((len(ego), 13))
+    for i, e in enumerate(ego):
+        if e is None:
+            out[i, 3:12] = np.eye(3).reshape(-1)
+            continue
+        trans, matrix, delta = e
+        out[i, 0:3] = np.asarray(trans, np.float64).reshape(3)
+        out[i, 3:12] = np.asarray(matrix, np.float64).reshape(9)
+        out[i, 12] = float(delta)
+    return out
+
+
+def _kf_tail(p):
+    return (float(p['sigma_l']), float(p['iou_threshold']), int(p['max_age']), int(p['min_hits']), float(p['L']),
+            float(p['R_scaler']))
+
+
+def kf_state_bytes(log_capacity):
+    """Bytes of a Kalman tracker state buffer (dodt_kf_state_bytes)."""
+    n = C.c_size_t()
+    _lib.check(_lib.load().dodt_kf_state_bytes(int(log_capacity), C.byref(n)), 'dodt_kf_state_bytes')
+    return int(n.value)
+
+
+def kf_reset(ctx, d_state, log_capacity):
+    _lib.check(ctx.lib.dodt_kf_reset(ctx.handle, _p(d_state), int(log_capacity)), 'dodt_kf_reset')
+
+
+def kf_track_keyframes(ctx, d_state, d_rows, d_counts, n_keyframes, max_rows, ego_rows, calib42, params):
+    """n_keyframes encoded lists (dodt_kf_track_keyframes): d_rows (n, max_rows, 16) float64, d_counts (n,) int32,
+    ego_rows (n, 13) (kf_ego_rows), calib42 (temporal_calib), params: sigma_l, iou_threshold, max_age, min_hits, L,
+    R_scaler."""
+    if d_rows.dtype != np.float64:
+        raise ValueError('keyframe rows must be float64')
+    ego_rows = np.asarray(ego_rows, np.float64).reshape(-1)
+    if len(ego_rows) != 13 * int(n_keyframes):
+        raise ValueError('kf_track_keyframes: one ego row (13) per keyframe')
+    _lib.check(ctx.lib.dodt_kf_track_keyframes(
+        ctx.handle, _p(d_state), _p(d_rows), _p(d_counts), int(n_keyframes), int(max_rows),
+        _arr(C.c_double, ego_rows), _arr(C.c_double, calib42), *_kf_tail(params)), 'dodt_kf_track_keyframes')
+
+
+def kf_track_pairs(ctx, d_state, d_records, d_counts, n_pairs, max_det, p2, image_wh, score_threshold, ego_rows,
+                   calib42, params):
+    """Encode n_pairs record pairs and track their keyframe-0 lists (dodt_kf_track_pairs); ego_rows[j]: the motion
+    into pair j's keyframe 0."""
+    if d_records.dtype not in (np.float32, np.float64):
+        raise ValueError('records must be float32 or float64')
+    ego_rows = np.asarray(ego_rows, np.float64).reshape(-1)
+    if len(ego_rows) != 13 * int(n_pairs):
+        raise ValueError('kf_track_pairs: one ego row (13) per pair')
+    _lib.check(ctx.lib.dodt_kf_track_pairs(
+        ctx.handle, _p(d_state), _p(d_records), int(d_records.dtype == np.float64), _p(d_counts), int(n_pairs),
+        int(max_det), _arr(C.c_double, np.asarray(p2, np.float64).reshape(12)), float(image_wh[0]),
+        float(image_wh[1]), float(score_threshold), _arr(C.c_double, ego_rows), _arr(C.c_double, calib42),
+        *_kf_tail(params)), 'dodt_kf_track_pairs')
+
+
+def kf_flush(ctx, d_state, ego_row, calib42, params):
+    """The kept keyframe-1 rows as the final keyframe (ego_row: 13 doubles or None), then finish (dodt_kf_flush)."""
+    ego = None if ego_row is None else _arr(C.c_double, np.asarray(ego_row, np.float64).reshape(13))
+    _lib.check(ctx.lib.dodt_kf_flush(ctx.handle, _p(d_state), ego, _arr(C.c_double, calib42), *_kf_tail(params)),
+               'dodt_kf_flush')
+
+
+def kf_filter_steps(ctx, d_x0, d_ops, d_z, d_n_ops, d_LR, n_tracks, max_ops, d_x_out, d_P_out):
+    """The track filter alone (dodt_kf_filter_steps): x (n, max_ops, 8) and P (n, max_ops, 8, 8) after every
+    operation."""
+    _lib.check(ctx.lib.dodt_kf_filter_steps(ctx.handle, _p(d_x0), _p(d_ops), _p(d_z), _p(d_n_ops), _p(d_LR),
+                                            int(n_tracks), int(max_ops), _p(d_x_out), _p(d_P_out)),
+               'dodt_kf_filter_steps')
+
+
+def kf_assign(ctx, d_iou, n_tracks, n_dets, iou_threshold, d_matches, d_unmatched_dets, d_unmatched_tracks,
+              d_counts):
+    """Optimal assignment + gate of a float32 (n_tracks, n_dets) IoU matrix (dodt_kf_assign)."""
+    _lib.check(ctx.lib.dodt_kf_assign(ctx.handle, _p(d_iou), int(n_tracks), int(n_dets), float(iou_threshold),
+                                      _p(d_matches), _p(d_unmatched_dets), _p(d_unmatched_tracks), _p(d_counts)),
+               'dodt_kf_assign')
+
+
+def kf_iou_matrix(ctx, d_last, n_tracks, d_dets, n_dets, ego_row, calib42, d_iou_out):
+    """cal_transformed_ious of boxes [h,w,l,x,y,z,ry] float64 as float32 (dodt_kf_iou_matrix)."""
+    ego = None if ego_row is None else _arr(C.c_double, np.asarray(ego_row, np.float64).reshape(13))
+    _lib.check(ctx.lib.dodt_kf_iou_matrix(ctx.handle, _p(d_last), int(n_tracks), _p(d_dets), int(n_dets), ego,
+                                          _arr(C.c_double, calib42), _p(d_iou_out)), 'dodt_kf_iou_matrix')

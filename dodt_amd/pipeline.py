@@ -155,7 +155,9 @@ def resolve_schedule(environ, computed_heads, frames_per_sample, n_side_streams)
 # computes them, and adds the side streams' head scratch
 # `geoms`: the geometry (_Geometry) of every frame of the step, as its prep used it
 # `active`: None, or per tracker lane whether the step's pair belongs to that lane's video (tracker=dict(lanes=True))
-_Step = namedtuple('_Step', 'step cur rslot heads recover geoms fr feat counts scratch active', defaults=(None,) * 5)
+# `ego`: per pair of the step its (trans, matrix, delta) or None (pipelines with the Kalman tracker, which associates the
+# NEXT keyframe with it)
+_Step = namedtuple('_Step', 'step cur rslot heads recover geoms fr feat counts scratch active ego', defaults=(None,) * 6)
 
 
 def _pad_lookahead(lookahead):
@@ -238,6 +240,12 @@ class FramePairPipeline(object):
         for it.  With lanes=True pair p of every step belongs to LANE p instead: pairs_per_step (at most 5, the
         pipeline's limit) videos side by side, each lane with its own tracker state, calibration and
         end_sequence(lane=) (run()'s `active`); needs sequence=False.
+        With kind='kalman' (default 'iou') the stage is the Kalman-filter tracker instead:
+        dict(kind='kalman', sigma_l=0.0, iou_threshold=0.1, max_age=3, min_hits=3, stride=None, L=10.0, R_scaler=1/16,
+        score_threshold=0.1, max_sequence_dets=65536) -- pair j's keyframe 0 is keyframe j of the sequence, the last
+        pair's keyframe 1 the final one; stride: frames between two keyframes (None: tau of `temporal`, or 1).  Every
+        ego_motion entry of its steps is None (parked) or (trans, matrix, delta); tracks_so_far() and end_sequence()
+        return kalman_tracker.Tracker objects; no lanes.
         bev_input_skip: the fp32 BEV net skips the tiles that no BEV cell inside the camera's frustum reaches (their
         values depend on the weights alone, dodt_extractor_set_input_support); False: full tables.
         bev_frame_tables: with bev_input_skip, every step also filters those tables on the device by the cells that are
@@ -298,6 +306,7 @@ class FramePairPipeline(object):
             raise ValueError('image_wh_max is smaller than image_wh')
         self.track_geom = None         # the geometry of the tracker's current sequence (None: none has begun)
         self.lanes = self.tracker is not None and self.tracker['lanes']
+        self.kalman = self.tracker is not None and self.tracker.get('kind') == 'kalman'
         self.track_geoms = [None] * self.pairs      # (lanes: the same per lane)
         # streams: conv stacks of the two nets side by side, per-frame work on its own.  A second pipeline in the same
         # process takes the first one's streams (`reuse_streams_of`): new ones would share hardware queues with them
@@ -490,7 +499,11 @@ class FramePairPipeline(object):
         # ---- the IoU tracker (opt-in): one sequence's state on the device, launches on the image stream ------------
         if self.tracker is not None:
             tk = self.tracker
-            if self.lanes:     # one state per pair of a step, in one buffer
+            if self.kalman:
+                self.track_state = tracking.KalmanTracker(self.ctx, tk['sigma_l'], tk['iou_threshold'], tk['max_age'],
+                                                          tk['min_hits'], tk['L'], tk['R_scaler'],
+                                                          log_capacity=tk['max_sequence_dets'])
+            elif self.lanes:     # one state per pair of a step, in one buffer
                 self.track_state = tracking.TrackerLanes(self.ctx, self.pairs, tk['max_sequence_dets'],
                                                          tk['high_threshold'], tk['iou_threshold'], tk['t_min'],
                                                          tk['score_threshold'])
@@ -525,6 +538,11 @@ class FramePairPipeline(object):
         if self.fps != 2:
             raise ValueError('tracker: needs frame pairs (frames_per_sample == 2)')
         t = dict(tracker)
+        kind = t.pop('kind', 'iou')
+        if kind == 'kalman':
+            return self._kalman_args(t)
+        if kind != 'iou':
+            raise ValueError("tracker: kind must be 'iou' or 'kalman'")
         tk = dict(score_threshold=float(t.pop('score_threshold', 0.1)),
                   high_threshold=float(t.pop('high_threshold', 0.5)),
                   iou_threshold=float(t.pop('iou_threshold', 0.005)), t_min=int(t.pop('t_min', 3)),
@@ -537,6 +555,38 @@ class FramePairPipeline(object):
         if tk['max_sequence_dets'] < 1:
             raise ValueError('tracker: max_sequence_dets must be >= 1')
         return tk
+
+    def _kalman_args(self, t):
+        """tracker=dict(kind='kalman', ...) without its kind."""
+        if t.pop('lanes', False):
+            raise ValueError("tracker: kind='kalman' has no lanes")
+        stride = t.pop('stride', None)
+        tk = dict(kind='kalman', lanes=False, score_threshold=float(t.pop('score_threshold', 0.1)),
+                  sigma_l=float(t.pop('sigma_l', 0.0)), iou_threshold=float(t.pop('iou_threshold', 0.1)),
+                  max_age=int(t.pop('max_age', 3)), min_hits=int(t.pop('min_hits', 3)),
+                  stride=None if stride is None else int(stride), L=float(t.pop('L', 10.0)),
+                  R_scaler=float(t.pop('R_scaler', 1.0 / 16)), classes=tuple(t.pop('classes', self.classes)),
+                  max_sequence_dets=int(t.pop('max_sequence_dets', 65536)))
+        if t:
+            raise ValueError('tracker: unknown keys %s' % sorted(t))
+        if tk['stride'] is not None and tk['stride'] < 1:
+            raise ValueError('tracker: stride must be >= 1')
+        if tk['max_sequence_dets'] < 1:
+            raise ValueError('tracker: max_sequence_dets must be >= 1')
+        return tk
+
+    def _check_ego(self, *ego_motions):
+        """Kalman tracker: what the association cannot take, refused before anything is enqueued.  ego_motions: a step's
+        ego_motion (None, or a list of entries) -- this call's and its look-ahead's."""
+        if not self.kalman:
+            return
+        for em in ego_motions:
+            if em is not None and len(em) != (1 if self.sequence else self.pairs):
+                raise ValueError('ego_motion: one entry per pair of the step')
+            for e in em or ():
+                if e is not None and len(e) != 3:
+                    raise ValueError("ego_motion: with tracker kind='kalman' an entry is None (parked) or (trans, matrix, "
+                                     "delta); the association needs the yaw delta")
 
     # ---- per-sample geometry (DESIGN section 8e) -------------------------------------------------------------------
     def _geometry(self, calib):
@@ -717,6 +767,7 @@ class FramePairPipeline(object):
             raise ValueError('run_from_host: a sequence pipeline takes push_frame_from_host()')
         la = _pad_lookahead(lookahead)
         geoms, la_geoms, active = self._check_run(h_images, heads, la, calib, host=True, active=active)
+        self._check_ego(ego_motion, None if la is None else la[3])
         if self.prepped == self.step_idx:       # staged and prepared by the previous call's look-ahead
             d_pts = d_imgs = None
         else:
@@ -765,7 +816,7 @@ class FramePairPipeline(object):
         None) into d_bev, the anchor filter on the un-registered grid, the fetch of its count into `slot`, the kept
         anchors' projections -- all into the set b --, and the preprocessed image into d_img; under the geometry g of the
         frame's sample."""
-        bp = g.bp if ego_motion is None else ops.with_ego_motion(g.bp, *ego_motion)
+        bp = g.bp if ego_motion is None else ops.with_ego_motion(g.bp, *ego_motion[:2])   # (a third entry: the yaw delta)
         ops.bev_slices(c, d_points, n_points, bp, d_bev, b['occ'])
         ops.anchor_filter(c, b['occ'], self.nx, self.nz, self.d_cells, self.n_all, b['keep'], b['count'])
         ops.fetch_i32_begin(c, b['count'], 1, slot)
@@ -786,7 +837,9 @@ class FramePairPipeline(object):
         ego_motion: None, or one (trans (3,), matrix (3,3)) per pair of the step -- the
         registration of the pair's second frame into the first frame's coordinates
         (datasets.kitti.kitti_tracking_utils.coordinate_transform; applied to the second
-        frame's BEV maps, not to its anchor-filter grid, like the reference).
+        frame's BEV maps, not to its anchor-filter grid, like the reference).  An entry may be None (a parked ego) and
+        may carry a third element, the yaw delta of coordinate_transform: the Kalman tracker's association needs it
+        (a 2-tuple is refused there), every other pipeline ignores it.
         lookahead: None, or (d_points, n_points, d_images[, ego_motion[, calib]]) of the NEXT step: its prep is enqueued now,
         in front of the previous step's tail on the side streams, so that the next step's convs do not wait for
         that tail (a caller that knows its next inputs -- a stream of frames -- should pass them; the next call
@@ -814,6 +867,7 @@ class FramePairPipeline(object):
             raise ValueError('run: a sequence pipeline takes push_frame()')
         la = _pad_lookahead(lookahead)
         geoms, la_geoms, active = self._check_run(d_images, heads, la, calib, host=False, active=active)
+        self._check_ego(ego_motion, None if la is None else la[3])
         if la is not None:
             la = la[:4] + (la_geoms,)
         return self._step(self._prep, (d_points, n_points, d_images, ego_motion, geoms), heads, la, recover, geoms,
@@ -901,14 +955,18 @@ class FramePairPipeline(object):
             prep(k + 1, *lookahead, ahead=True)
         # -- the previous step's tail runs under this step's convs --------------------------
         self._pending_tail()
-        self.pending = self._step_record(k, heads, recover is not None, geoms, active)
+        ego = None
+        if self.kalman:         # (run(): one entry per pair or None; push_frame(): the new frame's entry or None)
+            em = inputs[3]
+            ego = [em] if self.sequence else [None] * self.pairs if em is None else list(em)
+        self.pending = self._step_record(k, heads, recover is not None, geoms, active, ego)
         self.step_idx += 1
         return cur
 
-    def _step_record(self, k, heads=None, recover=False, geoms=None, active=None):
+    def _step_record(self, k, heads=None, recover=False, geoms=None, active=None, ego=None):
         """The record of step k as the call that enqueues it leaves it in `pending` (_Step)."""
         return _Step(step=k, cur=k & 1, rslot=k % len(self.rec2), heads=heads, recover=recover,
-                     geoms=[self.geom0] * self.nf if geoms is None else geoms, active=active)
+                     geoms=[self.geom0] * self.nf if geoms is None else geoms, active=active, ego=ego)
 
     def _image_forward(self, k):
         """The image stack of step k on the image stream: over every frame of the step into feat[k & 1]; in sequence
@@ -1021,6 +1079,7 @@ class FramePairPipeline(object):
             raise ValueError('calib: a sequence has one calibration; it changes only on the push that begins one')
         if self.seq_primed and (heads is None) != (self.rpn_head is not None):
             raise ValueError('pass `heads` exactly when the pipeline has no head_params')
+        self._check_ego([ego_motion] if self.seq_primed else None, None if la is None else [la[3]])
         if self.prepped != k or not self.seq_primed:         # (else: prepared, and checked, by the previous call)
             self._check_images([d_image], [g], host)
         if la is not None:
@@ -1147,6 +1206,14 @@ class FramePairPipeline(object):
             self._mark(c, st.step, 'tracker_end')
             return
         g = st.geoms[0]        # (one per sequence, _check_run / _push)
+        if self.kalman:
+            # the same place and slot argument; each pair's own motion associates the keyframe after it (the state
+            # object keeps the last one for the next step), all of it by value in the kernel arguments
+            self.track_state.track_records(self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, g.p2, g.image_wh,
+                                           st.ego or [None] * self.pairs, g.temporal_rows(),
+                                           self.tracker['score_threshold'], ctx=c)
+            self._mark(c, st.step, 'tracker_end')
+            return
         self.track_state.track_records(self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, g.p2, g.image_wh, ctx=c)
         self._mark(c, st.step, 'tracker_end')
 
@@ -1177,15 +1244,35 @@ class FramePairPipeline(object):
         sequence (lanes pipelines, where a pair's number counts the lane's own active steps)."""
         state = self._lane(lane, 'tracks_so_far')
         self.ctx.wait_for(self.img_ctx)             # (the downloads go through the main stream)
+        if self.kalman:
+            return self._kalman_tracks(frame_ids, None)
         return tracking.tracks_from_log(state.read(), self._frame_ids(frame_ids), self.tracker['classes'])
 
-    def end_sequence(self, frame_ids=None, lane=None):
+    def _kalman_stride(self):
+        if self.tracker['stride'] is not None:
+            return self.tracker['stride']
+        return self.temporal['n_frames'] - 1 if self.temporal is not None else 1
+
+    def _kalman_tracks(self, frame_ids, frame_total):
+        """The Kalman tracker's finished tracks as kf_pipeline returns them: kalman_tracker.Tracker objects whose dets
+        (dicts 'frame_id' = keyframe * stride, 'boxes3d' [h,w,l,x,y,z,ry], 'boxes2d', 'scores'; virtual ones included)
+        are rebuilt from the device's log by interpolation_detections."""
+        if frame_ids is not None:
+            raise ValueError("frame_ids: the Kalman tracker numbers frames keyframe * stride (tracker=dict(stride=))")
+        fin, log = self.track_state.read()
+        tk = self.tracker
+        return tracking.kf_tracks_from_log(fin, log, self._kalman_stride(), frame_total, L=tk['L'],
+                                           R_scaler=tk['R_scaler'])
+
+    def end_sequence(self, frame_ids=None, lane=None, frame_total=None):
         """End the sequence after finish(): finish the remaining active tracks, download, and start a new sequence.
         Returns the host function's tracks_finished (kept as last_sequence_tracks for kitti_tracking_rows()).
         Sequence mode: the next push_frame() primes again, and a look-ahead that no push followed is dropped; without a
         tracker that is all (returns None).  Lanes: ends lane `lane`'s sequence alone -- its state is flushed, downloaded
         and reset, the other lanes go on --, kept as last_sequence_tracks[lane]; finish() first all the same, so ending one
-        video drains the pipeline once."""
+        video drains the pipeline once.  Kalman tracker: the last pair's keyframe 1 is tracked as the final keyframe
+        first; returns kf_pipeline's Tracker objects, frame ids keyframe * stride, a coasting track's virtual detections
+        at most at frame_total - 1 (None: no clamp)."""
         if self.tracker is None and not self.sequence:
             raise ValueError('end_sequence: the pipeline has no tracker')
         if self.lanes:
@@ -1203,11 +1290,20 @@ class FramePairPipeline(object):
             raise ValueError('end_sequence: lane= needs a pipeline built with tracker=dict(lanes=True)')
         if self.pending is not None:
             raise ValueError('end_sequence: call finish() first (the last step is not tracked yet)')
+        geom = self.geom0 if self.track_geom is None else self.track_geom
         self.track_geom = None         # (the next sequence may bring another calibration)
         if self.sequence:
             self.seq_primed, self.prepped = False, -1
             if self.tracker is None:
                 return None
+        if self.kalman:
+            # the last pair's keyframe 1 is the sequence's final keyframe, then kf_pipeline's last statement
+            self.track_state.flush(geom.temporal_rows(), ctx=self.img_ctx)
+            self.ctx.wait_for(self.img_ctx)
+            tracks = self._kalman_tracks(frame_ids, frame_total)
+            self.track_state.reset(ctx=self.img_ctx)
+            self.last_sequence_tracks = tracks
+            return tracks
         self.track_state.flush(ctx=self.img_ctx)
         tracks = self.tracks_so_far(frame_ids)
         self.track_state.reset(ctx=self.img_ctx)
@@ -1218,7 +1314,13 @@ class FramePairPipeline(object):
         """convert_trajectory_to_kitti_format of `tracks` (default: the last sequence end_sequence() returned, on a lanes
         pipeline the last one of lane `lane`): the reference's KITTI tracking rows, as strings."""
         from dodt_amd.core.dt_evaluator_utils import convert_trajectory_to_kitti_format
+        # (the converter takes encode_tracking_dets' label items -- 'info', 'offsets', string frame ids --, which a Kalman
+        #  track's detections are not)
+        if tracks is not None and len(tracks) and not isinstance(tracks[0], dict):
+            raise ValueError('kitti_tracking_rows: not for the Kalman tracker\'s Tracker objects (DESIGN section 8g)')
         if tracks is None:
+            if self.kalman:
+                raise ValueError("kitti_tracking_rows: not for tracker kind='kalman' (DESIGN section 8g)")
             if self.lanes:
                 self._lane(lane, 'kitti_tracking_rows')
                 tracks = self.last_sequence_tracks[int(lane)]

@@ -5,6 +5,10 @@ of dicts out, the encoding and the tracking in HIP (dodt_amd/csrc/tracking.hip).
 Tracker owns one sequence's device state.  The pipeline runs the same kernels on its detection records in place
 (FramePairPipeline(tracker=...), tracks_so_far(), end_sequence()); these wrappers are what the tests compare with
 the host module and the reference's goldens.
+
+KalmanTracker / kf_pipeline: the Kalman-filter variant (dodt_amd.experiments.video_detection_kf.kf_pipeline) the same
+way -- the IoU matrix, the optimal assignment, the filter and the track lists in HIP (dodt_amd/csrc/kalman.hip), the
+host function's arguments in and its list of kalman_tracker.Tracker objects out.
 """
 import numpy as np
 
@@ -125,6 +129,199 @@ class TrackerLanes(object):
 
 def _floats(rows, a, b):
     return np.ascontiguousarray(rows[:, a:b]).view(np.float32)
+
+
+# ---- the Kalman-filter tracker (dodt_amd/csrc/kalman.hip) ---------------------------------------------------------------
+KF_MAX_LIVE = 256               # live tracks at the start of a keyframe
+KF_STATUS_LOG, KF_STATUS_LIVE, KF_STATUS_SOLVER = 1, 2, 4
+# the state buffer (kalman.hip: KfHeader, KfTrack[256 + 128], the kept keyframe-1 rows, KfTrack[cap], KfLog[cap])
+_KF_HDR = ('n_live', 'next_id', 'n_log', 'n_fin', 'keyframe', 'status', 'log_cap', 'n_k1')
+KF_TRACK = np.dtype([('id', '<i4'), ('hits', '<i4'), ('no_losses', '<i4'), ('last_kf', '<i4'), ('x', '<f8', (8,)),
+                     ('P', '<f8', (4, 2, 2)), ('det', '<f8', (12,))])
+KF_LOG = np.dtype([('id', '<i4'), ('keyframe', '<i4'), ('kind', '<i4'), ('row', '<i4'), ('det', '<f8', (12,))])
+_KF_LIVE_OFF = _HDR_BYTES
+_KF_K1_OFF = _KF_LIVE_OFF + (KF_MAX_LIVE + MAX_ROWS) * KF_TRACK.itemsize
+_KF_FIN_OFF = _KF_K1_OFF + MAX_ROWS * K1_COLS * 4
+_POS = [3, 4, 5]
+
+
+class KalmanTracker(object):
+    """One sequence's Kalman-filter tracker state on the device (video_detection_kf.kf_pipeline's live / done lists and
+    a log of every real and coasting entry of a track).  Limits: 128 detections per keyframe, 256 live tracks at the
+    start of a keyframe, log_capacity log entries and finished tracks; running past one raises when the state is read.
+    Every launch goes on `ctx` (default: the state's context)."""
+
+    def __init__(self, ctx=None, sigma_l=0.0, iou_threshold=0.1, max_age=3, min_hits=3, L=10.0, R_scaler=1.0 / 16,
+                 log_capacity=8192, d_state=None):
+        self.ctx = ctx or device.default_context()
+        self.cap = int(log_capacity)
+        if self.cap < 1:
+            raise ValueError('log_capacity must be >= 1')
+        self.params = dict(sigma_l=float(sigma_l), iou_threshold=float(iou_threshold), max_age=int(max_age),
+                           min_hits=int(min_hits), L=float(L), R_scaler=float(R_scaler))
+        nbytes = ops.kf_state_bytes(self.cap)
+        assert KF_TRACK.itemsize == 304 and KF_LOG.itemsize == 112
+        assert nbytes == _KF_FIN_OFF + self.cap * (KF_TRACK.itemsize + KF_LOG.itemsize), 'state layout'
+        if d_state is not None and d_state.nbytes < nbytes:
+            raise ValueError('d_state: %d bytes, the state needs %d' % (d_state.nbytes, nbytes))
+        self.d_state = self.ctx.empty((nbytes,), np.uint8) if d_state is None else d_state
+        self.pending_ego = None         # (track_records: the last pair's own motion, the next keyframe's association)
+        self.reset()
+
+    def reset(self, ctx=None):
+        """Start a new sequence: ids from 0."""
+        ops.kf_reset(ctx or self.ctx, self.d_state, self.cap)
+        self.pending_ego = None
+
+    def flush(self, calib42, ctx=None):
+        """The end of kf_pipeline: the keyframe-1 rows track_records kept are the final keyframe, then the live tracks
+        with hits >= min_hits are finished."""
+        ego = None if self.pending_ego is None else ops.kf_ego_rows([self.pending_ego])[0]
+        ops.kf_flush(ctx or self.ctx, self.d_state, ego, calib42, self.params)
+        self.pending_ego = None
+
+    def track_keyframes(self, d_rows, d_counts, n_keyframes, max_rows, ego, calib42, ctx=None):
+        """n_keyframes encoded lists, continuing the sequence: d_rows (n, max_rows, 16) float64 (boxes2d 4:8, boxes3d
+        8:15, score 15), d_counts (n,); ego[k]: (trans, matrix, delta) from the keyframe before k to k, or None."""
+        ops.kf_track_keyframes(ctx or self.ctx, self.d_state, d_rows, d_counts, n_keyframes, max_rows,
+                               ops.kf_ego_rows(ego), calib42, self.params)
+
+    def track_records(self, d_records, d_counts, n_pairs, max_det, p2, image_wh, ego, calib42, score_threshold=0.1,
+                      ctx=None):
+        """Encode n_pairs record pairs (n_pairs, 2, max_det, 17) and track them: pair j's keyframe-0 rows are the next
+        keyframe of the sequence, the last pair's keyframe-1 rows wait for flush().  ego[j]: pair j's own motion
+        (trans, matrix, delta) from its keyframe 0 to its keyframe 1, or None -- the association of the keyframe
+        AFTER it."""
+        ego = list(ego)
+        if len(ego) != int(n_pairs):
+            raise ValueError('track_records: one ego entry per pair')
+        if n_pairs == 0:
+            return
+        into = [self.pending_ego] + ego[:-1]
+        ops.kf_track_pairs(ctx or self.ctx, self.d_state, d_records, d_counts, n_pairs, max_det, p2, image_wh,
+                           score_threshold, ops.kf_ego_rows(into), calib42, self.params)
+        self.pending_ego = ego[-1]
+
+    def header(self):
+        h = self.d_state.offset(0, (len(_KF_HDR),), np.int32).download()
+        return dict(zip(_KF_HDR, (int(v) for v in h)))
+
+    def used_bytes(self):
+        """The state's bytes that mean something (header, live tracks, kept rows, finished tracks, log), downloaded:
+        what two equal histories leave equal."""
+        h = self.header()
+        n_k1 = max(h['n_k1'], 0)
+        parts = [(0, _HDR_BYTES), (_KF_LIVE_OFF, h['n_live'] * KF_TRACK.itemsize), (_KF_K1_OFF, n_k1 * K1_COLS * 4),
+                 (_KF_FIN_OFF, min(h['n_fin'], self.cap) * KF_TRACK.itemsize),
+                 (_KF_FIN_OFF + self.cap * KF_TRACK.itemsize, min(h['n_log'], self.cap) * KF_LOG.itemsize)]
+        return [self.d_state.offset(off, (n,), np.uint8).download() for off, n in parts if n > 0]
+
+    def read(self):
+        """Download (synchronous on the state's context): (finished tracks, KF_TRACK records in finishing order; the log,
+        KF_LOG records in writing order).  Raises RuntimeError if a limit was exceeded."""
+        h = self.header()
+        if h['status'] & KF_STATUS_LIVE:
+            raise RuntimeError('kalman tracker: more than %d live tracks' % KF_MAX_LIVE)
+        if h['status'] & KF_STATUS_LOG:
+            raise RuntimeError('kalman tracker: log capacity %d exceeded (%d log entries, %d finished tracks needed)'
+                               % (self.cap, h['n_log'], h['n_fin']))
+        if h['status'] & KF_STATUS_SOLVER:
+            raise RuntimeError('kalman tracker: an IoU matrix without a finite assignment (NaN boxes)')
+        n_fin, n_log = h['n_fin'], h['n_log']
+        fin = self.d_state.offset(_KF_FIN_OFF, (max(n_fin, 1) * KF_TRACK.itemsize,), np.uint8).download()
+        log = self.d_state.offset(_KF_FIN_OFF + self.cap * KF_TRACK.itemsize, (max(n_log, 1) * KF_LOG.itemsize,),
+                                  np.uint8).download()
+        return fin.view(KF_TRACK)[:n_fin], log.view(KF_LOG)[:n_log]
+
+
+def kf_log_det(entry, stride):
+    """A log entry's detection as the host's dict (the pipeline's keyframe rows carry nothing else)."""
+    d = entry['det']
+    return {'frame_id': int(entry['keyframe']) * stride, 'boxes3d': np.array(d[0:7], np.float64),
+            'boxes2d': np.array(d[7:11], np.float64), 'scores': float(d[11])}
+
+
+def kf_tracks_from_log(fin, log, stride, frame_total=None, real_det=None, L=10.0, R_scaler=1.0 / 16):
+    """KalmanTracker.read() -> kf_pipeline's result: kalman_tracker.Tracker objects (id, hits, no_losses, x_state (8,1),
+    P (8,8), box, dets).  dets is rebuilt from the track's log entries as the host builds it: a real entry is
+    real_det(keyframe, row) (default: kf_log_det), a coasting one a copy of the entry before it at the logged position,
+    one stride on (at most frame_total - 1); interpolation_detections fills the frames in between."""
+    import copy
+
+    from dodt_amd.experiments.video_detection_kf import interpolation_detections
+    from dodt_amd.utils.kalman_tracker import Tracker as KfTrack
+    order = np.argsort(log['id'], kind='stable')
+    ids = log['id'][order]
+    out = []
+    for f in fin:
+        trk = KfTrack()
+        trk.L, trk.R_scaler = float(L), float(R_scaler)
+        trk.update_R()
+        trk.id, trk.hits, trk.no_losses = int(f['id']), int(f['hits']), int(f['no_losses'])
+        trk.x_state = np.array(f['x'], np.float64).reshape(8, 1)
+        trk.P = np.zeros((8, 8))
+        for b in range(4):
+            trk.P[2 * b:2 * b + 2, 2 * b:2 * b + 2] = f['P'][b]
+        trk.box = [float(trk.x_state[i, 0]) for i in (0, 2, 4, 6)]
+        lo, hi = np.searchsorted(ids, f['id'], 'left'), np.searchsorted(ids, f['id'], 'right')
+        for e in log[order[lo:hi]]:
+            if e['kind'] == 0:
+                det = kf_log_det(e, stride) if real_det is None else real_det(int(e['keyframe']), int(e['row']))
+            else:
+                if not trk.dets:
+                    raise RuntimeError('kalman tracker: track %d starts with a coasting entry' % trk.id)
+                det = copy.deepcopy(trk.dets[-1])
+                det['boxes3d'][_POS] = e['det'][3:6]
+                det['frame_id'] = det['frame_id'] + stride
+                if frame_total is not None:
+                    det['frame_id'] = min(det['frame_id'], frame_total - 1)
+                det['is_virtual'] = True
+            if trk.dets:
+                interpolation_detections(trk, det, stride)
+            else:
+                trk.dets.append(det)
+        out.append(trk)
+    return out
+
+
+def _kf_check_detections(detections, stride):
+    """What kf_pipeline refuses before anything reaches the device -> (rows (n, max_rows, 16) float64, counts (n,))."""
+    n = len(detections)
+    max_rows = max([1] + [len(f) for f in detections])
+    if max_rows > MAX_ROWS:
+        raise ValueError('at most %d detections per keyframe' % MAX_ROWS)
+    rows = np.zeros((n, max_rows, K1_COLS), np.float64)
+    counts = np.zeros((n,), np.int32)
+    for k, frame in enumerate(detections):
+        for i, det in enumerate(frame):
+            if int(det['frame_id']) != k * stride:
+                raise ValueError('kf_pipeline: detection %d of keyframe %d has frame_id %r, not %d'
+                                 % (i, k, det['frame_id'], k * stride))
+            rows[k, i, 4:8] = np.asarray(det['boxes2d'], np.float64).reshape(4)
+            rows[k, i, 8:15] = np.asarray(det['boxes3d'], np.float64).reshape(7)
+            rows[k, i, 15] = float(det['scores'])
+        counts[k] = len(frame)
+    return rows, counts
+
+
+def kf_pipeline(ego, calib, detections, stride, frame_total, sigma_l, iou_threshold, max_age=3, min_hits=3, ctx=None):
+    """video_detection_kf.kf_pipeline on the device (dodt_kf_track_keyframes): the host function's arguments, the same
+    list of Tracker objects whose dets hold the caller's detection dicts.  ego(k * stride - stride, k * stride) is called
+    once per keyframe k >= 1; a detection whose frame_id is not its keyframe's k * stride is a ValueError.  Boxes go
+    to the device as float64."""
+    rows, counts = _kf_check_detections(detections, stride)
+    n = len(detections)
+    if n == 0:
+        return []
+    ctx = ctx or device.default_context()
+    egos = [None] + [ego(k * stride - stride, k * stride) for k in range(1, n)]
+    calib42 = ops.temporal_calib(calib[0], calib[1])
+    cap = max(1, min(n * (KF_MAX_LIVE + MAX_ROWS), int(counts.sum()) * (int(max_age) + 2)))
+    tr = KalmanTracker(ctx, sigma_l, iou_threshold, max_age, min_hits, log_capacity=cap)
+    tr.track_keyframes(ctx.array(rows), ctx.array(counts), n, rows.shape[1], egos, calib42)
+    tr.flush(calib42)
+    fin, log = tr.read()
+    return kf_tracks_from_log(fin, log, stride, frame_total, real_det=lambda k, i: detections[k][i])
 
 
 def _label_item(frame_id, row, classes, offsets=None):

@@ -813,6 +813,72 @@ int dodt_track_encoded(dodt_ctx* ctx, void* d_state, const float* d_track, const
                        const int32_t* d_counts, int n_pairs, int max_rows, double high_threshold,
                        double iou_threshold, int t_min);
 
+/* ---- (h) the Kalman-filter tracker: keyframes -> tracks of filtered positions -----------------
+ * The reference's second video-level tracker (avod/experiments/video_detection_kf.py kf_pipeline with
+ * avod/utils/kalman_tracker.py); the host form is dodt_amd/experiments/video_detection_kf.py.  Per
+ * keyframe: the detections with score >= sigma_l; the float32 matrix of 3-D IoUs between every live
+ * track's last detection and every detection moved into the track's frame by the ego-motion; the optimal
+ * assignment (maximum total IoU) and the gate (an assigned pair with IoU < iou_threshold is unmatched on
+ * both sides); predict + update of the matched tracks with the measurement [x, y, z, z]; a new track per
+ * unmatched detection (those no track was assigned to, ascending, then the gate-failed ones in ascending
+ * track order; ids count from 0); the unmatched tracks coast (predict; a virtual detection at the
+ * predicted position, or the end of the track once its last detection lies outside the camera's wedge);
+ * tracks with no_losses > max_age leave, those with hits >= min_hits into the finished list.
+ * The state of one sequence lives in a device buffer the caller allocates (layout: dodt_amd/tracking.py):
+ * header, at most 256 live tracks at the start of a keyframe, the kept keyframe-1 rows, log_capacity
+ * finished tracks and log entries.  At most 128 detections per keyframe.  More live tracks, or a log
+ * past its capacity, set a bit of the state's status word; nothing is written out of bounds.
+ * Launches per batch of up to 16 keyframes on ctx's stream, nothing downloaded: (records only) the
+ * encoding of dodt_track_encode; the IoU matrix of the batch's first keyframe over the whole chip; the
+ * step (one workgroup: assignment on one wave by shortest augmenting paths, gate, filter one lane per
+ * track, compaction), which computes the later keyframes' matrices itself, since they depend on the
+ * step before.  ego: host, 13 doubles per keyframe -- trans (3), matrix (3x3 row major), delta of
+ * coordinate_transform from the keyframe BEFORE it to it; calib: host, the 42 doubles of
+ * dodt_interpolate_pairs; both read before the call returns and passed to the kernels by value.
+ *
+ * Bytes of a state buffer with room for log_capacity (>= 1) log entries and finished tracks. */
+int dodt_kf_state_bytes(int log_capacity, size_t* bytes);
+/* Start a sequence: empty state, ids from 0, keyframe 0. */
+int dodt_kf_reset(dodt_ctx* ctx, void* d_state, int log_capacity);
+/* n_keyframes lists already encoded: d_rows (n_keyframes, max_rows, 16) float64 in the KITTI row layout
+ * (boxes2d in cols 4..7, boxes3d [h,w,l,x,y,z,ry] in 8..14, score in 15; nothing else is read), d_counts
+ * (n_keyframes,) rows per list; max_rows <= 128. */
+int dodt_kf_track_keyframes(dodt_ctx* ctx, void* d_state, const double* d_rows, const int32_t* d_counts,
+                            int n_keyframes, int max_rows, const double* ego, const double* calib,
+                            double sigma_l, double iou_threshold, int max_age, int min_hits, double L,
+                            double R_scaler);
+/* n_pairs record pairs (dodt_track_pairs' arguments): pair j's keyframe-0 rows, encoded, are keyframe j
+ * of the batch; the last pair's keyframe-1 rows are kept in the state for dodt_kf_flush (a later batch
+ * replaces them).  ego[j]: the motion into pair j's keyframe 0. */
+int dodt_kf_track_pairs(dodt_ctx* ctx, void* d_state, const void* d_records, int records_f64,
+                        const int32_t* d_counts, int n_pairs, int max_det, const double* p2, double image_w,
+                        double image_h, double score_threshold, const double* ego, const double* calib,
+                        double sigma_l, double iou_threshold, int max_age, int min_hits, double L,
+                        double R_scaler);
+/* The end of the sequence: the kept keyframe-1 rows, if any, are the final keyframe (ego: the motion
+ * into it, NULL: none); then every live track with hits >= min_hits is finished, in order, and the live
+ * list is emptied. */
+int dodt_kf_flush(dodt_ctx* ctx, void* d_state, const double* ego, const double* calib, double sigma_l,
+                  double iou_threshold, int max_age, int min_hits, double L, double R_scaler);
+/* The filter alone, the step kernel's device functions: n_tracks independent tracks, one lane each.
+ * d_x0 (n_tracks, 4) initial positions (rates 0), d_LR (n_tracks, 3) [L0, L, R_scaler]: P0 = L0 I and
+ * R = R_scaler L I (the host class keeps the P of its construction when L is set afterwards), d_ops
+ * (n_tracks, max_ops) 0: predict, else predict + update with d_z (n_tracks, max_ops, 4); d_n_ops
+ * (n_tracks,).  After every operation: d_x_out (n_tracks, max_ops, 8), d_P_out (n_tracks, max_ops, 64). */
+int dodt_kf_filter_steps(dodt_ctx* ctx, const double* d_x0, const int32_t* d_ops, const double* d_z,
+                         const int32_t* d_n_ops, const double* d_LR, int n_tracks, int max_ops,
+                         double* d_x_out, double* d_P_out);
+/* The assignment and the gate alone: d_iou (n_tracks <= 256, n_dets <= 128) float32 -> d_matches (k, 2)
+ * [track, detection] in ascending track order, d_unmatched_dets and d_unmatched_tracks in the host's
+ * order, d_counts [k, unmatched detections, unmatched tracks, 1 if no finite assignment exists]. */
+int dodt_kf_assign(dodt_ctx* ctx, const float* d_iou, int n_tracks, int n_dets, double iou_threshold,
+                   int32_t* d_matches, int32_t* d_unmatched_dets, int32_t* d_unmatched_tracks,
+                   int32_t* d_counts);
+/* The association's IoU alone: d_iou_out (n_tracks, n_dets) float32 = cal_transformed_ious of boxes
+ * d_last (n_tracks, 7) and d_dets (n_dets, 7), [h,w,l,x,y,z,ry] float64, under one ego row (NULL: none). */
+int dodt_kf_iou_matrix(dodt_ctx* ctx, const double* d_last, int n_tracks, const double* d_dets, int n_dets,
+                       const double* ego, const double* calib, float* d_iou_out);
+
 /* ---- (e) multi-GPU: the one exchange step of the path, RCCL over xGMI, no PyTorch -----------
  * The reference runs on ONE device (avod/experiments/run_tracking_inference.py:109-128 sets a
  * single CUDA_VISIBLE_DEVICES and walks the sequences in a loop), so there is no reference
