@@ -243,6 +243,14 @@ SIGNATURES = {
     'dodt_kf_filter_steps': (_i, [_vp, _vp, _pi32, _vp, _pi32, _vp, _i, _i, _vp, _vp]),
     'dodt_kf_assign': (_i, [_vp, _pf, _i, _i, _d, _pi32, _pi32, _pi32, _pi32]),
     'dodt_kf_iou_matrix': (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(_d), C.POINTER(_d), _pf]),
+    'dodt_vt_state_bytes': (_i, [_i, C.POINTER(C.c_size_t)]),
+    'dodt_vt_reset': (_i, [_vp, _vp, _i]),
+    'dodt_vt_track_keyframes': (_i, [_vp, _vp, _vp, _i, _pi32, _i, _i, C.POINTER(_d), C.POINTER(_d), _d, _d, _d, _i,
+                                     _i, _i, _i, _i]),
+    'dodt_vt_track_pairs': (_i, [_vp, _vp, _vp, _i, _pi32, _i, _i, C.POINTER(_d), _d, _d, _d, C.POINTER(_d),
+                                 C.POINTER(_d), _d, _d, _d, _i, _i, _i]),
+    'dodt_vt_flush': (_i, [_vp, _vp, C.POINTER(_d), C.POINTER(_d), _d, _d, _d, _i, _i, _i]),
+    'dodt_vt_iou_matrix': (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(_d), C.POINTER(_d), _vp]),
 }
 COMM_ID_BYTES = 128
 

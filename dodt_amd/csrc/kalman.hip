@@ -17,6 +17,7 @@
 // P stays block diagonal (F, Q, H, R are, and P0 = L I), so four 2x2 blocks and a diagonal S are the whole arithmetic.
 // Builds with -ffp-contract=off.
 #include "common.h"
+#include "ego_transform.h"
 #include "iou3d.h"
 #include "track_encode.h"
 
@@ -87,9 +88,6 @@ __device__ void kf_load_det(const KfRows& r, int k, int i, double* det) {
     det[11] = kf_col(r, k, i, 15);
 }
 
-struct KfCalib {            // ops.temporal_calib: inv(R0_rect), inv(Tr_velo_to_cam) (3x4), Tr_velo_to_cam, R0_rect
-    double r0_inv[9], tr_inv[12], tr[12], r0[9];
-};
 struct KfEgo {              // per keyframe of a chunk: trans (3), matrix (3x3, row major), delta -- the motion from the
     double e[kChunk][13];   // keyframe before it
 };
@@ -98,35 +96,12 @@ struct KfParams {
     int max_age, min_hits;
 };
 
-// cal_transformed_ious: `det` [h,w,l,x,y,z,ry] moved into the frame of `last` (label_transform_box: corners -> velo ->
-// (+trans) @ matrix -> rect, the host's expression order), then iou_3d under the host's permutation to [x,y,z,l,w,h,ry]
+// cal_transformed_ious: `det` [h,w,l,x,y,z,ry] moved into the frame of `last` (ego_moved_box, ego_transform.h), then
+// iou_3d under the host's permutation to [x,y,z,l,w,h,ry]
 __device__ double kf_iou(const double* last, const double* det, const double* ego, const KfCalib& k) {
-    const double h = det[0], w = det[1], l = det[2], x = det[3], y = det[4], z = det[5], ry = det[6];
-    const double c = cos(ry), s = sin(ry);
-    const double rot[9] = {c, 0, s, 0, 1, 0, -s, 0, c};
-    const double xc[8] = {l / 2, l / 2, -l / 2, -l / 2, l / 2, l / 2, -l / 2, -l / 2};
-    const double yc[8] = {0, 0, 0, 0, -h, -h, -h, -h};
-    const double zc[8] = {w / 2, -w / 2, -w / 2, w / 2, w / 2, -w / 2, -w / 2, w / 2};
-    const double org[3] = {x, y, z};
-    double sum[3] = {0, 0, 0};
-    for (int v = 0; v < 8; ++v) {
-        double p[3], ref[3], velo[3], v2[3], ref2[3];
-        for (int r = 0; r < 3; ++r)
-            p[r] = rot[3 * r] * xc[v] + rot[3 * r + 1] * yc[v] + rot[3 * r + 2] * zc[v] + org[r];
-        for (int r = 0; r < 3; ++r)
-            ref[r] = k.r0_inv[3 * r] * p[0] + k.r0_inv[3 * r + 1] * p[1] + k.r0_inv[3 * r + 2] * p[2];
-        for (int r = 0; r < 3; ++r)
-            velo[r] = ref[0] * k.tr_inv[4 * r] + ref[1] * k.tr_inv[4 * r + 1] + ref[2] * k.tr_inv[4 * r + 2]
-                      + k.tr_inv[4 * r + 3];
-        for (int r = 0; r < 3; ++r)
-            v2[r] = (velo[0] + ego[0]) * ego[3 + r] + (velo[1] + ego[1]) * ego[6 + r] + (velo[2] + ego[2]) * ego[9 + r];
-        for (int r = 0; r < 3; ++r)
-            ref2[r] = v2[0] * k.tr[4 * r] + v2[1] * k.tr[4 * r + 1] + v2[2] * k.tr[4 * r + 2] + k.tr[4 * r + 3];
-        for (int r = 0; r < 3; ++r)
-            sum[r] += k.r0[3 * r] * ref2[0] + k.r0[3 * r + 1] * ref2[1] + k.r0[3 * r + 2] * ref2[2];
-    }
     const double a[7] = {last[3], last[4], last[5], last[2], last[1], last[0], last[6]};
-    const double b[7] = {sum[0] / 8, sum[1] / 8 + h / 2.0, sum[2] / 8, l, w, h, ry + ego[12]};
+    double b[7];
+    ego_moved_box(det, ego, k, b);
     return iou_3d(a, b);
 }
 

@@ -721,3 +721,71 @@ def kf_iou_matrix(ctx, d_last, n_tracks, d_dets, n_dets, ego_row, calib42, d_iou
     ego = None if ego_row is None else _arr(C.c_double, np.asarray(ego_row, np.float64).reshape(13))
     _lib.check(ctx.lib.dodt_kf_iou_matrix(ctx.handle, _p(d_last), int(n_tracks), _p(d_dets), int(n_dets), ego,
                                           _arr(C.c_double, calib42), _p(d_iou_out)), 'dodt_kf_iou_matrix')
+
+
+# ---- the velocity-extrapolating IoU tracker (dodt_vt_*, dodt_amd/csrc/velocity_track.hip) ------------------------------
+def _vt_tail(p):
+    return (float(p['sigma_l']), float(p['sigma_h']), float(p['sigma_iou']), int(p['t_min']), int(p['extend_len']),
+            int(p['stride']))
+
+
+def vt_state_bytes(log_capacity):
+    """Bytes of a velocity tracker state buffer (dodt_vt_state_bytes)."""
+    n = C.c_size_t()
+    _lib.check(_lib.load().dodt_vt_state_bytes(int(log_capacity), C.byref(n)), 'dodt_vt_state_bytes')
+    return int(n.value)
+
+
+def vt_reset(ctx, d_state, log_capacity):
+    _lib.check(ctx.lib.dodt_vt_reset(ctx.handle, _p(d_state), int(log_capacity)), 'dodt_vt_reset')
+
+
+def vt_track_keyframes(ctx, d_state, d_rows, d_counts, n_keyframes, max_rows, ego_rows, calib42, params, box_f64=None,
+                       score_f64=None):
+    """n_keyframes encoded lists (dodt_vt_track_keyframes): d_rows (n, max_rows, 16) float32 or float64, d_counts (n,)
+    int32, ego_rows (n, 13) (kf_ego_rows), calib42 (temporal_calib), params: sigma_l, sigma_h, sigma_iou, t_min,
+    extend_len, stride.  box_f64 / score_f64: the dtype the host holds boxes3d / the scores in -- the speed and the
+    predictions are computed, the scores compared in it (None: the rows' dtype; True only with float64 rows)."""
+    if d_rows.dtype not in (np.float32, np.float64):
+        raise ValueError('keyframe rows must be float32 or float64')
+    f64 = d_rows.dtype == np.float64
+    box_f64, score_f64 = (f64 if v is None else bool(v) for v in (box_f64, score_f64))
+    if (box_f64 or score_f64) and not f64:
+        raise ValueError('vt_track_keyframes: float64 boxes or scores need float64 rows')
+    ego_rows = np.asarray(ego_rows, np.float64).reshape(-1)
+    if len(ego_rows) != 13 * int(n_keyframes):
+        raise ValueError('vt_track_keyframes: one ego row (13) per keyframe')
+    _lib.check(ctx.lib.dodt_vt_track_keyframes(
+        ctx.handle, _p(d_state), _p(d_rows), int(d_rows.dtype == np.float64), _p(d_counts), int(n_keyframes),
+        int(max_rows), _arr(C.c_double, ego_rows), _arr(C.c_double, calib42), *_vt_tail(params), int(box_f64),
+        int(score_f64)), 'dodt_vt_track_keyframes')
+
+
+def vt_track_pairs(ctx, d_state, d_records, d_counts, n_pairs, max_det, p2, image_wh, score_threshold, ego_rows,
+                   calib42, params):
+    """Encode n_pairs record pairs and track their keyframe-0 lists (dodt_vt_track_pairs); ego_rows[j]: the motion
+    into pair j's keyframe 0."""
+    if d_records.dtype not in (np.float32, np.float64):
+        raise ValueError('records must be float32 or float64')
+    ego_rows = np.asarray(ego_rows, np.float64).reshape(-1)
+    if len(ego_rows) != 13 * int(n_pairs):
+        raise ValueError('vt_track_pairs: one ego row (13) per pair')
+    _lib.check(ctx.lib.dodt_vt_track_pairs(
+        ctx.handle, _p(d_state), _p(d_records), int(d_records.dtype == np.float64), _p(d_counts), int(n_pairs),
+        int(max_det), _arr(C.c_double, np.asarray(p2, np.float64).reshape(12)), float(image_wh[0]),
+        float(image_wh[1]), float(score_threshold), _arr(C.c_double, ego_rows), _arr(C.c_double, calib42),
+        *_vt_tail(params)), 'dodt_vt_track_pairs')
+
+
+def vt_flush(ctx, d_state, ego_row, calib42, params):
+    """The kept keyframe-1 rows as the final keyframe (ego_row: 13 doubles or None), then finish (dodt_vt_flush)."""
+    ego = None if ego_row is None else _arr(C.c_double, np.asarray(ego_row, np.float64).reshape(13))
+    _lib.check(ctx.lib.dodt_vt_flush(ctx.handle, _p(d_state), ego, _arr(C.c_double, calib42), *_vt_tail(params)),
+               'dodt_vt_flush')
+
+
+def vt_iou_matrix(ctx, d_last, n_tracks, d_dets, n_dets, ego_row, calib42, d_iou_out):
+    """video_detection_iou.cal_transformed_ious of boxes [h,w,l,x,y,z,ry] float64 as float64 (dodt_vt_iou_matrix)."""
+    ego = None if ego_row is None else _arr(C.c_double, np.asarray(ego_row, np.float64).reshape(13))
+    _lib.check(ctx.lib.dodt_vt_iou_matrix(ctx.handle, _p(d_last), int(n_tracks), _p(d_dets), int(n_dets), ego,
+                                          _arr(C.c_double, calib42), _p(d_iou_out)), 'dodt_vt_iou_matrix')

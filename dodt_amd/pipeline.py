@@ -246,6 +246,11 @@ class FramePairPipeline(object):
         pair's keyframe 1 the final one; stride: frames between two keyframes (None: tau of `temporal`, or 1).  Every
         ego_motion entry of its steps is None (parked) or (trans, matrix, delta); tracks_so_far() and end_sequence()
         return kalman_tracker.Tracker objects; no lanes.
+        With kind='velocity' it is the velocity-extrapolating greedy IoU tracker:
+        dict(kind='velocity', sigma_l=0.1, sigma_h=0.5, sigma_iou=0.1, t_min=3, extend_len=3, stride=None,
+        score_threshold=0.1, log_capacity=65536) -- keyframes, stride and ego_motion entries as for kind='kalman';
+        tracks_so_far() and end_sequence(frame_total=None) return video_detection_iou.interpolate_by_track's track dicts
+        (None: the sequence ends at the last keyframe), kitti_tracking_rows() that module's rows; no lanes, no frame_ids.
         bev_input_skip: the fp32 BEV net skips the tiles that no BEV cell inside the camera's frustum reaches (their
         values depend on the weights alone, dodt_extractor_set_input_support); False: full tables.
         bev_frame_tables: with bev_input_skip, every step also filters those tables on the device by the cells that are
@@ -307,6 +312,7 @@ class FramePairPipeline(object):
         self.track_geom = None         # the geometry of the tracker's current sequence (None: none has begun)
         self.lanes = self.tracker is not None and self.tracker['lanes']
         self.kalman = self.tracker is not None and self.tracker.get('kind') == 'kalman'
+        self.velocity = self.tracker is not None and self.tracker.get('kind') == 'velocity'
         self.track_geoms = [None] * self.pairs      # (lanes: the same per lane)
         # streams: conv stacks of the two nets side by side, per-frame work on its own.  A second pipeline in the same
         # process takes the first one's streams (`reuse_streams_of`): new ones would share hardware queues with them
@@ -503,6 +509,10 @@ class FramePairPipeline(object):
                 self.track_state = tracking.KalmanTracker(self.ctx, tk['sigma_l'], tk['iou_threshold'], tk['max_age'],
                                                           tk['min_hits'], tk['L'], tk['R_scaler'],
                                                           log_capacity=tk['max_sequence_dets'])
+            elif self.velocity:
+                self.track_state = tracking.VelocityTracker(self.ctx, tk['sigma_l'], tk['sigma_h'], tk['sigma_iou'],
+                                                            tk['t_min'], tk['extend_len'], self._kalman_stride(),
+                                                            log_capacity=tk['log_capacity'])
             elif self.lanes:     # one state per pair of a step, in one buffer
                 self.track_state = tracking.TrackerLanes(self.ctx, self.pairs, tk['max_sequence_dets'],
                                                          tk['high_threshold'], tk['iou_threshold'], tk['t_min'],
@@ -541,8 +551,10 @@ class FramePairPipeline(object):
         kind = t.pop('kind', 'iou')
         if kind == 'kalman':
             return self._kalman_args(t)
+        if kind == 'velocity':
+            return self._velocity_args(t)
         if kind != 'iou':
-            raise ValueError("tracker: kind must be 'iou' or 'kalman'")
+            raise ValueError("tracker: kind must be 'iou', 'kalman' or 'velocity'")
         tk = dict(score_threshold=float(t.pop('score_threshold', 0.1)),
                   high_threshold=float(t.pop('high_threshold', 0.5)),
                   iou_threshold=float(t.pop('iou_threshold', 0.005)), t_min=int(t.pop('t_min', 3)),
@@ -575,18 +587,45 @@ class FramePairPipeline(object):
             raise ValueError('tracker: max_sequence_dets must be >= 1')
         return tk
 
+    def _velocity_args(self, t):
+        """tracker=dict(kind='velocity', ...) without its kind."""
+        if t.pop('lanes', False):
+            raise ValueError("tracker: kind='velocity' has no lanes")
+        stride = t.pop('stride', None)
+        tk = dict(kind='velocity', lanes=False, score_threshold=float(t.pop('score_threshold', 0.1)),
+                  sigma_l=float(t.pop('sigma_l', 0.1)), sigma_h=float(t.pop('sigma_h', 0.5)),
+                  sigma_iou=float(t.pop('sigma_iou', 0.1)), t_min=int(t.pop('t_min', 3)),
+                  extend_len=int(t.pop('extend_len', 3)), stride=None if stride is None else int(stride),
+                  classes=tuple(t.pop('classes', self.classes)), log_capacity=int(t.pop('log_capacity', 65536)))
+        if t:
+            raise ValueError('tracker: unknown keys %s' % sorted(t))
+        if tk['stride'] is not None and not 1 <= tk['stride'] <= tracking.VT_MAX_STEP:
+            raise ValueError('tracker: stride must be 1..%d' % tracking.VT_MAX_STEP)
+        if not 1 <= tk['extend_len'] <= tracking.VT_MAX_STEP:
+            raise ValueError('tracker: extend_len must be 1..%d' % tracking.VT_MAX_STEP)
+        if tk['log_capacity'] < 1:
+            raise ValueError('tracker: log_capacity must be >= 1')
+        return tk
+
+    def _ego_deltas(self):
+        """The tracker stage associates across the ego-motion: every ego_motion entry must bring its yaw delta."""
+        # (getattr: __init__ always sets `velocity`; objects made bare by __new__, as tests/test_kalman_device_args.py
+        #  makes them, set `kalman` alone)
+        return self.kalman or getattr(self, 'velocity', False)
+
     def _check_ego(self, *ego_motions):
-        """Kalman tracker: what the association cannot take, refused before anything is enqueued.  ego_motions: a step's
-        ego_motion (None, or a list of entries) -- this call's and its look-ahead's."""
-        if not self.kalman:
+        """Kalman and velocity trackers: what the association cannot take, refused before anything is enqueued.
+        ego_motions: a step's ego_motion (None, or a list of entries) -- this call's and its look-ahead's."""
+        if not self._ego_deltas():
             return
         for em in ego_motions:
             if em is not None and len(em) != (1 if self.sequence else self.pairs):
                 raise ValueError('ego_motion: one entry per pair of the step')
             for e in em or ():
                 if e is not None and len(e) != 3:
-                    raise ValueError("ego_motion: with tracker kind='kalman' an entry is None (parked) or (trans, matrix, "
-                                     "delta); the association needs the yaw delta")
+                    raise ValueError("ego_motion: with tracker kind='%s' an entry is None (parked) or (trans, matrix, "
+                                     "delta); the association needs the yaw delta"
+                                     % ('kalman' if self.kalman else 'velocity'))
 
     # ---- per-sample geometry (DESIGN section 8e) -------------------------------------------------------------------
     def _geometry(self, calib):
@@ -956,7 +995,7 @@ class FramePairPipeline(object):
         # -- the previous step's tail runs under this step's convs --------------------------
         self._pending_tail()
         ego = None
-        if self.kalman:         # (run(): one entry per pair or None; push_frame(): the new frame's entry or None)
+        if self._ego_deltas():  # (run(): one entry per pair or None; push_frame(): the new frame's entry or None)
             em = inputs[3]
             ego = [em] if self.sequence else [None] * self.pairs if em is None else list(em)
         self.pending = self._step_record(k, heads, recover is not None, geoms, active, ego)
@@ -1206,7 +1245,7 @@ class FramePairPipeline(object):
             self._mark(c, st.step, 'tracker_end')
             return
         g = st.geoms[0]        # (one per sequence, _check_run / _push)
-        if self.kalman:
+        if self.kalman or self.velocity:
             # the same place and slot argument; each pair's own motion associates the keyframe after it (the state
             # object keeps the last one for the next step), all of it by value in the kernel arguments
             self.track_state.track_records(self.rec2[r], self.cnt2[r], self.pairs, MAX_DET, g.p2, g.image_wh,
@@ -1246,6 +1285,8 @@ class FramePairPipeline(object):
         self.ctx.wait_for(self.img_ctx)             # (the downloads go through the main stream)
         if self.kalman:
             return self._kalman_tracks(frame_ids, None)
+        if self.velocity:
+            return self._velocity_tracks(frame_ids, None)
         return tracking.tracks_from_log(state.read(), self._frame_ids(frame_ids), self.tracker['classes'])
 
     def _kalman_stride(self):
@@ -1263,6 +1304,20 @@ class FramePairPipeline(object):
         tk = self.tracker
         return tracking.kf_tracks_from_log(fin, log, self._kalman_stride(), frame_total, L=tk['L'],
                                            R_scaler=tk['R_scaler'])
+
+    def _velocity_tracks(self, frame_ids, frame_total):
+        """The velocity tracker's finished tracks as interpolate_by_track returns them: dicts 'dets' (dicts 'frame_id' =
+        keyframe * stride, 'info', 'boxes2d', 'boxes3d' [h,w,l,x,y,z,ry], 'score', float32; interpolated, predicted and
+        extended entries included), 'direction', 'max_score', 'speed', 'extend_len', rebuilt from the device's log
+        (tracking.vt_tracks_from_log).  frame_total None: the sequence ends at the last keyframe tracked."""
+        if frame_ids is not None:
+            raise ValueError("frame_ids: the velocity tracker numbers frames keyframe * stride (tracker=dict(stride=))")
+        fin, log = self.track_state.read()
+        stride = self._kalman_stride()
+        if frame_total is None:
+            frame_total = max(self.track_state.header()['keyframe'] - 1, 0) * stride + 1
+        return tracking.vt_tracks_from_log(fin, log, stride, self.tracker['extend_len'], frame_total,
+                                           classes=self.tracker['classes'])
 
     def end_sequence(self, frame_ids=None, lane=None, frame_total=None):
         """End the sequence after finish(): finish the remaining active tracks, download, and start a new sequence.
@@ -1296,11 +1351,11 @@ class FramePairPipeline(object):
             self.seq_primed, self.prepped = False, -1
             if self.tracker is None:
                 return None
-        if self.kalman:
-            # the last pair's keyframe 1 is the sequence's final keyframe, then kf_pipeline's last statement
+        if self.kalman or self.velocity:
+            # the last pair's keyframe 1 is the sequence's final keyframe, then the host function's last statements
             self.track_state.flush(geom.temporal_rows(), ctx=self.img_ctx)
             self.ctx.wait_for(self.img_ctx)
-            tracks = self._kalman_tracks(frame_ids, frame_total)
+            tracks = (self._kalman_tracks if self.kalman else self._velocity_tracks)(frame_ids, frame_total)
             self.track_state.reset(ctx=self.img_ctx)
             self.last_sequence_tracks = tracks
             return tracks
@@ -1314,6 +1369,14 @@ class FramePairPipeline(object):
         """convert_trajectory_to_kitti_format of `tracks` (default: the last sequence end_sequence() returned, on a lanes
         pipeline the last one of lane `lane`): the reference's KITTI tracking rows, as strings."""
         from dodt_amd.core.dt_evaluator_utils import convert_trajectory_to_kitti_format
+        if tracks is None and self.tracker is not None and self.velocity:
+            tracks = self.last_sequence_tracks
+            if tracks is None:
+                raise ValueError('kitti_tracking_rows: no sequence has ended')
+        # the velocity tracker's dicts ('dets') go through its own converter (video_detection_iou.py)
+        if tracks is not None and len(tracks) and isinstance(tracks[0], dict) and 'dets' in tracks[0]:
+            from dodt_amd.experiments import video_detection_iou
+            return video_detection_iou.convert_trajectory_to_kitti_format(tracks)
         # (the converter takes encode_tracking_dets' label items -- 'info', 'offsets', string frame ids --, which a Kalman
         #  track's detections are not)
         if tracks is not None and len(tracks) and not isinstance(tracks[0], dict):

@@ -9,6 +9,10 @@ the host module and the reference's goldens.
 KalmanTracker / kf_pipeline: the Kalman-filter variant (dodt_amd.experiments.video_detection_kf.kf_pipeline) the same
 way -- the IoU matrix, the optimal assignment, the filter and the track lists in HIP (dodt_amd/csrc/kalman.hip), the
 host function's arguments in and its list of kalman_tracker.Tracker objects out.
+VelocityTracker / interpolate_by_track: the velocity-extrapolating greedy IoU tracker
+(dodt_amd.experiments.video_detection_iou.interpolate_by_track) the same way -- the IoU matrix, the greedy walk, the
+predictions and the track lists in HIP (dodt_amd/csrc/velocity_track.hip), the host function's arguments in and its list of
+track dicts out.
 """
 import numpy as np
 
@@ -322,6 +326,232 @@ def kf_pipeline(ego, calib, detections, stride, frame_total, sigma_l, iou_thresh
     tr.flush(calib42)
     fin, log = tr.read()
     return kf_tracks_from_log(fin, log, stride, frame_total, real_det=lambda k, i: detections[k][i])
+
+
+# ---- the velocity-extrapolating IoU tracker (dodt_amd/csrc/velocity_track.hip) -----------------------------------------
+VT_STATUS_LOG, VT_STATUS_LIVE, VT_STATUS_IOU = 1, 2, 4
+VT_HAS_SPEED, VT_CUT = 1, 2             # VT_TRACK['flags']
+# the state buffer (velocity_track.hip: VtHeader, VtTrack[256 + 128], the kept keyframe-1 rows, VtTrack[cap], VtLog[cap]);
+# the header's fields are the Kalman state's
+VT_TRACK = np.dtype([('id', '<i4'), ('n_dets', '<i4'), ('extend_len', '<i4'), ('flags', '<i4'), ('max_score', '<f8'),
+                     ('speed', '<f8', (3,)), ('det', '<f8', (13,))])
+VT_LOG = np.dtype([('id', '<i4'), ('keyframe', '<i4'), ('kind', '<i4'), ('row', '<i4'), ('det', '<f8', (13,))])
+_VT_LIVE_OFF = _HDR_BYTES
+_VT_K1_OFF = _VT_LIVE_OFF + (KF_MAX_LIVE + MAX_ROWS) * VT_TRACK.itemsize
+_VT_FIN_OFF = _VT_K1_OFF + MAX_ROWS * K1_COLS * 4
+_XZR = [3, 5, 6]
+
+
+VT_MAX_STEP = 4096              # stride and extend_len: the bound of the device's prediction loop
+
+
+def _vt_check_params(stride, extend_len):
+    if not 1 <= int(stride) <= VT_MAX_STEP:
+        raise ValueError('stride must be 1..%d' % VT_MAX_STEP)
+    if not 1 <= int(extend_len) <= VT_MAX_STEP:
+        raise ValueError('extend_len must be 1..%d (the host function empties a coasting track at 0)' % VT_MAX_STEP)
+
+
+class VelocityTracker(object):
+    """One sequence's velocity-extrapolating IoU tracker state on the device (video_detection_iou.interpolate_by_track's
+    active / finished lists and a log of every real and predicted entry of a track).  Limits: 128 detections per
+    keyframe, 256 live tracks at the start of a keyframe, log_capacity log entries and finished tracks; running past
+    one, or an IoU that is not finite, raises when the state is read.  Every launch goes on `ctx` (default: the state's
+    context)."""
+
+    def __init__(self, ctx=None, sigma_l=0.1, sigma_h=0.5, sigma_iou=0.1, t_min=3, extend_len=3, stride=1,
+                 log_capacity=8192, d_state=None):
+        _vt_check_params(stride, extend_len)
+        self.cap = int(log_capacity)
+        if self.cap < 1:
+            raise ValueError('log_capacity must be >= 1')
+        self.ctx = ctx or device.default_context()
+        self.params = dict(sigma_l=float(sigma_l), sigma_h=float(sigma_h), sigma_iou=float(sigma_iou), t_min=int(t_min),
+                           extend_len=int(extend_len), stride=int(stride))
+        nbytes = ops.vt_state_bytes(self.cap)
+        assert VT_TRACK.itemsize == 152 and VT_LOG.itemsize == 120
+        assert nbytes == _VT_FIN_OFF + self.cap * (VT_TRACK.itemsize + VT_LOG.itemsize), 'state layout'
+        if d_state is not None and d_state.nbytes < nbytes:
+            raise ValueError('d_state: %d bytes, the state needs %d' % (d_state.nbytes, nbytes))
+        self.d_state = self.ctx.empty((nbytes,), np.uint8) if d_state is None else d_state
+        self.pending_ego = None         # (track_records: the last pair's own motion, the next keyframe's association)
+        self.reset()
+
+    def reset(self, ctx=None):
+        """Start a new sequence: ids from 0."""
+        ops.vt_reset(ctx or self.ctx, self.d_state, self.cap)
+        self.pending_ego = None
+
+    def flush(self, calib42, ctx=None):
+        """The end of interpolate_by_track's loop: the keyframe-1 rows track_records kept are the final keyframe, then
+        the live tracks with max_score >= sigma_h and >= t_min entries are finished."""
+        ego = None if self.pending_ego is None else ops.kf_ego_rows([self.pending_ego])[0]
+        ops.vt_flush(ctx or self.ctx, self.d_state, ego, calib42, self.params)
+        self.pending_ego = None
+
+    def track_keyframes(self, d_rows, d_counts, n_keyframes, max_rows, ego, calib42, ctx=None, box_f64=None,
+                        score_f64=None):
+        """n_keyframes encoded lists, continuing the sequence: d_rows (n, max_rows, 16) float32 or float64 (boxes2d 4:8,
+        boxes3d 8:15, score 15), d_counts (n,); ego[k]: (trans, matrix, delta) from the keyframe before k to k, or
+        None.  box_f64 / score_f64: the dtype the host holds boxes3d / the scores in (None: the rows')."""
+        ops.vt_track_keyframes(ctx or self.ctx, self.d_state, d_rows, d_counts, n_keyframes, max_rows,
+                               ops.kf_ego_rows(ego), calib42, self.params, box_f64, score_f64)
+
+    def track_records(self, d_records, d_counts, n_pairs, max_det, p2, image_wh, ego, calib42, score_threshold=0.1,
+                      ctx=None):
+        """Encode n_pairs record pairs (n_pairs, 2, max_det, 17) and track them: pair j's keyframe-0 rows are the next
+        keyframe of the sequence, the last pair's keyframe-1 rows wait for flush().  ego[j]: pair j's own motion
+        (trans, matrix, delta) from its keyframe 0 to its keyframe 1, or None -- the association of the keyframe
+        AFTER it."""
+        ego = list(ego)
+        if len(ego) != int(n_pairs):
+            raise ValueError('track_records: one ego entry per pair')
+        if n_pairs == 0:
+            return
+        into = [self.pending_ego] + ego[:-1]
+        ops.vt_track_pairs(ctx or self.ctx, self.d_state, d_records, d_counts, n_pairs, max_det, p2, image_wh,
+                           score_threshold, ops.kf_ego_rows(into), calib42, self.params)
+        self.pending_ego = ego[-1]
+
+    def header(self):
+        h = self.d_state.offset(0, (len(_KF_HDR),), np.int32).download()
+        return dict(zip(_KF_HDR, (int(v) for v in h)))
+
+    def used_bytes(self):
+        """The state's bytes that mean something (header, live tracks, kept rows, finished tracks, log), downloaded:
+        what two equal histories leave equal."""
+        h = self.header()
+        n_k1 = max(h['n_k1'], 0)
+        parts = [(0, _HDR_BYTES), (_VT_LIVE_OFF, h['n_live'] * VT_TRACK.itemsize), (_VT_K1_OFF, n_k1 * K1_COLS * 4),
+                 (_VT_FIN_OFF, min(h['n_fin'], self.cap) * VT_TRACK.itemsize),
+                 (_VT_FIN_OFF + self.cap * VT_TRACK.itemsize, min(h['n_log'], self.cap) * VT_LOG.itemsize)]
+        return [self.d_state.offset(off, (n,), np.uint8).download() for off, n in parts if n > 0]
+
+    def read(self):
+        """Download (synchronous on the state's context): (finished tracks, VT_TRACK records in finishing order; the log,
+        VT_LOG records in writing order).  Raises RuntimeError if a limit was exceeded or an IoU was not finite."""
+        h = self.header()
+        if h['status'] & VT_STATUS_LIVE:
+            raise RuntimeError('velocity tracker: more than %d live tracks' % KF_MAX_LIVE)
+        if h['status'] & VT_STATUS_LOG:
+            raise RuntimeError('velocity tracker: log capacity %d exceeded (%d log entries, %d finished tracks needed)'
+                               % (self.cap, h['n_log'], h['n_fin']))
+        if h['status'] & VT_STATUS_IOU:
+            raise RuntimeError('velocity tracker: an IoU that is not finite (NaN boxes)')
+        n_fin, n_log = h['n_fin'], h['n_log']
+        fin = self.d_state.offset(_VT_FIN_OFF, (max(n_fin, 1) * VT_TRACK.itemsize,), np.uint8).download()
+        log = self.d_state.offset(_VT_FIN_OFF + self.cap * VT_TRACK.itemsize, (max(n_log, 1) * VT_LOG.itemsize,),
+                                  np.uint8).download()
+        return fin.view(VT_TRACK)[:n_fin], log.view(VT_LOG)[:n_log]
+
+
+def vt_log_det(entry, stride, dtype=np.float32, classes=None):
+    """A log entry's detection (det: boxes3d, boxes2d, score, class index) as the host's dict; classes: the names
+    'info' is filled from (None: no 'info')."""
+    d = entry['det']
+    det = {'frame_id': int(entry['keyframe']) * stride, 'boxes2d': np.array(d[7:11], dtype),
+           'boxes3d': np.array(d[0:7], dtype), 'score': dtype(d[11])}
+    if classes is not None:
+        det['info'] = np.array([classes[int(d[12])], '-1', '-1', '-10.0'])
+    return det
+
+
+def vt_tracks_from_log(fin, log, stride, extend_len, frame_num, real_det=None, dtype=np.float32, classes=None):
+    """VelocityTracker.read() -> interpolate_by_track's result: track dicts 'dets', 'direction', 'max_score', 'speed',
+    'extend_len'.  dets is rebuilt from the track's log entries with the host module's own functions: a real entry is
+    real_det(keyframe, row) (default: vt_log_det in `dtype`, 'info' from `classes`), joined by interpolate_det (the frames in between); a
+    predicted one a copy of the entry before it, one frame on, at the logged x, z, ry; a finished record whose
+    predictions were cut loses its last extend_len entries.  max_score, speed and extend_len are the device's.  Then
+    the two end extensions (extend_track_start, extend_track_end under frame_num)."""
+    import copy
+
+    from dodt_amd.experiments import video_detection_iou as host
+    order = np.argsort(log['id'], kind='stable')
+    ids = log['id'][order]
+    out = []
+    for f in fin:
+        trk = {'dets': [], 'direction': [], 'max_score': None, 'speed': [0.0, 0.0, 0.0], 'extend_len': 0}
+        lo, hi = np.searchsorted(ids, f['id'], 'left'), np.searchsorted(ids, f['id'], 'right')
+        for e in log[order[lo:hi]]:
+            if e['kind'] == 0:
+                det = (vt_log_det(e, stride, dtype, classes) if real_det is None
+                       else real_det(int(e['keyframe']), int(e['row'])))
+                if trk['dets']:
+                    host.interpolate_det(trk, det)
+                else:
+                    trk['direction'] = [1 if det['boxes3d'][-1] > 0 else -1]
+                trk['max_score'] = np.asarray(det['score']).dtype.type(f['max_score'])
+                trk['dets'].append(det)
+            else:
+                if not trk['dets']:
+                    raise RuntimeError('velocity tracker: track %d starts with a predicted entry' % int(f['id']))
+                det = copy.deepcopy(trk['dets'][-1])
+                det['frame_id'] += 1
+                det['boxes3d'][_XZR] = e['det'][_XZR]
+                trk['dets'].append(det)
+        if f['flags'] & VT_CUT:
+            trk['dets'] = trk['dets'][:-int(extend_len)]
+        if len(trk['dets']) != int(f['n_dets']):
+            raise RuntimeError('velocity tracker: track %d has %d entries in the log, %d on the device'
+                               % (int(f['id']), len(trk['dets']), int(f['n_dets'])))
+        if f['flags'] & VT_HAS_SPEED:
+            trk['speed'] = np.array(f['speed'], trk['dets'][-1]['boxes3d'].dtype)
+        trk['extend_len'] = int(f['extend_len'])
+        out.append(trk)
+    out = host.extend_track_start(out, stride)
+    return host.extend_track_end(out, stride, frame_num)
+
+
+def _vt_check_detections(detections, stride):
+    """What interpolate_by_track refuses before anything reaches the device -> (rows (n, max_rows, 16), counts (n,),
+    box_f64, score_f64): the dtypes the host computes in -- boxes3d arithmetic in float32 if every boxes3d is, score
+    comparisons in float32 if every score is --; the rows are float32 if both are, else float64 (which holds float32
+    values exactly)."""
+    n = len(detections)
+    max_rows = max([1] + [len(f) for f in detections])
+    if max_rows > MAX_ROWS:
+        raise ValueError('at most %d detections per keyframe' % MAX_ROWS)
+    dets = [d for f in detections for d in f]
+    box_f64 = not all(np.asarray(d['boxes3d']).dtype == np.float32 for d in dets)
+    score_f64 = not all(np.asarray(d['score']).dtype == np.float32 for d in dets)
+    rows = np.zeros((n, max_rows, K1_COLS), np.float64 if box_f64 or score_f64 else np.float32)
+    counts = np.zeros((n,), np.int32)
+    for k, frame in enumerate(detections):
+        for i, det in enumerate(frame):
+            if int(det['frame_id']) != k * stride:
+                raise ValueError('interpolate_by_track: detection %d of keyframe %d has frame_id %r, not %d'
+                                 % (i, k, det['frame_id'], k * stride))
+            rows[k, i, 4:8] = np.asarray(det['boxes2d']).reshape(4)
+            rows[k, i, 8:15] = np.asarray(det['boxes3d']).reshape(7)
+            rows[k, i, 15] = det['score']
+        counts[k] = len(frame)
+    return rows, counts, box_f64, score_f64
+
+
+def interpolate_by_track(ego, calib, detections, stride, frame_num, sigma_l, sigma_h, sigma_iou, t_min, extend_len,
+                         ctx=None):
+    """video_detection_iou.interpolate_by_track on the device (dodt_vt_track_keyframes): the host function's arguments,
+    the same list of track dicts whose real entries are the caller's detection dicts.  ego(k * stride - stride,
+    k * stride) is called once per keyframe k >= 1.  A detection whose frame_id is not its keyframe's k * stride, more
+    than 128 detections in a keyframe, extend_len and stride outside 1..4096 are ValueErrors.  The device computes speed
+    and predictions in float32 if every boxes3d array is float32, else in float64, and compares scores in float32 if
+    every score is float32, else in float64 -- as the host does on those arrays."""
+    _vt_check_params(stride, extend_len)
+    rows, counts, box_f64, score_f64 = _vt_check_detections(detections, stride)
+    n = len(detections)
+    if n == 0:
+        return []
+    ctx = ctx or device.default_context()
+    egos = [None] + [ego(k * stride - stride, k * stride) for k in range(1, n)]
+    calib42 = ops.temporal_calib(calib[0], calib[1])
+    per_kf = min(int(stride), int(extend_len)) + 1
+    cap = max(1, min(n * (KF_MAX_LIVE * per_kf + MAX_ROWS), int(counts.sum()) * (int(extend_len) + 2)))
+    tr = VelocityTracker(ctx, sigma_l, sigma_h, sigma_iou, t_min, extend_len, stride, log_capacity=cap)
+    tr.track_keyframes(ctx.array(rows), ctx.array(counts), n, rows.shape[1], egos, calib42, box_f64=box_f64,
+                       score_f64=score_f64)
+    tr.flush(calib42)
+    fin, log = tr.read()
+    return vt_tracks_from_log(fin, log, stride, extend_len, frame_num, real_det=lambda k, i: detections[k][i])
 
 
 def _label_item(frame_id, row, classes, offsets=None):

@@ -879,6 +879,53 @@ int dodt_kf_assign(dodt_ctx* ctx, const float* d_iou, int n_tracks, int n_dets, 
 int dodt_kf_iou_matrix(dodt_ctx* ctx, const double* d_last, int n_tracks, const double* d_dets, int n_dets,
                        const double* ego, const double* calib, float* d_iou_out);
 
+/* ---- the velocity-extrapolating greedy IoU tracker on the device (velocity_track.hip) -----------
+ * interpolate_by_track of dodt_amd/experiments/video_detection_iou.py: greedy association in track order
+ * (each live track takes the first maximum of its IoUs with the detections still free and matches it if
+ * that is > sigma_iou), a track without a match extrapolated by its last displacement for up to extend_len
+ * frames, then cut and finished if max_score >= sigma_h and it has >= t_min entries.  The state, the ego
+ * rows (13 doubles per keyframe: the motion from the keyframe before it) and the calibration (42 doubles)
+ * are those of dodt_kf_*; keyframe k is frame k * stride.  The IoU is float64 under this tracker's
+ * permutation (the track's box enters with l and h swapped); speed and prediction are computed in the
+ * dtype the host holds boxes3d in (float32 sums rounded to float32), scores are compared in the scores' dtype.  The log holds a
+ * track's real entries (keyframe, row) and predicted entries (box); the frames between two matched
+ * keyframes and the extensions at both ends are rebuilt from it on the host.  Limits: 128 detections per
+ * keyframe, 256 live tracks at the start of a keyframe, log_capacity log entries and finished tracks, 1 <=
+ * stride, extend_len <= 4096; running past one sets a status bit and writes nothing out of bounds, as does
+ * an IoU that is not finite.
+ *
+ * Bytes of a state buffer with room for log_capacity (>= 1) log entries and finished tracks. */
+int dodt_vt_state_bytes(int log_capacity, size_t* bytes);
+/* Start a sequence: empty state, ids from 0, keyframe 0. */
+int dodt_vt_reset(dodt_ctx* ctx, void* d_state, int log_capacity);
+/* n_keyframes lists already encoded: d_rows (n_keyframes, max_rows, 16) float32 or float64 (rows_f64) in
+ * the KITTI row layout (boxes2d in cols 4..7, boxes3d [h,w,l,x,y,z,ry] in 8..14, score in 15), d_counts
+ * (n_keyframes,) rows per list; max_rows <= 128.  box_f64 / score_f64: the host holds boxes3d / the scores as
+ * float64 (only with rows_f64): the dtype of the speed and prediction arithmetic / of the score comparisons;
+ * the state remembers score_f64 for the finish test of dodt_vt_flush. */
+int dodt_vt_track_keyframes(dodt_ctx* ctx, void* d_state, const void* d_rows, int rows_f64,
+                            const int32_t* d_counts, int n_keyframes, int max_rows, const double* ego,
+                            const double* calib, double sigma_l, double sigma_h, double sigma_iou, int t_min,
+                            int extend_len, int stride, int box_f64, int score_f64);
+/* n_pairs record pairs (dodt_track_pairs' arguments): pair j's keyframe-0 rows, encoded (float32), are
+ * keyframe j of the batch; the last pair's keyframe-1 rows are kept in the state for dodt_vt_flush (a
+ * later batch replaces them).  ego[j]: the motion into pair j's keyframe 0. */
+int dodt_vt_track_pairs(dodt_ctx* ctx, void* d_state, const void* d_records, int records_f64,
+                        const int32_t* d_counts, int n_pairs, int max_det, const double* p2, double image_w,
+                        double image_h, double score_threshold, const double* ego, const double* calib,
+                        double sigma_l, double sigma_h, double sigma_iou, int t_min, int extend_len,
+                        int stride);
+/* The end of the sequence: the kept keyframe-1 rows, if any, are the final keyframe (ego: the motion
+ * into it, NULL: none); then every live track with max_score >= sigma_h and >= t_min entries is finished,
+ * in order, its predictions not cut, and the live list is emptied. */
+int dodt_vt_flush(dodt_ctx* ctx, void* d_state, const double* ego, const double* calib, double sigma_l,
+                  double sigma_h, double sigma_iou, int t_min, int extend_len, int stride);
+/* The association's IoU alone (a test entry): d_iou_out (n_tracks, n_dets) float64 = this tracker's
+ * cal_transformed_ious of boxes d_last (n_tracks, 7) and d_dets (n_dets, 7), [h,w,l,x,y,z,ry] float64,
+ * under one ego row (NULL: none). */
+int dodt_vt_iou_matrix(dodt_ctx* ctx, const double* d_last, int n_tracks, const double* d_dets, int n_dets,
+                       const double* ego, const double* calib, double* d_iou_out);
+
 /* ---- (e) multi-GPU: the one exchange step of the path, RCCL over xGMI, no PyTorch -----------
  * The reference runs on ONE device (avod/experiments/run_tracking_inference.py:109-128 sets a
  * single CUDA_VISIBLE_DEVICES and walks the sequences in a loop), so there is no reference
