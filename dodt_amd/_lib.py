@@ -240,6 +240,9 @@ SIGNATURES = {
     'dodt_kf_track_pairs': (_i, [_vp, _vp, _vp, _i, _pi32, _i, _i, C.POINTER(_d), _d, _d, _d, C.POINTER(_d),
                                  C.POINTER(_d), _d, _d, _i, _i, _d, _d]),
     'dodt_kf_flush': (_i, [_vp, _vp, C.POINTER(_d), C.POINTER(_d), _d, _d, _i, _i, _d, _d]),
+    'dodt_kf_lanes_stride': (_i, [_i, C.POINTER(C.c_size_t)]),
+    'dodt_kf_track_lanes': (_i, [_vp, _vp, C.c_size_t, _i, C.POINTER(C.c_ubyte), _vp, _i, _pi32, _i, C.POINTER(_d),
+                                 C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), _d, _d, _d, _i, _i, _d, _d]),
     'dodt_kf_filter_steps': (_i, [_vp, _vp, _pi32, _vp, _pi32, _vp, _i, _i, _vp, _vp]),
     'dodt_kf_assign': (_i, [_vp, _pf, _i, _i, _d, _pi32, _pi32, _pi32, _pi32]),
     'dodt_kf_iou_matrix': (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(_d), C.POINTER(_d), _pf]),
@@ -250,6 +253,9 @@ SIGNATURES = {
     'dodt_vt_track_pairs': (_i, [_vp, _vp, _vp, _i, _pi32, _i, _i, C.POINTER(_d), _d, _d, _d, C.POINTER(_d),
                                  C.POINTER(_d), _d, _d, _d, _i, _i, _i]),
     'dodt_vt_flush': (_i, [_vp, _vp, C.POINTER(_d), C.POINTER(_d), _d, _d, _d, _i, _i, _i]),
+    'dodt_vt_lanes_stride': (_i, [_i, C.POINTER(C.c_size_t)]),
+    'dodt_vt_track_lanes': (_i, [_vp, _vp, C.c_size_t, _i, C.POINTER(C.c_ubyte), _vp, _i, _pi32, _i, C.POINTER(_d),
+                                 C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), _d, _d, _d, _d, _i, _i, _i]),
     'dodt_vt_iou_matrix': (_i, [_vp, _vp, _i, _vp, _i, C.POINTER(_d), C.POINTER(_d), _vp]),
 }
 COMM_ID_BYTES = 128

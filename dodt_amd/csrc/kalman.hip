@@ -13,6 +13,11 @@
 //   kf_step_kernel  one workgroup: per keyframe the score filter, the optimal assignment (wave 0, shortest augmenting
 //                   paths), the gate, the filter one lane per track, `inside`, and the compaction of live / finished /
 //                   log by the workgroup prefix scan.
+// Lanes (dodt_kf_track_lanes): pair i of a step belongs to lane i, each lane with a state, an ego row, a calibration
+// and an image size of its own -- the same three launches over a chunk of kLaneChunk lanes: the shared lanes encode
+// (track_encode.h), kf_iou_lanes_kernel (grid.y = lane, lane i's matrix in slice i of the workspace) and
+// kf_step_lanes_kernel (one workgroup per lane: the step's one body with n_kf = 1 on the lane's own state).  No
+// workgroup waits for another; an inactive lane's workgroups return before they read or write anything.
 // The ego rows and the calibration travel by value in the kernel arguments.  The filter and the IoU are float64;
 // P stays block diagonal (F, Q, H, R are, and P0 = L I), so four 2x2 blocks and a diagonal S are the whole arithmetic.
 // Builds with -ffp-contract=off.
@@ -29,6 +34,8 @@ namespace {
 constexpr int kMaxLive = 256;                 // live tracks at the start of a keyframe (rows of the IoU matrix)
 constexpr int kLiveSlots = kMaxLive + kRows;  // ... plus the new tracks of one keyframe, before the drop
 constexpr int kChunk = 16;                    // keyframes per launch triple
+constexpr int kLaneChunk = 8;                 // lanes per launch triple (their constants fill the kernel arguments)
+static_assert(kLaneChunk <= kChunk, "a chunk of lanes encodes into the workspace sized for kChunk pairs");
 constexpr int kDet = 12;                      // a detection as doubles: boxes3d [h,w,l,x,y,z,ry], boxes2d (4), score
 constexpr int kStatusLog = 1, kStatusLive = 2, kStatusSolver = 4;
 static_assert(kMaxLive == kThreads, "one lane per live track");
@@ -95,6 +102,24 @@ struct KfParams {
     double sigma_l, iou_thr, L, R;
     int max_age, min_hits;
 };
+// The per-lane constants of a chunk of lanes, by value in the kernel arguments like KfEgo and KfCalib: read before the
+// call returns, no upload, no lifetime.  440 bytes per lane; a launch's arguments are limited to 4 KB.
+struct KfLane {
+    double ego[13];         // the motion into the lane's current keyframe
+    KfCalib cal;
+};
+struct KfLaneTable {
+    KfLane a[kLaneChunk];
+};
+static_assert(sizeof(KfLane) == 440 && sizeof(KfLaneTable) + sizeof(KfRows) + sizeof(KfParams) + 64 <= 4096,
+              "the step kernel's arguments: the lanes' table, the rows, the parameters and six words of pointers");
+// lane i's keyframe as a batch of its own: the rows from list i on
+__device__ KfRows kf_lane_rows(const KfRows& r, int i) {
+    KfRows o = r;
+    o.base = static_cast<const char*>(r.base) + (size_t)i * r.kf_stride * (r.f64 ? sizeof(double) : sizeof(float));
+    o.cnt = r.cnt + (size_t)i * r.cnt_stride;
+    return o;
+}
 
 // cal_transformed_ious: `det` [h,w,l,x,y,z,ry] moved into the frame of `last` (ego_moved_box, ego_transform.h), then
 // iou_3d under the host's permutation to [x,y,z,l,w,h,ry]
@@ -327,23 +352,43 @@ __device__ __forceinline__ void kf_matrix(const KfRows& rows, int k, const KfTra
     }
 }
 
-// M (kMaxLive x kRows float32) of keyframe `k` of the batch, over the whole chip
-__global__ void __launch_bounds__(kThreads)
-kf_iou_kernel(KfRows rows, int k, const void* state, KfEgo ego, KfCalib cal, float* __restrict__ M) {
+// workgroup blockIdx.x's share of M (kMaxLive x kRows float32) of keyframe `k` of `rows` against the live tracks of `state`
+__device__ __forceinline__ void kf_iou_state(const KfRows& rows, int k, const void* state, const double* ego,
+                                             const KfCalib& cal, float* __restrict__ M) {
     const char* b = static_cast<const char*>(state);
     const KfHeader* h = reinterpret_cast<const KfHeader*>(b);
     const int nt = min(max(h->n_live, 0), kMaxLive);
-    kf_matrix(rows, k, reinterpret_cast<const KfTrack*>(b + kLiveOff), nt, ego.e[k], cal, M,
+    kf_matrix(rows, k, reinterpret_cast<const KfTrack*>(b + kLiveOff), nt, ego, cal, M,
               blockIdx.x * kThreads + threadIdx.x, gridDim.x * kThreads);
 }
 
-// One workgroup: keyframes 0..n_kf-1 of `rows` in order on `state`.  M holds keyframe 0's matrix (kf_iou_kernel); the
+// M of keyframe `k` of the batch, over the whole chip
+__global__ void __launch_bounds__(kThreads)
+kf_iou_kernel(KfRows rows, int k, const void* state, KfEgo ego, KfCalib cal, float* __restrict__ M) {
+    kf_iou_state(rows, k, state, ego.e[k], cal, M);
+}
+
+// Lanes: grid (kMaxLive * kRows / kThreads, lanes); lane blockIdx.y's keyframe against its OWN state under its own ego
+// row and calibration, its matrix in slice blockIdx.y of M.
+__global__ void __launch_bounds__(kThreads)
+kf_iou_lanes_kernel(KfRows rows, unsigned mask, const char* __restrict__ states, size_t stride, KfLaneTable tab,
+                    float* __restrict__ M) {
+    const int i = blockIdx.y;
+    if (!lane_on(mask, i)) return;
+    kf_iou_state(kf_lane_rows(rows, i), 0, states + (size_t)i * stride, tab.a[i].ego, tab.a[i].cal,
+                 M + (size_t)i * kMaxLive * kRows);
+}
+
+// One workgroup: keyframes 0..n_kf-1 of `rows` in order on `state`, keyframe k under the ego row ego + 13 k.  The one
+// body of kf_step_kernel (a batch of one sequence) and kf_step_lanes_kernel (per workgroup a lane's view: one keyframe,
+// its state).  M holds keyframe 0's matrix (kf_iou_kernel); the
 // later ones are computed here.  k1 (or NULL): the keyframe-1 rows (kRows x 16 float32) and their count to keep in the
 // state behind the batch.  kept: the batch is the state's own kept list (rows.base / rows.cnt point into it) -- skipped
 // if none is kept, forgotten afterwards.  finish: then every live track with hits >= min_hits is finished, in order.
-__global__ void __launch_bounds__(kThreads)
-kf_step_kernel(KfRows rows, int n_kf, void* state, float* __restrict__ M, KfEgo ego, KfCalib cal, KfParams prm,
-               const float* __restrict__ k1, const int32_t* __restrict__ k1_cnt, int kept, int finish) {
+__device__ __forceinline__ void kf_step_keyframes(const KfRows& rows, int n_kf, void* state, float* __restrict__ M,
+                                                  const double* ego, const KfCalib& cal, const KfParams& prm,
+                                                  const float* __restrict__ k1, const int32_t* __restrict__ k1_cnt,
+                                                  int kept, int finish) {
     __shared__ Solver sol;
     __shared__ KfHeader h;
     __shared__ int fdet[kRows], det2trk[kRows], newdet[kRows], trk2det[kMaxLive], wave_tot[kThreads / 64];
@@ -362,7 +407,7 @@ kf_step_kernel(KfRows rows, int n_kf, void* state, float* __restrict__ M, KfEgo 
         int nd;
         const int dpos = block_scan(keep_d, wave_tot, &nd);
         if (keep_d) fdet[dpos] = t;
-        if (k > 0) kf_matrix(rows, k, st.live, nt, ego.e[k], cal, M, t, kThreads);
+        if (k > 0) kf_matrix(rows, k, st.live, nt, ego + 13 * k, cal, M, t, kThreads);
         __syncthreads();
         // ---- assignment (wave 0) and gate -----------------------------------------------------------------------------
         if (nt > 0 && nd > 0) {
@@ -502,6 +547,23 @@ kf_step_kernel(KfRows rows, int n_kf, void* state, float* __restrict__ M, KfEgo 
     }
     __syncthreads();
     if (t == 0) *st.hdr = h;
+}
+
+__global__ void __launch_bounds__(kThreads)
+kf_step_kernel(KfRows rows, int n_kf, void* state, float* __restrict__ M, KfEgo ego, KfCalib cal, KfParams prm,
+               const float* __restrict__ k1, const int32_t* __restrict__ k1_cnt, int kept, int finish) {
+    kf_step_keyframes(rows, n_kf, state, M, ego.e[0], cal, prm, k1, k1_cnt, kept, finish);
+}
+
+// Lanes: grid = lanes, one workgroup per lane; an inactive lane's workgroup leaves at once (the mask is uniform).  Lane
+// i keeps ITS keyframe-1 rows (list i of k1, count cnt[i * kCnt + 1]) in its state.
+__global__ void __launch_bounds__(kThreads)
+kf_step_lanes_kernel(KfRows rows, unsigned mask, char* states, size_t stride, float* __restrict__ M, KfLaneTable tab,
+                     KfParams prm, const float* __restrict__ k1, const int32_t* __restrict__ cnt) {
+    const int i = blockIdx.x;
+    if (!lane_on(mask, i)) return;
+    kf_step_keyframes(kf_lane_rows(rows, i), 1, states + (size_t)i * stride, M + (size_t)i * kMaxLive * kRows,
+                      tab.a[i].ego, tab.a[i].cal, prm, k1 + (size_t)i * kRows * kK1, cnt + (size_t)i * kCnt + 1, 0, 0);
 }
 
 __global__ void kf_reset_kernel(void* state, int cap) {
@@ -693,6 +755,69 @@ extern "C" int dodt_kf_track_pairs(dodt_ctx* ctx, void* d_state, const void* d_r
         const int rc = kf_walk(ctx, d_state, rows, n, ego + (size_t)p0 * 13, calib, prm,
                                k1 + (size_t)last * kRows * kK1, cnt + (size_t)last * kCnt + 1, 0, 0);
         if (rc != DODT_OK) return rc;
+    }
+    return DODT_OK;
+}
+
+extern "C" int dodt_kf_lanes_stride(int log_capacity, size_t* stride) {
+    DODT_REQUIRE(log_capacity >= 1 && stride, "dodt_kf_lanes_stride: bad arguments");
+    *stride = (kf_state_bytes(log_capacity) + 255) / 256 * 256;
+    return DODT_OK;
+}
+
+extern "C" int dodt_kf_track_lanes(dodt_ctx* ctx, void* d_states, size_t stride, int n_lanes,
+                                   const unsigned char* active, const void* d_records, int records_f64,
+                                   const int32_t* d_counts, int max_det, const double* p2s, const double* image_whs,
+                                   const double* egos, const double* calibs, double score_threshold, double sigma_l,
+                                   double iou_threshold, int max_age, int min_hits, double L, double R_scaler) {
+    DODT_REQUIRE(ctx && d_states && n_lanes >= 0, "dodt_kf_track_lanes: bad arguments");
+    if (n_lanes == 0) return DODT_OK;
+    DODT_REQUIRE(d_records && d_counts && p2s && image_whs && egos && calibs, "dodt_kf_track_lanes: NULL argument");
+    DODT_REQUIRE(max_det >= 1 && max_det <= kRows, "dodt_kf_track_lanes: max_det %d outside 1..%d", max_det, kRows);
+    DODT_REQUIRE(stride >= kf_state_bytes(1) && stride % alignof(KfTrack) == 0,
+                 "dodt_kf_track_lanes: stride %zu is no distance between two states", stride);
+    const size_t enc_bytes = (size_t)kChunk * kRows * (kTrk + kK1) * sizeof(float) + kChunk * kCnt * sizeof(int32_t);
+    if (ctx->tracking_enc.reserve(enc_bytes) != DODT_OK) return DODT_ERR_HIP;
+    if (ctx->tracking_ws.reserve((size_t)kLaneChunk * kMaxLive * kRows * sizeof(float)) != DODT_OK) return DODT_ERR_HIP;
+    float* trk = static_cast<float*>(ctx->tracking_enc.ptr);
+    float* k1 = trk + (size_t)kChunk * kRows * kTrk;
+    int32_t* cnt = reinterpret_cast<int32_t*>(k1 + (size_t)kChunk * kRows * kK1);
+    float* M = static_cast<float*>(ctx->tracking_ws.ptr);
+    const KfParams prm = kf_params(sigma_l, iou_threshold, max_age, min_hits, L, R_scaler);
+    // lane i's keyframe: pair i's keyframe-0 rows (cols 0..15 of its track items, count in cnt[3])
+    const KfRows rows{trk, cnt + 3, 0, kTrk, kCnt, kRows, (size_t)kRows * kTrk};
+    const size_t rec_bytes = records_f64 ? sizeof(double) : sizeof(float);
+    for (int l0 = 0; l0 < n_lanes; l0 += kLaneChunk) {
+        const int n = n_lanes - l0 < kLaneChunk ? n_lanes - l0 : kLaneChunk;
+        LaneCals<kLaneChunk> enc{};
+        KfLaneTable tab{};
+        unsigned mask = 0;
+        for (int i = 0; i < n; ++i) {
+            memcpy(enc.c[i].P.p, p2s + (size_t)(l0 + i) * 12, sizeof(enc.c[i].P.p));
+            enc.c[i].iw = image_whs[2 * (l0 + i)];
+            enc.c[i].ih = image_whs[2 * (l0 + i) + 1];
+            memcpy(tab.a[i].ego, egos + (size_t)(l0 + i) * 13, sizeof(tab.a[i].ego));
+            memcpy(&tab.a[i].cal, calibs + (size_t)(l0 + i) * 42, sizeof(KfCalib));
+            if (!active || active[l0 + i]) mask |= 1u << i;
+        }
+        if (!mask) continue;
+        const char* rec = static_cast<const char*>(d_records) + (size_t)l0 * 2 * max_det * kRecCols * rec_bytes;
+        char* states = static_cast<char*>(d_states) + (size_t)l0 * stride;
+        if (records_f64)
+            hipLaunchKernelGGL((encode_lanes_kernel<double, kLaneChunk>), dim3(n), dim3(kThreads), 0, ctx->stream,
+                               reinterpret_cast<const double*>(rec), d_counts + 2 * l0, max_det, enc, mask,
+                               score_threshold, trk, k1, cnt);
+        else
+            hipLaunchKernelGGL((encode_lanes_kernel<float, kLaneChunk>), dim3(n), dim3(kThreads), 0, ctx->stream,
+                               reinterpret_cast<const float*>(rec), d_counts + 2 * l0, max_det, enc, mask,
+                               score_threshold, trk, k1, cnt);
+        DODT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(kf_iou_lanes_kernel, dim3(kMaxLive * kRows / kThreads, n), dim3(kThreads), 0, ctx->stream,
+                           rows, mask, static_cast<const char*>(states), stride, tab, M);
+        DODT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(kf_step_lanes_kernel, dim3(n), dim3(kThreads), 0, ctx->stream, rows, mask, states, stride, M,
+                           tab, prm, static_cast<const float*>(k1), static_cast<const int32_t*>(cnt));
+        DODT_LAUNCH_CHECK();
     }
     return DODT_OK;
 }

@@ -131,4 +131,27 @@ encode_kernel(const T* __restrict__ records, const int32_t* __restrict__ counts,
     encode_pair(records, counts, max_det, P, iw, ih, thr, trk, k1, cnt);
 }
 
+// Lanes: pair blockIdx.x belongs to lane blockIdx.x, each lane with a calibration and an image size of its own.  The
+// calibrations of a chunk of N lanes travel by value in the kernel arguments (N * 112 bytes): read before the call
+// returns like p2, no upload, no lifetime; the index is blockIdx.x, uniform over the workgroup.
+struct LaneCal {
+    P2 P;
+    double iw, ih;
+};
+template <int N>
+struct LaneCals {
+    LaneCal c[N];
+};
+__device__ bool lane_on(unsigned mask, int lane) { return (mask >> lane) & 1u; }
+
+template <typename T, int N>
+__global__ void __launch_bounds__(kThreads)
+encode_lanes_kernel(const T* __restrict__ records, const int32_t* __restrict__ counts, int max_det, LaneCals<N> tab,
+                    unsigned mask, double thr, float* __restrict__ trk, float* __restrict__ k1,
+                    int32_t* __restrict__ cnt) {
+    if (!lane_on(mask, blockIdx.x)) return;
+    const LaneCal& cal = tab.c[blockIdx.x];
+    encode_pair(records, counts, max_det, cal.P, cal.iw, cal.ih, thr, trk, k1, cnt);
+}
+
 }  // namespace

@@ -21,7 +21,7 @@
 // 3 decimals exactly as numpy rounds (rint(x * 1000) / 1000 in float64).  Builds with -ffp-contract=off.
 #include "common.h"
 #include "iou3d.h"
-#include "track_encode.h"         // kitti_row, encode_pair, encode_kernel, block_scan (shared with kalman.hip)
+#include "track_encode.h"         // kitti_row, encode_pair, encode_kernel, encode_lanes_kernel, block_scan (shared)
 
 #include <cfloat>
 #include <climits>
@@ -87,26 +87,9 @@ struct Lists {              // encoded pairs: trk (n, rows, 23), k1 (n, rows, 16
     int cnt_stride, rows;
 };
 
-// The calibrations of a chunk of lanes, by value in the kernel arguments (kChunk * 112 = 1792 bytes): read before the
-// call returns like p2, no upload, no lifetime; the index is blockIdx.x, uniform over the workgroup.
-struct LaneCal {
-    P2 P;
-    double iw, ih;
-};
-struct LaneTable {
-    LaneCal c[kChunk];
-};
-__device__ bool lane_on(unsigned mask, int lane) { return (mask >> lane) & 1u; }
-
-template <typename T>
-__global__ void __launch_bounds__(kThreads)
-encode_lanes_kernel(const T* __restrict__ records, const int32_t* __restrict__ counts, int max_det, LaneTable tab,
-                    unsigned mask, double thr, float* __restrict__ trk, float* __restrict__ k1,
-                    int32_t* __restrict__ cnt) {
-    if (!lane_on(mask, blockIdx.x)) return;
-    const LaneCal& cal = tab.c[blockIdx.x];
-    encode_pair(records, counts, max_det, cal.P, cal.iw, cal.ih, thr, trk, k1, cnt);
-}
+// The calibrations of a chunk of lanes, by value in the kernel arguments (kChunk * 112 = 1792 bytes; LaneCals,
+// encode_lanes_kernel and lane_on of track_encode.h, shared with the other two trackers' lanes).
+using LaneTable = LaneCals<kChunk>;
 
 __device__ bool skipped(const Lists& ls, int p) { return ls.cnt_stride > 2 && ls.cnt[(size_t)p * ls.cnt_stride + 2]; }
 __device__ int n_trk(const Lists& ls, int p) { return min(max(ls.cnt[(size_t)p * ls.cnt_stride], 0), ls.rows); }
@@ -670,11 +653,11 @@ extern "C" int dodt_track_lanes(dodt_ctx* ctx, void* d_states, size_t stride, in
         const char* rec = static_cast<const char*>(d_records) + (size_t)l0 * 2 * max_det * kRecCols * rec_bytes;
         char* states = static_cast<char*>(d_states) + (size_t)l0 * stride;
         if (records_f64)
-            hipLaunchKernelGGL(encode_lanes_kernel<double>, dim3(n), dim3(kThreads), 0, ctx->stream,
+            hipLaunchKernelGGL((encode_lanes_kernel<double, kChunk>), dim3(n), dim3(kThreads), 0, ctx->stream,
                                reinterpret_cast<const double*>(rec), d_counts + 2 * l0, max_det, tab, mask,
                                score_threshold, trk, k1, cnt);
         else
-            hipLaunchKernelGGL(encode_lanes_kernel<float>, dim3(n), dim3(kThreads), 0, ctx->stream,
+            hipLaunchKernelGGL((encode_lanes_kernel<float, kChunk>), dim3(n), dim3(kThreads), 0, ctx->stream,
                                reinterpret_cast<const float*>(rec), d_counts + 2 * l0, max_det, tab, mask,
                                score_threshold, trk, k1, cnt);
         DODT_LAUNCH_CHECK();

@@ -20,6 +20,11 @@
 // float32 before it goes into the state's double slots, and a score is compared with a threshold rounded to the scores'
 // dtype (as NumPy compares a float32 with a Python float).  The header keeps the scores' dtype for the finish test of a
 // flush.  The IoU is float64 either way.  Builds with -ffp-contract=off.
+// Lanes (dodt_vt_track_lanes): pair i of a step belongs to lane i, each lane with a state, an ego row, a calibration
+// and an image size of its own -- the same three launches over a chunk of kLaneChunk lanes: the shared lanes encode
+// (track_encode.h), vt_iou_lanes_kernel (grid.y = lane, lane i's matrix in slice i of the workspace) and
+// vt_step_lanes_kernel (one workgroup per lane: the step's one body with n_kf = 1 on the lane's own state).  An
+// inactive lane's workgroups return before they read or write anything.
 // Every loop is bounded by the list sizes, by `stride` or by `extend_len`; nothing waits on another workgroup.
 #include "common.h"
 #include "ego_transform.h"
@@ -34,6 +39,8 @@ namespace {
 constexpr int kMaxLive = 256;                 // live tracks at the start of a keyframe (rows of the IoU matrix)
 constexpr int kLiveSlots = kMaxLive + kRows;  // ... plus the new tracks of one keyframe, before the clamp
 constexpr int kChunk = 16;                    // keyframes per launch triple
+constexpr int kLaneChunk = 8;                 // lanes per launch triple (their constants fill the kernel arguments)
+static_assert(kLaneChunk <= kChunk, "a chunk of lanes encodes into the workspace sized for kChunk pairs");
 constexpr int kDet = 13;                      // a detection as doubles: boxes3d [h,w,l,x,y,z,ry], boxes2d (4), score,
                                               // class (col 0 of the row)
 constexpr int kMaxStep = 4096;                // stride and extend_len: the bound of the prediction loop
@@ -106,6 +113,24 @@ struct VtParams {
     int t_min, extend_len, stride;
     int box_f64, score_f64;     // the dtype the host holds boxes3d / scores in: arithmetic and comparisons follow it
 };
+// The per-lane constants of a chunk of lanes, by value in the kernel arguments like VtEgo and KfCalib: read before the
+// call returns, no upload, no lifetime.  440 bytes per lane; a launch's arguments are limited to 4 KB.
+struct VtLane {
+    double ego[13];         // the motion into the lane's current keyframe
+    KfCalib cal;
+};
+struct VtLaneTable {
+    VtLane a[kLaneChunk];
+};
+static_assert(sizeof(VtLane) == 440 && sizeof(VtLaneTable) + sizeof(VtRows) + sizeof(VtParams) + 64 <= 4096,
+              "the step kernel's arguments: the lanes' table, the rows, the parameters and six words of pointers");
+// lane i's keyframe as a batch of its own: the rows from list i on
+__device__ VtRows vt_lane_rows(const VtRows& r, int i) {
+    VtRows o = r;
+    o.base = static_cast<const char*>(r.base) + (size_t)i * r.kf_stride * (r.f64 ? sizeof(double) : sizeof(float));
+    o.cnt = r.cnt + (size_t)i * r.cnt_stride;
+    return o;
+}
 
 // ---- arithmetic in the rows' dtype ---------------------------------------------------------------------------------
 __device__ double vt_add(double a, double b, int f64) { return f64 ? a + b : (double)((float)a + (float)b); }
@@ -134,14 +159,31 @@ __device__ __forceinline__ void vt_matrix(const VtRows& rows, int k, const VtTra
     }
 }
 
-// M (kMaxLive x kRows float64) of keyframe `k` of the batch, over the whole chip
-__global__ void __launch_bounds__(kThreads)
-vt_iou_kernel(VtRows rows, int k, const void* state, VtEgo ego, KfCalib cal, double* __restrict__ M) {
+// workgroup blockIdx.x's share of M (kMaxLive x kRows float64) of keyframe `k` of `rows` against the live tracks of `state`
+__device__ __forceinline__ void vt_iou_state(const VtRows& rows, int k, const void* state, const double* ego,
+                                             const KfCalib& cal, double* __restrict__ M) {
     const char* b = static_cast<const char*>(state);
     const VtHeader* h = reinterpret_cast<const VtHeader*>(b);
     const int nt = min(max(h->n_live, 0), kMaxLive);
-    vt_matrix(rows, k, reinterpret_cast<const VtTrack*>(b + kLiveOff), nt, ego.e[k], cal, M,
+    vt_matrix(rows, k, reinterpret_cast<const VtTrack*>(b + kLiveOff), nt, ego, cal, M,
               blockIdx.x * kThreads + threadIdx.x, gridDim.x * kThreads);
+}
+
+// M of keyframe `k` of the batch, over the whole chip
+__global__ void __launch_bounds__(kThreads)
+vt_iou_kernel(VtRows rows, int k, const void* state, VtEgo ego, KfCalib cal, double* __restrict__ M) {
+    vt_iou_state(rows, k, state, ego.e[k], cal, M);
+}
+
+// Lanes: grid (kMaxLive * kRows / kThreads, lanes); lane blockIdx.y's keyframe against its OWN state under its own ego
+// row and calibration, its matrix in slice blockIdx.y of M.
+__global__ void __launch_bounds__(kThreads)
+vt_iou_lanes_kernel(VtRows rows, unsigned mask, const char* __restrict__ states, size_t stride, VtLaneTable tab,
+                    double* __restrict__ M) {
+    const int i = blockIdx.y;
+    if (!lane_on(mask, i)) return;
+    vt_iou_state(vt_lane_rows(rows, i), 0, states + (size_t)i * stride, tab.a[i].ego, tab.a[i].cal,
+                 M + (size_t)i * kMaxLive * kRows);
 }
 
 // (a, ja) comes before (b, jb): the larger IoU, on a tie the lower index (j < 0: no candidate)
@@ -205,14 +247,17 @@ __device__ void vt_log_entry(VtLog* e, int id, int keyframe, int kind, int row, 
     for (int c = 0; c < kDet; ++c) e->det[c] = det[c];
 }
 
-// One workgroup: keyframes 0..n_kf-1 of `rows` in order on `state`.  M holds keyframe 0's matrix (vt_iou_kernel); the
+// One workgroup: keyframes 0..n_kf-1 of `rows` in order on `state`, keyframe k under the ego row ego + 13 k.  The one
+// body of vt_step_kernel (a batch of one sequence) and vt_step_lanes_kernel (per workgroup a lane's view: one keyframe,
+// its state).  M holds keyframe 0's matrix (vt_iou_kernel); the
 // later ones are computed here.  k1 (or NULL): the keyframe-1 rows (kRows x 16 float32) and their count to keep in the
 // state behind the batch.  kept: the batch is the state's own kept list (rows.base / rows.cnt point into it) -- skipped
 // if none is kept, forgotten afterwards.  finish: then every live track with max_score >= sigma_h and >= t_min entries
 // is finished, in order, its predictions not cut.
-__global__ void __launch_bounds__(kThreads)
-vt_step_kernel(VtRows rows, int n_kf, void* state, double* __restrict__ M, VtEgo ego, KfCalib cal, VtParams prm,
-               const float* __restrict__ k1, const int32_t* __restrict__ k1_cnt, int kept, int finish) {
+__device__ __forceinline__ void vt_step_keyframes(const VtRows& rows, int n_kf, void* state, double* __restrict__ M,
+                                                  const double* ego, const KfCalib& cal, const VtParams& prm,
+                                                  const float* __restrict__ k1, const int32_t* __restrict__ k1_cnt,
+                                                  int kept, int finish) {
     __shared__ VtHeader h;
     __shared__ int fdet[kRows], det2trk[kRows], trk2det[kMaxLive], wave_tot[kThreads / 64], bad_iou;
     const int t = threadIdx.x, f64 = prm.box_f64, sf64 = prm.score_f64;
@@ -236,7 +281,7 @@ vt_step_kernel(VtRows rows, int n_kf, void* state, double* __restrict__ M, VtEgo
         const int dpos = block_scan(keep_d, wave_tot, &nd);
         if (keep_d) fdet[dpos] = t;
         if (t < kRows) det2trk[t] = -1;
-        if (k > 0) vt_matrix(rows, k, st.live, nt, ego.e[k], cal, M, t, kThreads);
+        if (k > 0) vt_matrix(rows, k, st.live, nt, ego + 13 * k, cal, M, t, kThreads);
         __syncthreads();
         // ---- the greedy walk (wave 0) ---------------------------------------------------------------------------------
         if (t < 64) {
@@ -362,6 +407,23 @@ vt_step_kernel(VtRows rows, int n_kf, void* state, double* __restrict__ M, VtEgo
     }
     __syncthreads();
     if (t == 0) *st.hdr = h;
+}
+
+__global__ void __launch_bounds__(kThreads)
+vt_step_kernel(VtRows rows, int n_kf, void* state, double* __restrict__ M, VtEgo ego, KfCalib cal, VtParams prm,
+               const float* __restrict__ k1, const int32_t* __restrict__ k1_cnt, int kept, int finish) {
+    vt_step_keyframes(rows, n_kf, state, M, ego.e[0], cal, prm, k1, k1_cnt, kept, finish);
+}
+
+// Lanes: grid = lanes, one workgroup per lane; an inactive lane's workgroup leaves at once (the mask is uniform).  Lane
+// i keeps ITS keyframe-1 rows (list i of k1, count cnt[i * kCnt + 1]) in its state.
+__global__ void __launch_bounds__(kThreads)
+vt_step_lanes_kernel(VtRows rows, unsigned mask, char* states, size_t stride, double* __restrict__ M, VtLaneTable tab,
+                     VtParams prm, const float* __restrict__ k1, const int32_t* __restrict__ cnt) {
+    const int i = blockIdx.x;
+    if (!lane_on(mask, i)) return;
+    vt_step_keyframes(vt_lane_rows(rows, i), 1, states + (size_t)i * stride, M + (size_t)i * kMaxLive * kRows,
+                      tab.a[i].ego, tab.a[i].cal, prm, k1 + (size_t)i * kRows * kK1, cnt + (size_t)i * kCnt + 1, 0, 0);
 }
 
 __global__ void vt_reset_kernel(void* state, int cap) {
@@ -493,6 +555,71 @@ extern "C" int dodt_vt_track_pairs(dodt_ctx* ctx, void* d_state, const void* d_r
         const int rc = vt_walk(ctx, d_state, rows, n, ego + (size_t)p0 * 13, calib, prm,
                                k1 + (size_t)last * kRows * kK1, cnt + (size_t)last * kCnt + 1, 0, 0);
         if (rc != DODT_OK) return rc;
+    }
+    return DODT_OK;
+}
+
+extern "C" int dodt_vt_lanes_stride(int log_capacity, size_t* stride) {
+    DODT_REQUIRE(log_capacity >= 1 && stride, "dodt_vt_lanes_stride: bad arguments");
+    *stride = (vt_state_bytes(log_capacity) + 255) / 256 * 256;
+    return DODT_OK;
+}
+
+extern "C" int dodt_vt_track_lanes(dodt_ctx* ctx, void* d_states, size_t stride, int n_lanes,
+                                   const unsigned char* active, const void* d_records, int records_f64,
+                                   const int32_t* d_counts, int max_det, const double* p2s, const double* image_whs,
+                                   const double* egos, const double* calibs, double score_threshold, double sigma_l,
+                                   double sigma_h, double sigma_iou, int t_min, int extend_len, int stride_frames) {
+    DODT_REQUIRE(ctx && d_states && n_lanes >= 0, "dodt_vt_track_lanes: bad arguments");
+    const VtParams prm{sigma_l, sigma_h, sigma_iou, t_min, extend_len, stride_frames, 0, 0};  // (encoded rows: float32)
+    DODT_REQUIRE(vt_params_ok(prm), "dodt_vt_track_lanes: extend_len %d, stride %d outside 1..%d", extend_len,
+                 stride_frames, kMaxStep);
+    if (n_lanes == 0) return DODT_OK;
+    DODT_REQUIRE(d_records && d_counts && p2s && image_whs && egos && calibs, "dodt_vt_track_lanes: NULL argument");
+    DODT_REQUIRE(max_det >= 1 && max_det <= kRows, "dodt_vt_track_lanes: max_det %d outside 1..%d", max_det, kRows);
+    DODT_REQUIRE(stride >= vt_state_bytes(1) && stride % alignof(VtTrack) == 0,
+                 "dodt_vt_track_lanes: stride %zu is no distance between two states", stride);
+    const size_t enc_bytes = (size_t)kChunk * kRows * (kTrk + kK1) * sizeof(float) + kChunk * kCnt * sizeof(int32_t);
+    if (ctx->tracking_enc.reserve(enc_bytes) != DODT_OK) return DODT_ERR_HIP;
+    if (ctx->tracking_ws.reserve((size_t)kLaneChunk * kMaxLive * kRows * sizeof(double)) != DODT_OK) return DODT_ERR_HIP;
+    float* trk = static_cast<float*>(ctx->tracking_enc.ptr);
+    float* k1 = trk + (size_t)kChunk * kRows * kTrk;
+    int32_t* cnt = reinterpret_cast<int32_t*>(k1 + (size_t)kChunk * kRows * kK1);
+    double* M = static_cast<double*>(ctx->tracking_ws.ptr);
+    // lane i's keyframe: pair i's keyframe-0 rows (cols 0..15 of its track items, count in cnt[3])
+    const VtRows rows{trk, cnt + 3, 0, kTrk, kCnt, kRows, (size_t)kRows * kTrk};
+    const size_t rec_bytes = records_f64 ? sizeof(double) : sizeof(float);
+    for (int l0 = 0; l0 < n_lanes; l0 += kLaneChunk) {
+        const int n = n_lanes - l0 < kLaneChunk ? n_lanes - l0 : kLaneChunk;
+        LaneCals<kLaneChunk> enc{};
+        VtLaneTable tab{};
+        unsigned mask = 0;
+        for (int i = 0; i < n; ++i) {
+            memcpy(enc.c[i].P.p, p2s + (size_t)(l0 + i) * 12, sizeof(enc.c[i].P.p));
+            enc.c[i].iw = image_whs[2 * (l0 + i)];
+            enc.c[i].ih = image_whs[2 * (l0 + i) + 1];
+            memcpy(tab.a[i].ego, egos + (size_t)(l0 + i) * 13, sizeof(tab.a[i].ego));
+            memcpy(&tab.a[i].cal, calibs + (size_t)(l0 + i) * 42, sizeof(KfCalib));
+            if (!active || active[l0 + i]) mask |= 1u << i;
+        }
+        if (!mask) continue;
+        const char* rec = static_cast<const char*>(d_records) + (size_t)l0 * 2 * max_det * kRecCols * rec_bytes;
+        char* states = static_cast<char*>(d_states) + (size_t)l0 * stride;
+        if (records_f64)
+            hipLaunchKernelGGL((encode_lanes_kernel<double, kLaneChunk>), dim3(n), dim3(kThreads), 0, ctx->stream,
+                               reinterpret_cast<const double*>(rec), d_counts + 2 * l0, max_det, enc, mask,
+                               score_threshold, trk, k1, cnt);
+        else
+            hipLaunchKernelGGL((encode_lanes_kernel<float, kLaneChunk>), dim3(n), dim3(kThreads), 0, ctx->stream,
+                               reinterpret_cast<const float*>(rec), d_counts + 2 * l0, max_det, enc, mask,
+                               score_threshold, trk, k1, cnt);
+        DODT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(vt_iou_lanes_kernel, dim3(kMaxLive * kRows / kThreads, n), dim3(kThreads), 0, ctx->stream,
+                           rows, mask, static_cast<const char*>(states), stride, tab, M);
+        DODT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(vt_step_lanes_kernel, dim3(n), dim3(kThreads), 0, ctx->stream, rows, mask, states, stride, M,
+                           tab, prm, static_cast<const float*>(k1), static_cast<const int32_t*>(cnt));
+        DODT_LAUNCH_CHECK();
     }
     return DODT_OK;
 }

@@ -693,6 +693,53 @@ def kf_track_pairs(ctx, d_state, d_records, d_counts, n_pairs, max_det, p2, imag
         *_kf_tail(params)), 'dodt_kf_track_pairs')
 
 
+KIND_LANES_CHUNK = 8            # lanes per launch triple of dodt_kf_track_lanes / dodt_vt_track_lanes (kLaneChunk)
+
+
+def _lanes_stride(name, log_capacity):
+    n = C.c_size_t()
+    _lib.check(getattr(_lib.load(), name)(int(log_capacity), C.byref(n)), name)
+    return int(n.value)
+
+
+def _kind_lanes(name, ctx, d_states, stride, n_lanes, d_records, d_counts, max_det, p2s, image_whs, ego_rows, calibs,
+                score_threshold, tail, active):
+    """The common arguments of dodt_kf_track_lanes / dodt_vt_track_lanes, checked."""
+    if d_records.dtype not in (np.float32, np.float64):
+        raise ValueError('records must be float32 or float64')
+    n_lanes = int(n_lanes)
+    per_lane = (('p2s', p2s, 12), ('image_whs', image_whs, 2), ('egos', ego_rows, 13), ('calibs', calibs, 42))
+    flat = []
+    for what, a, width in per_lane:
+        a = np.asarray(a, np.float64).reshape(-1)
+        if len(a) != width * n_lanes:
+            raise ValueError('%s: %s needs %d doubles per lane, %d lanes' % (name, what, width, n_lanes))
+        flat.append(_arr(C.c_double, a))
+    act = None
+    if active is not None:
+        if len(active) != n_lanes:
+            raise ValueError('%s: active has %d entries for %d lanes' % (name, len(active), n_lanes))
+        act = (C.c_ubyte * n_lanes)(*[1 if a else 0 for a in active])
+    _lib.check(getattr(ctx.lib, name)(
+        ctx.handle, _p(d_states), int(stride), n_lanes, act, _p(d_records), int(d_records.dtype == np.float64),
+        _p(d_counts), int(max_det), flat[0], flat[1], flat[2], flat[3], float(score_threshold), *tail), name)
+
+
+def kf_lanes_stride(log_capacity):
+    """Bytes between two lanes' Kalman states in one buffer (dodt_kf_lanes_stride)."""
+    return _lanes_stride('dodt_kf_lanes_stride', log_capacity)
+
+
+def kf_track_lanes(ctx, d_states, stride, n_lanes, d_records, d_counts, max_det, p2s, image_whs, ego_rows, calibs,
+                   score_threshold, params, active=None):
+    """One pair per lane, lane i on the Kalman state at d_states + i * stride (dodt_kf_track_lanes): d_records (n_lanes,
+    2, max_det, 17), d_counts (n_lanes, 2); per lane p2s[i] (3, 4), image_whs[i] (w, h), ego_rows[i] (13: the motion into
+    the lane's current keyframe, kf_ego_rows) and calibs[i] (42, temporal_calib); active: None, or one truth value per
+    lane (a lane that is not active keeps its state untouched)."""
+    _kind_lanes('dodt_kf_track_lanes', ctx, d_states, stride, n_lanes, d_records, d_counts, max_det, p2s, image_whs,
+                ego_rows, calibs, score_threshold, _kf_tail(params), active)
+
+
 def kf_flush(ctx, d_state, ego_row, calib42, params):
     """The kept keyframe-1 rows as the final keyframe (ego_row: 13 doubles or None), then finish (dodt_kf_flush)."""
     ego = None if ego_row is None else _arr(C.c_double, np.asarray(ego_row, np.float64).reshape(13))
@@ -775,6 +822,18 @@ def vt_track_pairs(ctx, d_state, d_records, d_counts, n_pairs, max_det, p2, imag
         int(max_det), _arr(C.c_double, np.asarray(p2, np.float64).reshape(12)), float(image_wh[0]),
         float(image_wh[1]), float(score_threshold), _arr(C.c_double, ego_rows), _arr(C.c_double, calib42),
         *_vt_tail(params)), 'dodt_vt_track_pairs')
+
+
+def vt_lanes_stride(log_capacity):
+    """Bytes between two lanes' velocity tracker states in one buffer (dodt_vt_lanes_stride)."""
+    return _lanes_stride('dodt_vt_lanes_stride', log_capacity)
+
+
+def vt_track_lanes(ctx, d_states, stride, n_lanes, d_records, d_counts, max_det, p2s, image_whs, ego_rows, calibs,
+                   score_threshold, params, active=None):
+    """kf_track_lanes for the velocity tracker's states and parameters (dodt_vt_track_lanes)."""
+    _kind_lanes('dodt_vt_track_lanes', ctx, d_states, stride, n_lanes, d_records, d_counts, max_det, p2s, image_whs,
+                ego_rows, calibs, score_threshold, _vt_tail(params), active)
 
 
 def vt_flush(ctx, d_state, ego_row, calib42, params):

@@ -245,12 +245,19 @@ class FramePairPipeline(object):
         score_threshold=0.1, max_sequence_dets=65536) -- pair j's keyframe 0 is keyframe j of the sequence, the last
         pair's keyframe 1 the final one; stride: frames between two keyframes (None: tau of `temporal`, or 1).  Every
         ego_motion entry of its steps is None (parked) or (trans, matrix, delta); tracks_so_far() and end_sequence()
-        return kalman_tracker.Tracker objects; no lanes.
+        return kalman_tracker.Tracker objects.
         With kind='velocity' it is the velocity-extrapolating greedy IoU tracker:
         dict(kind='velocity', sigma_l=0.1, sigma_h=0.5, sigma_iou=0.1, t_min=3, extend_len=3, stride=None,
         score_threshold=0.1, log_capacity=65536) -- keyframes, stride and ego_motion entries as for kind='kalman';
         tracks_so_far() and end_sequence(frame_total=None) return video_detection_iou.interpolate_by_track's track dicts
-        (None: the sequence ends at the last keyframe), kitti_tracking_rows() that module's rows; no lanes, no frame_ids.
+        (None: the sequence ends at the last keyframe), kitti_tracking_rows() that module's rows; no frame_ids.
+        Both kinds take lanes=True beside their keys (DESIGN sections 8g, 8h): pair p of every step is lane p, each lane
+        with its own tracker state, its pair's calibration (p2, image size and recovery rows) and its pair's ego_motion
+        entry -- a lane's own motion associates THAT lane's next keyframe; an inactive lane's entry is ignored and its
+        pending one kept.  Needs sequence=False and pairs_per_step >= 2 (one lane is the plain tracker).  run()'s
+        `active`, tracks_so_far(lane=), end_sequence(lane=, frame_total=) and kitti_tracking_rows(lane=) work per lane under
+        the single forms' rules (frame ids keyframe * stride, no frame_ids); end_sequence(lane=p) flushes lane p with its
+        own calibration and pending ego, downloads and resets it, and leaves the other lanes running.
         bev_input_skip: the fp32 BEV net skips the tiles that no BEV cell inside the camera's frustum reaches (their
         values depend on the weights alone, dodt_extractor_set_input_support); False: full tables.
         bev_frame_tables: with bev_input_skip, every step also filters those tables on the device by the cells that are
@@ -505,7 +512,17 @@ class FramePairPipeline(object):
         # ---- the IoU tracker (opt-in): one sequence's state on the device, launches on the image stream ------------
         if self.tracker is not None:
             tk = self.tracker
-            if self.kalman:
+            if self.kalman and self.lanes:      # one state per pair of a step, in one buffer
+                self.track_state = tracking.KalmanTrackerLanes(self.ctx, self.pairs, tk['sigma_l'], tk['iou_threshold'],
+                                                               tk['max_age'], tk['min_hits'], tk['L'], tk['R_scaler'],
+                                                               log_capacity=tk['max_sequence_dets'],
+                                                               score_threshold=tk['score_threshold'])
+            elif self.velocity and self.lanes:
+                self.track_state = tracking.VelocityTrackerLanes(self.ctx, self.pairs, tk['sigma_l'], tk['sigma_h'],
+                                                                 tk['sigma_iou'], tk['t_min'], tk['extend_len'],
+                                                                 self._kalman_stride(), log_capacity=tk['log_capacity'],
+                                                                 score_threshold=tk['score_threshold'])
+            elif self.kalman:
                 self.track_state = tracking.KalmanTracker(self.ctx, tk['sigma_l'], tk['iou_threshold'], tk['max_age'],
                                                           tk['min_hits'], tk['L'], tk['R_scaler'],
                                                           log_capacity=tk['max_sequence_dets'])
@@ -568,12 +585,22 @@ class FramePairPipeline(object):
             raise ValueError('tracker: max_sequence_dets must be >= 1')
         return tk
 
+    def _kind_lanes(self, t, kind):
+        """The `lanes` key of tracker=dict(kind='kalman' | 'velocity', ...): what it needs, refused before anything
+        touches the context."""
+        lanes = bool(t.pop('lanes', False))
+        if lanes and self.sequence:
+            raise ValueError('tracker: lanes need sequence=False (one lane per pair of a step)')
+        if lanes and self.pairs < 2:
+            raise ValueError("tracker: kind='%s' with lanes=True needs pairs_per_step >= 2 (one lane per pair of a step; "
+                             "one lane is the plain tracker, lanes=False)" % kind)
+        return lanes
+
     def _kalman_args(self, t):
         """tracker=dict(kind='kalman', ...) without its kind."""
-        if t.pop('lanes', False):
-            raise ValueError("tracker: kind='kalman' has no lanes")
+        lanes = self._kind_lanes(t, 'kalman')
         stride = t.pop('stride', None)
-        tk = dict(kind='kalman', lanes=False, score_threshold=float(t.pop('score_threshold', 0.1)),
+        tk = dict(kind='kalman', lanes=lanes, score_threshold=float(t.pop('score_threshold', 0.1)),
                   sigma_l=float(t.pop('sigma_l', 0.0)), iou_threshold=float(t.pop('iou_threshold', 0.1)),
                   max_age=int(t.pop('max_age', 3)), min_hits=int(t.pop('min_hits', 3)),
                   stride=None if stride is None else int(stride), L=float(t.pop('L', 10.0)),
@@ -589,10 +616,9 @@ class FramePairPipeline(object):
 
     def _velocity_args(self, t):
         """tracker=dict(kind='velocity', ...) without its kind."""
-        if t.pop('lanes', False):
-            raise ValueError("tracker: kind='velocity' has no lanes")
+        lanes = self._kind_lanes(t, 'velocity')
         stride = t.pop('stride', None)
-        tk = dict(kind='velocity', lanes=False, score_threshold=float(t.pop('score_threshold', 0.1)),
+        tk = dict(kind='velocity', lanes=lanes, score_threshold=float(t.pop('score_threshold', 0.1)),
                   sigma_l=float(t.pop('sigma_l', 0.1)), sigma_h=float(t.pop('sigma_h', 0.5)),
                   sigma_iou=float(t.pop('sigma_iou', 0.1)), t_min=int(t.pop('t_min', 3)),
                   extend_len=int(t.pop('extend_len', 3)), stride=None if stride is None else int(stride),
@@ -1240,6 +1266,14 @@ class FramePairPipeline(object):
             # every lane's pair in one launch triple: lane i under the calibration the step brought for pair i, the idle
             # lanes of the step left as they are
             gs = st.geoms[::self.fps]
+            if self.kalman or self.velocity:
+                # lane p also under pair p's recovery calibration and ego entry: each lane's own motion associates that
+                # lane's next keyframe (the lane objects keep it), all of it by value in the kernel arguments
+                self.track_state.track_records(self.rec2[r], self.cnt2[r], MAX_DET, [g.p2 for g in gs],
+                                               [g.image_wh for g in gs], st.ego or [None] * self.pairs,
+                                               [g.temporal_rows() for g in gs], active=st.active, ctx=c)
+                self._mark(c, st.step, 'tracker_end')
+                return
             self.track_state.track_records(self.rec2[r], self.cnt2[r], MAX_DET, [g.p2 for g in gs],
                                            [g.image_wh for g in gs], active=st.active, ctx=c)
             self._mark(c, st.step, 'tracker_end')
@@ -1284,9 +1318,9 @@ class FramePairPipeline(object):
         state = self._lane(lane, 'tracks_so_far')
         self.ctx.wait_for(self.img_ctx)             # (the downloads go through the main stream)
         if self.kalman:
-            return self._kalman_tracks(frame_ids, None)
+            return self._kalman_tracks(frame_ids, None, state)
         if self.velocity:
-            return self._velocity_tracks(frame_ids, None)
+            return self._velocity_tracks(frame_ids, None, state)
         return tracking.tracks_from_log(state.read(), self._frame_ids(frame_ids), self.tracker['classes'])
 
     def _kalman_stride(self):
@@ -1294,28 +1328,29 @@ class FramePairPipeline(object):
             return self.tracker['stride']
         return self.temporal['n_frames'] - 1 if self.temporal is not None else 1
 
-    def _kalman_tracks(self, frame_ids, frame_total):
+    def _kalman_tracks(self, frame_ids, frame_total, state=None):
         """The Kalman tracker's finished tracks as kf_pipeline returns them: kalman_tracker.Tracker objects whose dets
         (dicts 'frame_id' = keyframe * stride, 'boxes3d' [h,w,l,x,y,z,ry], 'boxes2d', 'scores'; virtual ones included)
-        are rebuilt from the device's log by interpolation_detections."""
+        are rebuilt from the device's log by interpolation_detections.  state: a lane's tracker (None: the pipeline's)."""
         if frame_ids is not None:
             raise ValueError("frame_ids: the Kalman tracker numbers frames keyframe * stride (tracker=dict(stride=))")
-        fin, log = self.track_state.read()
+        fin, log = (state or self.track_state).read()
         tk = self.tracker
         return tracking.kf_tracks_from_log(fin, log, self._kalman_stride(), frame_total, L=tk['L'],
                                            R_scaler=tk['R_scaler'])
 
-    def _velocity_tracks(self, frame_ids, frame_total):
+    def _velocity_tracks(self, frame_ids, frame_total, state=None):
         """The velocity tracker's finished tracks as interpolate_by_track returns them: dicts 'dets' (dicts 'frame_id' =
         keyframe * stride, 'info', 'boxes2d', 'boxes3d' [h,w,l,x,y,z,ry], 'score', float32; interpolated, predicted and
         extended entries included), 'direction', 'max_score', 'speed', 'extend_len', rebuilt from the device's log
         (tracking.vt_tracks_from_log).  frame_total None: the sequence ends at the last keyframe tracked."""
         if frame_ids is not None:
             raise ValueError("frame_ids: the velocity tracker numbers frames keyframe * stride (tracker=dict(stride=))")
-        fin, log = self.track_state.read()
+        state = state or self.track_state           # (a lane's tracker, or the pipeline's)
+        fin, log = state.read()
         stride = self._kalman_stride()
         if frame_total is None:
-            frame_total = max(self.track_state.header()['keyframe'] - 1, 0) * stride + 1
+            frame_total = max(state.header()['keyframe'] - 1, 0) * stride + 1
         return tracking.vt_tracks_from_log(fin, log, stride, self.tracker['extend_len'], frame_total,
                                            classes=self.tracker['classes'])
 
@@ -1334,8 +1369,20 @@ class FramePairPipeline(object):
             state = self._lane(lane, 'end_sequence')
             if self.pending is not None:
                 raise ValueError('end_sequence: call finish() first (the last step is not tracked yet)')
+            if (self.kalman or self.velocity) and frame_ids is not None:    # (refused before the lane is touched)
+                raise ValueError("frame_ids: the %s tracker numbers frames keyframe * stride (tracker=dict(stride=))"
+                                 % ('Kalman' if self.kalman else 'velocity'))
             lane = int(lane)
+            geom = self.geom0 if self.track_geoms[lane] is None else self.track_geoms[lane]
             self.track_geoms[lane] = None           # (the lane's next video may bring another calibration)
+            if self.kalman or self.velocity:
+                # the lane's last pair's keyframe 1 is its final keyframe, under the lane's calibration and pending ego
+                state.flush(geom.temporal_rows(), ctx=self.img_ctx)
+                self.ctx.wait_for(self.img_ctx)
+                tracks = (self._kalman_tracks if self.kalman else self._velocity_tracks)(frame_ids, frame_total, state)
+                state.reset(ctx=self.img_ctx)
+                self.last_sequence_tracks[lane] = tracks
+                return tracks
             state.flush(ctx=self.img_ctx)
             tracks = self.tracks_so_far(frame_ids, lane=lane)
             state.reset(ctx=self.img_ctx)
@@ -1370,7 +1417,11 @@ class FramePairPipeline(object):
         pipeline the last one of lane `lane`): the reference's KITTI tracking rows, as strings."""
         from dodt_amd.core.dt_evaluator_utils import convert_trajectory_to_kitti_format
         if tracks is None and self.tracker is not None and self.velocity:
-            tracks = self.last_sequence_tracks
+            if self.lanes:
+                self._lane(lane, 'kitti_tracking_rows')
+                tracks = self.last_sequence_tracks[int(lane)]
+            else:
+                tracks = self.last_sequence_tracks
             if tracks is None:
                 raise ValueError('kitti_tracking_rows: no sequence has ended')
         # the velocity tracker's dicts ('dets') go through its own converter (video_detection_iou.py)

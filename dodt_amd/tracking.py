@@ -13,6 +13,8 @@ VelocityTracker / interpolate_by_track: the velocity-extrapolating greedy IoU tr
 (dodt_amd.experiments.video_detection_iou.interpolate_by_track) the same way -- the IoU matrix, the greedy walk, the
 predictions and the track lists in HIP (dodt_amd/csrc/velocity_track.hip), the host function's arguments in and its list of
 track dicts out.
+KalmanTrackerLanes / VelocityTrackerLanes: several sequences of those two trackers side by side, as TrackerLanes for
+the IoU tracker -- one state per lane in one buffer, every lane one pair further per call.
 """
 import numpy as np
 
@@ -238,6 +240,68 @@ class KalmanTracker(object):
         return fin.view(KF_TRACK)[:n_fin], log.view(KF_LOG)[:n_log]
 
 
+class _KindLanes(object):
+    """n_lanes states of one tracker kind in ONE device buffer, `stride` bytes apart: pair i of a step belongs to lane i
+    (one video or camera each), and every lane advances by one pair in one launch triple per ops.KIND_LANES_CHUNK lanes.
+    lane(i) is the kind's single tracker over lane i's slice: reset / flush / header / used_bytes / read as on a state
+    of its own, and its pending_ego -- the lane's last active pair's own motion, which associates the lane's next
+    keyframe.  track_records() is the only way to advance the lanes."""
+
+    def _init_lanes(self, ctx, n_lanes, log_capacity, score_threshold, stride, nbytes, make_lane, d_states=None):
+        """stride, nbytes: the kind's ops entries for them; make_lane(ctx, view): its single tracker over `view`;
+        d_states: None -- the object allocates the buffer --, or n_lanes * stride bytes (or more) that hold the states."""
+        self.ctx = ctx or device.default_context()
+        self.n_lanes, self.cap = int(n_lanes), int(log_capacity)
+        if self.n_lanes < 1:
+            raise ValueError('n_lanes must be >= 1')
+        if self.cap < 1:
+            raise ValueError('log_capacity must be >= 1')
+        self.score_threshold = float(score_threshold)
+        self.stride = stride(self.cap)
+        if d_states is not None and d_states.nbytes < self.n_lanes * self.stride:
+            raise ValueError('d_states: %d bytes, %d lanes need %d' % (d_states.nbytes, self.n_lanes,
+                                                                      self.n_lanes * self.stride))
+        self.d_states = self.ctx.empty((self.n_lanes * self.stride,), np.uint8) if d_states is None else d_states
+        self.lanes = [make_lane(self.ctx, self.d_states.offset(i * self.stride, (nbytes(self.cap),), np.uint8))
+                      for i in range(self.n_lanes)]
+        self.params = self.lanes[0].params
+
+    def lane(self, i):
+        return self.lanes[i]
+
+    def track_records(self, d_records, d_counts, max_det, p2s, image_whs, egos, calibs, active=None, ctx=None):
+        """Encode and track one step: d_records (n_lanes, 2, max_det, 17), d_counts (n_lanes, 2), lane i taking pair i
+        under p2s[i], image_whs[i] and calibs[i] (42, ops.temporal_calib).  egos[i]: pair i's own motion (trans, matrix,
+        delta) from its keyframe 0 to its keyframe 1, or None -- the association of lane i's NEXT keyframe; this
+        keyframe is associated under the one the lane's previous active pair brought.  active: None, or one truth value
+        per lane -- a lane that is not active keeps its state and its pending_ego, and its ego entry is ignored."""
+        egos = list(egos)
+        if len(egos) != self.n_lanes:
+            raise ValueError('track_records: one ego entry per lane')
+        if active is not None and len(active) != self.n_lanes:
+            raise ValueError('track_records: active has %d entries for %d lanes' % (len(active), self.n_lanes))
+        on = [True] * self.n_lanes if active is None else [bool(a) for a in active]
+        into = [ln.pending_ego if a else None for ln, a in zip(self.lanes, on)]
+        self._track_lanes(ctx or self.ctx, self.d_states, self.stride, self.n_lanes, d_records, d_counts, max_det, p2s,
+                          image_whs, ops.kf_ego_rows(into), calibs, self.score_threshold, self.params, active=on)
+        for ln, a, e in zip(self.lanes, on, egos):
+            if a:
+                ln.pending_ego = e
+
+
+class KalmanTrackerLanes(_KindLanes):
+    """_KindLanes of KalmanTracker states (dodt_kf_track_lanes)."""
+
+    def __init__(self, ctx=None, n_lanes=1, sigma_l=0.0, iou_threshold=0.1, max_age=3, min_hits=3, L=10.0,
+                 R_scaler=1.0 / 16, log_capacity=8192, score_threshold=0.1, d_states=None):
+        self._init_lanes(ctx, n_lanes, log_capacity, score_threshold, ops.kf_lanes_stride, ops.kf_state_bytes,
+                         lambda c, view: KalmanTracker(c, sigma_l, iou_threshold, max_age, min_hits, L, R_scaler,
+                                                       log_capacity=log_capacity, d_state=view), d_states)
+
+    def _track_lanes(self, *args, **kw):
+        ops.kf_track_lanes(*args, **kw)
+
+
 def kf_log_det(entry, stride):
     """A log entry's detection as the host's dict (the pipeline's keyframe rows carry nothing else)."""
     d = entry['det']
@@ -443,6 +507,19 @@ class VelocityTracker(object):
         log = self.d_state.offset(_VT_FIN_OFF + self.cap * VT_TRACK.itemsize, (max(n_log, 1) * VT_LOG.itemsize,),
                                   np.uint8).download()
         return fin.view(VT_TRACK)[:n_fin], log.view(VT_LOG)[:n_log]
+
+
+class VelocityTrackerLanes(_KindLanes):
+    """_KindLanes of VelocityTracker states (dodt_vt_track_lanes)."""
+
+    def __init__(self, ctx=None, n_lanes=1, sigma_l=0.1, sigma_h=0.5, sigma_iou=0.1, t_min=3, extend_len=3, stride=1,
+                 log_capacity=8192, score_threshold=0.1, d_states=None):
+        self._init_lanes(ctx, n_lanes, log_capacity, score_threshold, ops.vt_lanes_stride, ops.vt_state_bytes,
+                         lambda c, view: VelocityTracker(c, sigma_l, sigma_h, sigma_iou, t_min, extend_len, stride,
+                                                         log_capacity=log_capacity, d_state=view), d_states)
+
+    def _track_lanes(self, *args, **kw):
+        ops.vt_track_lanes(*args, **kw)
 
 
 def vt_log_det(entry, stride, dtype=np.float32, classes=None):

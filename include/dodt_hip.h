@@ -860,6 +860,30 @@ int dodt_kf_track_pairs(dodt_ctx* ctx, void* d_state, const void* d_records, int
  * list is emptied. */
 int dodt_kf_flush(dodt_ctx* ctx, void* d_state, const double* ego, const double* calib, double sigma_l,
                   double iou_threshold, int max_age, int min_hits, double L, double R_scaler);
+/* Lanes, as dodt_track_lanes: several sequences advance by one pair each in one call.  The distance in bytes
+ * between two lanes' states in one buffer: dodt_kf_state_bytes(log_capacity) rounded up to a multiple of 256.
+ * Needs no context. */
+int dodt_kf_lanes_stride(int log_capacity, size_t* stride);
+/* Pair i of the step belongs to lane i, whose state is the ordinary layout at d_states + i * stride
+ * (dodt_kf_reset, dodt_kf_flush and the host's reader work on that address unchanged).  d_records
+ * (n_lanes, 2, max_det, 17) and d_counts (n_lanes, 2): lane i's pair is pair i; its keyframe-0 rows are the
+ * lane's next keyframe, its keyframe-1 rows are kept in the lane's state.  Host arrays, all read before
+ * the call returns: active, n_lanes bytes (non-zero: the lane takes its pair) or NULL for every lane; p2s
+ * (n_lanes, 12), image_whs (n_lanes, 2), egos (n_lanes, 13: the motion into lane i's current keyframe; the
+ * parked row -- zero translation, the identity, delta 0 -- where it has none) and calibs (n_lanes, 42).
+ * The thresholds and the filter's parameters are the same for all lanes.  An active lane's state
+ * afterwards is byte for byte what dodt_kf_track_pairs(ctx, d_states + i * stride, pair i, n_pairs = 1,
+ * p2s[i], image_whs[i], egos[i], calibs[i], ...) leaves, the status bits included, which are the lane's
+ * own; of an inactive lane no byte is read or written.  Three launches per 8 lanes on ctx's stream, in
+ * the workspaces dodt_kf_track_pairs uses: the encoding (one workgroup per lane), the IoU matrices over
+ * the chip (grid.y = lane) and the step (one workgroup per lane, the body dodt_kf_track_pairs runs); the
+ * lanes' constants -- 440 bytes each -- travel by value in the kernel arguments, which is what bounds a
+ * chunk at 8 lanes.  A chunk without an active lane launches nothing. */
+int dodt_kf_track_lanes(dodt_ctx* ctx, void* d_states, size_t stride, int n_lanes, const unsigned char* active,
+                        const void* d_records, int records_f64, const int32_t* d_counts, int max_det,
+                        const double* p2s, const double* image_whs, const double* egos, const double* calibs,
+                        double score_threshold, double sigma_l, double iou_threshold, int max_age, int min_hits,
+                        double L, double R_scaler);
 /* The filter alone, the step kernel's device functions: n_tracks independent tracks, one lane each.
  * d_x0 (n_tracks, 4) initial positions (rates 0), d_LR (n_tracks, 3) [L0, L, R_scaler]: P0 = L0 I and
  * R = R_scaler L I (the host class keeps the P of its construction when L is set afterwards), d_ops
@@ -920,6 +944,16 @@ int dodt_vt_track_pairs(dodt_ctx* ctx, void* d_state, const void* d_records, int
  * in order, its predictions not cut, and the live list is emptied. */
 int dodt_vt_flush(dodt_ctx* ctx, void* d_state, const double* ego, const double* calib, double sigma_l,
                   double sigma_h, double sigma_iou, int t_min, int extend_len, int stride);
+/* Lanes: dodt_kf_lanes_stride and dodt_kf_track_lanes for this tracker's state -- the same arguments (the
+ * records float32 or float64 by records_f64, the encoded rows float32 as in dodt_vt_track_pairs), the
+ * same three launches per 8 lanes, an active lane left byte for byte as dodt_vt_track_pairs with n_pairs
+ * = 1 leaves it, an inactive one untouched. */
+int dodt_vt_lanes_stride(int log_capacity, size_t* stride);
+int dodt_vt_track_lanes(dodt_ctx* ctx, void* d_states, size_t stride, int n_lanes, const unsigned char* active,
+                        const void* d_records, int records_f64, const int32_t* d_counts, int max_det,
+                        const double* p2s, const double* image_whs, const double* egos, const double* calibs,
+                        double score_threshold, double sigma_l, double sigma_h, double sigma_iou, int t_min,
+                        int extend_len, int stride_frames);
 /* The association's IoU alone (a test entry): d_iou_out (n_tracks, n_dets) float64 = this tracker's
  * cal_transformed_ious of boxes d_last (n_tracks, 7) and d_dets (n_dets, 7), [h,w,l,x,y,z,ry] float64,
  * under one ego row (NULL: none). */

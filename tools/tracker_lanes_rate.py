@@ -2,8 +2,12 @@
 dodt_track_pairs calls on S separate states on the same stream (what a caller has to do without lanes), from HIP events;
 and one lanes pipeline (two videos, two pairs per step) for the record.
 
-    python tools/tracker_lanes_rate.py [--lanes 1,2,4,5,16] [--steps 300] [--warmup 60] [--pipeline-steps 400]
-                                       [--out tracker_lanes_rate.json]
+    python tools/tracker_lanes_rate.py [--kind iou|kalman|velocity] [--lanes 1,2,4,5,16] [--steps 300] [--warmup 60]
+                                       [--pipeline-steps 400] [--out tracker_lanes_rate.json]
+
+--kind kalman / velocity: the same comparison for that tracker -- one dodt_kf_track_lanes / dodt_vt_track_lanes call
+against S dodt_kf_track_pairs / dodt_vt_track_pairs calls, every lane parked under KITTI's calibration -- without the
+pipeline run.
 
 Records: the tests' generator (tests/_tracking_cases.py sequence(), n_obj = 20, 48 pairs per lane, another seed per
 lane), taken in turn -- every lane's state runs on through the wrap, as one long sequence --, resident on the device
@@ -26,7 +30,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import _tracking_cases as tc  # noqa: E402
-from dodt_amd import config, device, synth, tracking  # noqa: E402
+from dodt_amd import config, device, ops, synth, tracking  # noqa: E402
 from dodt_amd.pipeline import FramePairPipeline  # noqa: E402
 
 PARAMS = tc.REFERENCE
@@ -39,7 +43,30 @@ def _stats(us):
                 p90=round(float(us[len(us) * 9 // 10]), 1), steps=len(us))
 
 
-def lanes_against_calls(ctx, n_lanes, steps, warmup, cap):
+KIND_PARAMS = dict(kalman=dict(sigma_l=0.3, iou_threshold=0.1, max_age=3, min_hits=3),
+                   velocity=dict(sigma_l=0.3, sigma_h=0.5, sigma_iou=0.1, t_min=3, extend_len=3, stride=2))
+
+
+def _kind_forms(ctx, kind, n_lanes, cap):
+    """The two forms for kind 'kalman' / 'velocity' -> (lanes object, single trackers, step_lanes(views), step_call(i,
+    views)): every lane parked under KITTI's calibration, the score threshold PARAMS'."""
+    cal = config.KITTI_CALIBRATION
+    c42 = ops.temporal_calib(cal.r0_rect, cal.tr_velo_to_cam)
+    p2s, whs, c42s, parked = [cal.p2] * n_lanes, [cal.image_wh] * n_lanes, [c42] * n_lanes, [None] * n_lanes
+    lanes_cls, single_cls = ((tracking.KalmanTrackerLanes, tracking.KalmanTracker) if kind == 'kalman'
+                             else (tracking.VelocityTrackerLanes, tracking.VelocityTracker))
+    lanes = lanes_cls(ctx, n_lanes, log_capacity=cap, score_threshold=PARAMS[0], **KIND_PARAMS[kind])
+    singles = [single_cls(ctx, log_capacity=cap, **KIND_PARAMS[kind]) for _ in range(n_lanes)]
+
+    def step_lanes(views, max_det):
+        lanes.track_records(*views, max_det, p2s, whs, parked, c42s)
+
+    def step_call(i, views, max_det):
+        singles[i].track_records(*views, 1, max_det, cal.p2, cal.image_wh, [None], c42, score_threshold=PARAMS[0])
+    return lanes, singles, step_lanes, step_call
+
+
+def lanes_against_calls(ctx, n_lanes, steps, warmup, cap, kind='iou'):
     score, high, iou, t_min = PARAMS
     seqs = [tc.sequence(1000 + i, N_PAIRS, n_obj=20, empty=(9, 30)) for i in range(n_lanes)]
     max_det = tc.max_rows(*seqs)
@@ -54,15 +81,25 @@ def lanes_against_calls(ctx, n_lanes, steps, warmup, cap):
                   for k in range(N_PAIRS)]
     cal = config.KITTI_CALIBRATION
     p2s, whs = [cal.p2] * n_lanes, [cal.image_wh] * n_lanes
-    lanes = tracking.TrackerLanes(ctx, n_lanes, cap, high, iou, t_min, score)
-    singles = [tracking.Tracker(ctx, cap, high, iou, t_min, score) for _ in range(n_lanes)]
+    if kind == 'iou':
+        lanes = tracking.TrackerLanes(ctx, n_lanes, cap, high, iou, t_min, score)
+        singles = [tracking.Tracker(ctx, cap, high, iou, t_min, score) for _ in range(n_lanes)]
 
-    def step_lanes(k):
-        lanes.track_records(*step_views[k % N_PAIRS], max_det, p2s, whs)
+        def step_lanes(k):
+            lanes.track_records(*step_views[k % N_PAIRS], max_det, p2s, whs)
 
-    def step_calls(k):
-        for i, tr in enumerate(singles):
-            tr.track_records(*lane_views[k % N_PAIRS][i], 1, max_det, cal.p2, cal.image_wh)
+        def step_calls(k):
+            for i, tr in enumerate(singles):
+                tr.track_records(*lane_views[k % N_PAIRS][i], 1, max_det, cal.p2, cal.image_wh)
+    else:
+        lanes, singles, kind_lanes, kind_call = _kind_forms(ctx, kind, n_lanes, cap)
+
+        def step_lanes(k):
+            kind_lanes(step_views[k % N_PAIRS], max_det)
+
+        def step_calls(k):
+            for i in range(n_lanes):
+                kind_call(i, lane_views[k % N_PAIRS][i], max_det)
 
     times, k = {'lanes': [], 'calls': []}, {'lanes': 0, 'calls': 0}
     for name, fn in (('lanes', step_lanes), ('calls', step_calls)):
@@ -82,8 +119,10 @@ def lanes_against_calls(ctx, n_lanes, steps, warmup, cap):
     # both forms tracked the same pairs: the same states
     same = all(lanes.lane(i).header() == singles[i].header() for i in range(n_lanes))
     status = max(tr.header()['status'] for tr in singles)
-    return dict(lanes=n_lanes, max_det=max_det, us_lanes=_stats(times['lanes']), us_calls=_stats(times['calls']),
-                launches_lanes=3 * -(-n_lanes // 16), launches_calls=3 * n_lanes, same_headers=same, status=status)
+    chunk = 16 if kind == 'iou' else ops.KIND_LANES_CHUNK
+    return dict(kind=kind, lanes=n_lanes, max_det=max_det, us_lanes=_stats(times['lanes']),
+                us_calls=_stats(times['calls']), launches_lanes=3 * -(-n_lanes // chunk), launches_calls=3 * n_lanes,
+                same_headers=same, status=status)
 
 
 def pipeline_rates(ctx, steps, warmup, rounds, points, proposals):
@@ -153,16 +192,18 @@ def main():
     ap.add_argument('--points', type=int, default=120000)
     ap.add_argument('--proposals', type=int, default=1024)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--kind', default='iou', choices=('iou', 'kalman', 'velocity'),
+                    help="which tracker's lanes; the pipeline run is the IoU tracker's only")
     args = ap.parse_args()
     if args.steps < 200:
         ap.error('--steps: at least 200')
     ctx = device.default_context()
     results = dict(tracker=[], pipeline=None)
     for s in (int(v) for v in args.lanes.split(',')):
-        res = lanes_against_calls(ctx, s, args.steps, args.warmup, args.log)
+        res = lanes_against_calls(ctx, s, args.steps, args.warmup, args.log, args.kind)
         print(json.dumps(res), flush=True)
         results['tracker'].append(res)
-    if args.pipeline_steps:
+    if args.pipeline_steps and args.kind == 'iou':
         results['pipeline'] = pipeline_rates(ctx, args.pipeline_steps, 30, args.pipeline_rounds, args.points,
                                              args.proposals)
         print(json.dumps(results['pipeline']), flush=True)

@@ -1,7 +1,8 @@
 """Sustained pairs/s of the headline workload with the IoU tracker off, on, and on together with the temporal module M
 (FramePairPipeline(tracker=, temporal=)), all in one process, and the tracker's own time per step from HIP events.
 
-    python tools/tracker_rate.py [--steps 2000] [--rounds 2] [--modes f32,bf16] [--out tracker_rate.json]
+    python tools/tracker_rate.py [--kind iou|kalman|velocity] [--steps 2000] [--rounds 2] [--modes f32,bf16]
+                                 [--out tracker_rate.json]
 
 Workload (bench.py's headline): tau = 2, 120 000 points, 1 024 proposals, computed heads, one pair per step.  Modes:
 f32 (fp32 convs and heads, no look-ahead -- bench.py's fp32 default) and bf16 (--conv-dtype bf16 --head-dtype bf16
@@ -23,6 +24,12 @@ from dodt_amd import config, device, synth  # noqa: E402
 from dodt_amd.pipeline import FramePairPipeline  # noqa: E402
 
 
+# what the result line shows of the tracker's header, per kind (a missing key is an error, not a gap in the output)
+STATE_KEYS = dict(iou=('n_active', 'n_slots', 'n_log', 'n_fin', 'frame_num', 'status'),
+                  kalman=('n_live', 'next_id', 'keyframe', 'n_log', 'n_fin', 'status'),
+                  velocity=('n_live', 'next_id', 'keyframe', 'n_log', 'n_fin', 'status'))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--steps', type=int, default=2000)
@@ -34,11 +41,17 @@ def main():
     ap.add_argument('--tau', type=int, default=2)
     ap.add_argument('--log', type=int, default=1 << 21)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--kind', default='iou', choices=('iou', 'kalman', 'velocity'),
+                    help='the tracker stage: its default parameters, a parked ego')
     args = ap.parse_args()
     cfg = config.PYRAMID_DODT
     ctx = device.default_context()
     tm = dict(n_frames=args.tau + 1, threshold=0.1, on_conflict='next_best')
     tk = dict(score_threshold=0.1, high_threshold=0.5, iou_threshold=0.005, t_min=3, max_sequence_dets=args.log)
+    if args.kind == 'kalman':
+        tk = dict(kind='kalman', max_sequence_dets=args.log)
+    elif args.kind == 'velocity':
+        tk = dict(kind='velocity', log_capacity=args.log)
     hp = synth.head_params()
     # three distinct pairs, resident before timing (bench.py's ring of batches)
     batches = []
@@ -95,7 +108,7 @@ def main():
         alone = mc.elapsed_ms(0, mc, 1) * 1e3 / 200
         ctx.wait_for(mc)
         hdr = on.track_state.header()
-        res = dict(mode=mode, conv_dtype=dt, head_dtype=dt, lookahead=ahead, steps=args.steps, rounds=args.rounds,
+        res = dict(kind=args.kind, mode=mode, conv_dtype=dt, head_dtype=dt, lookahead=ahead, steps=args.steps, rounds=args.rounds,
                    pairs_per_s_off=[round(r, 1) for r in rates['off']], pairs_per_s_on=[round(r, 1) for r in rates['on']],
                    pairs_per_s_on_m=[round(r, 1) for r in rates['on_m']],
                    ratio_on_off=round(float(np.mean(rates['on']) / np.mean(rates['off'])), 4),
@@ -103,7 +116,7 @@ def main():
                    tracker_us_in_pipeline_median=round(float(np.median(inside)), 1),
                    tracker_us_in_pipeline=[round(v, 1) for v in inside], tracker_us_alone=round(alone, 1),
                    record_rows_last_step=on.d_rec_counts.download().reshape(-1).tolist(),
-                   tracker_state={k: hdr[k] for k in ('n_active', 'n_slots', 'n_log', 'n_fin', 'frame_num', 'status')})
+                   tracker_state={k: hdr[k] for k in STATE_KEYS[args.kind]})
         print(json.dumps(res), flush=True)
         results.append(res)
         for p in pipes.values():
